@@ -7,17 +7,23 @@ update) over the whole grid, inputs already resident in HBM.  Default workload:
 configs[2] of BASELINE.json, the configuration the metric is quoted on -- N1280
 (2560x1920) fp64 with nz=56 levels -- which fits one MI355X (about 16 GB).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N>1 splits the grid into N latitude bands (strong scaling): per step every rank
 all-gathers its sigma moments and swaps theta halo rows with its band neighbours over
 RCCL (the reference's swap_bounds stub, generic/halo_exchange_mod.f90:12-17).
 
-Prints ONE JSON line on rank 0 with the `roofline`, `cpu_baseline` and `parity` objects.
-`value` is nx*ny / (wall time of the K timed steps / K), as the driver's contract asks;
-`value_median` is the same from the median of per-step HIP-event times,
-taken in a second K-step pass so that no event sits between the timed launches.
+Prints ONE JSON line on rank 0.  `value` is nx*ny / (wall time of the K timed steps / K),
+as the driver's contract asks; `ms_per_step` is the wall time of one timed step.  A plain
+run sets up, warms up, times the K steps and reports; --full adds everything else: the
+`roofline`, `secondary`, `cpu_baseline` and `parity` objects, and `value_median`, the
+same as `value` from the median of per-step HIP-event times, taken in a
+second K-step pass so that no event sits between the timed launches.
+
+--dump-outputs DIR writes the state the last timed step left (windspeed, winddir, thc,
+sb_con: what a caller of seabreeze_diag receives) as DIR/<name>.npy in the run's precision.
+The inputs are deterministic, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -46,6 +52,10 @@ from seabreeze_param_amd.bands import BandRunner, row_cost, split_rows  # noqa: 
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 REL_FLOOR = 1e-2        # parity: |a-b| / max(|b|, REL_FLOOR)
+DUMP_BUDGET = 64_000_000   # --dump-outputs: bytes in all
+DUMP_SAMPLE = 1 << 20      # cells kept of every field when the whole fields exceed the budget
+DUMP_SEED = 20170828
+OUTPUT_NAMES = ("windspeed", "winddir", "thc", "sb_con")
 
 
 def algorithmic_bytes(n, n_band, nz, s=8, wind_final=True):
@@ -95,6 +105,22 @@ def relerr(a, b):
     d = np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.maximum(np.abs(b.astype(np.float64)), REL_FLOOR)
     d[np.isnan(a) & np.isnan(b)] = 0.0
     return float(d.max()) if d.size else 0.0
+
+
+def dump_outputs(outdir, fields):
+    """Write `fields` (name -> array, all of one shape) as outdir/<name>.npy.  When they exceed DUMP_BUDGET bytes in
+    all, the same fixed, seeded sample of DUMP_SAMPLE cells is kept of every field, and outdir/sample_index.npy holds
+    the cells' flat indices (float64, exact).  Returns the names written."""
+    os.makedirs(outdir, exist_ok=True)
+    fields = {k: np.ascontiguousarray(a) for k, a in fields.items()}
+    n = next(iter(fields.values())).size
+    if sum(a.nbytes for a in fields.values()) > DUMP_BUDGET:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        fields = {k: a.reshape(-1)[idx] for k, a in fields.items()}
+        fields["sample_index"] = idx.astype(np.float64)
+    for k, a in fields.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return list(fields)
 
 
 def cpu_baseline_and_parity(st, cdist, p, u, v, thetas, nz, gpu_states, timestep, budget_s=20.0, prec=8):
@@ -282,24 +308,32 @@ def main():
     ap.add_argument("--nz", type=int, default=56)
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                     help="working precision (BASELINE configs[3], the N2560 grid, is quoted in fp32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle (baseline AND parity check)")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline per variant")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the CPU oracle's parity check and baseline, per-step event times, per-kernel "
+                         "events and roofline, the replanned passes and the setup kernels (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all: a fixed, "
+                         "seeded sample of cells of a larger grid)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle (baseline AND parity check)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="--full: seconds of CPU baseline per variant")
     ap.add_argument("--comm", choices=("native", "torch", "gloo"), default="native",
                     help="N>1: ghost rows + moments over the library's own RCCL communicator (native; the "
                          "control plane is gloo), over torch.distributed's nccl backend (torch), or over gloo "
                          "(rehearsal of the N>1 code path on a box with fewer GPUs than ranks).  A transport that "
                          "cannot be initialised ends the run with a non-zero exit code: there is no silent fallback.")
     ap.add_argument("--profile-passes", type=int, default=1,
-                    help="extra K-step passes with HIP events around every kernel (0 = events inside the timed pass)")
+                    help="--full: extra K-step passes with HIP events around every kernel (0 = events inside the timed pass)")
     ap.add_argument("--no-fold", action="store_true", help="measurement: k_prep as a kernel of its own (sb_set_fold(ctx, 0))")
     ap.add_argument("--no-replan", action="store_true",
-                    help="skip the extra passes with sb_set_plan_cache(ctx, 0) (profiling runs: rocprofv3's per-kernel averages "
+                    help="--full: skip the extra passes with sb_set_plan_cache(ctx, 0) (profiling runs: rocprofv3's per-kernel averages "
                          "then refer to the stored-plan state alone)")
     ap.add_argument("--watchdog", type=float, default=600.0,
                     help="N>1: seconds a rank may spend in one stage of the run before it gives up (0: never)")
     ap.add_argument("--static-sigma", action="store_true",
                     help="opt-in variant, never the headline: sigma's statistics formed once (sb_set_static_sigma)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
 
@@ -404,16 +438,18 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # ---- parity sequence (single GPU): tn = 1, 2, 15 from a zero state, states kept for the checker ----
+    # ---- parity sequence: tn = 1, 2, 15 from a zero state.  These first calls make the contrast kernel's stored plan,
+    # the state the headline times whatever W is; with --full their states are kept for the checker ----
     gpu_states = None
     dog.mark("parity steps (first band steps: ghost rows and moments travel)")
-    if not args.no_cpu_baseline:
-        gpu_states = {"steps": [], "states": []}
+    if not (args.full and args.no_cpu_baseline):
+        gpu_states = {"steps": [], "states": []} if args.full else None
         for tn in (1, 2, 15):
             runner.step(timestep, tn, sets[tn % NSET])
             runner.synchronize()
-            gpu_states["steps"].append((tn, host_sets[tn % NSET]) if world == 1 else (tn, tn % NSET))
-            gpu_states["states"].append([t.cpu().numpy().copy() for t in (runner.ws, runner.wd, runner.thc, runner.sb_con)])
+            if gpu_states is not None:
+                gpu_states["steps"].append((tn, host_sets[tn % NSET]) if world == 1 else (tn, tn % NSET))
+                gpu_states["states"].append([t.cpu().numpy().copy() for t in (runner.ws, runner.wd, runner.thc, runner.sb_con)])
     band_check = None
     dog.mark("band parity against the oracle")
     if world > 1 and gpu_states is not None:
@@ -442,7 +478,7 @@ def main():
             el = float(tmax.item())
         return el, tn
 
-    events_inside = args.profile_passes == 0
+    events_inside = args.full and args.profile_passes == 0
     tn = 1
     dog.mark("warm-up and timed steps")
     if events_inside:                                   # (the PMC passes: events of the K timed steps only)
@@ -454,11 +490,22 @@ def main():
     else:
         elapsed, tn = timed_pass(tn, W)
 
+    # ---- what the last timed step computed, before any further pass changes the state --------------------------
+    if args.dump_outputs:
+        dog.mark("output dump")
+        local = dict(zip(OUTPUT_NAMES, (t.cpu().numpy() for t in (runner.ws, runner.wd, runner.thc, runner.sb_con))))
+        if world > 1:                                   # every rank's band, in rank (= latitude) order
+            parts = [None] * world
+            dist.all_gather_object(parts, local)
+            local = {k: np.concatenate([pt[k] for pt in parts], axis=0) for k in OUTPUT_NAMES}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, local)
+
     # ---- per-step HIP-event times (median): a K-step pass of its own; only where torch's events sit
     # on the stream the kernels run on (one HIP runtime) ---------------------------------------------------------
     median_ms = None
     dog.mark("event passes")
-    if shared_runtime:
+    if args.full and shared_runtime:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)]
         evs[0].record()
         for i in range(K):
@@ -469,17 +516,18 @@ def main():
         median_ms = float(np.median(step_ms))
 
     # ---- per-kernel HIP-event timing (the library's own events on the stream its kernels run on) -------
-    if not events_inside:
-        ctx.profile_begin(K * args.profile_passes)
-        for _ in range(K * args.profile_passes):
-            runner.step(timestep, tn, sets[tn % NSET]); tn += 1
-    kern_ms, ncalls = ctx.profile_end()
-    counters = ctx.last_counters()
+    if args.full:
+        if not events_inside:
+            ctx.profile_begin(K * args.profile_passes)
+            for _ in range(K * args.profile_passes):
+                runner.step(timestep, tn, sets[tn % NSET]); tn += 1
+        kern_ms, ncalls = ctx.profile_end()
+        counters = ctx.last_counters()
 
     # ---- the same K steps with the contrast kernel's plan remade in every call (sb_set_plan_cache(0)): what a first
     # call, or a call after the ice edge moved, costs.  The headline above is the stored-plan state. -------------
     replan = None
-    if world == 1 and not args.no_replan:
+    if args.full and world == 1 and not args.no_replan:
         ctx.set_plan_cache(False)
         el_r, tn = timed_pass(tn, W)
         ctx.profile_begin(K)
@@ -494,17 +542,6 @@ def main():
     ms_per_step = elapsed / K * 1e3
     value = nx * ny / (elapsed / K)
 
-    n_local = nx * (r1 - r0)
-    n_band_local = int(band[r0:r1].sum())
-    ab = algorithmic_bytes(n_local, n_band_local, nz, s=esz, wind_final=(world == 1))
-    knames = ("k_scan", "k_wind", "k_thc")
-    dom = max(knames, key=lambda k: kern_ms[k])
-    fracs = {k: (ab[k] / (kern_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if kern_ms[k] > 0 else None) for k in knames}
-    lim = min((k for k in knames if fracs[k] is not None), key=lambda k: fracs[k], default=None)
-    dom_gbs = ab[dom] / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
-    call_gbs = ab["total"] / (elapsed / K) / 1e9
-    traffic, traffic_src = pmc_traffic(dom, nx, ny, nz) if world == 1 else (None, None)
-
     result = {
         "metric": "grid-points/sec for sea_breeze_diag on N2560x1920 global grid; achieved HBM GB/s",
         "value": value,
@@ -513,8 +550,11 @@ def main():
         "steps": K,
         "warmup": W,
         "ms_per_step": ms_per_step,
-        "median_ms_per_step": median_ms,
-        "value_median": nx * ny / (median_ms * 1e-3) if median_ms else None,
+    }
+    if args.full:
+        result["median_ms_per_step"] = median_ms
+        result["value_median"] = nx * ny / (median_ms * 1e-3) if median_ms else None
+    result.update({
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -537,7 +577,20 @@ def main():
             "multi_rank_rccl": "unmeasured on hardware so far (one GPU per box in the build pool)" if world == 1 else "this run",
             "input_gen_s": round(gen_s, 1),
         },
-        "roofline": {
+    })
+
+    if args.full:
+        n_local = nx * (r1 - r0)
+        n_band_local = int(band[r0:r1].sum())
+        ab = algorithmic_bytes(n_local, n_band_local, nz, s=esz, wind_final=(world == 1))
+        knames = ("k_scan", "k_wind", "k_thc")
+        dom = max(knames, key=lambda k: kern_ms[k])
+        fracs = {k: (ab[k] / (kern_ms[k] * 1e-3) / 1e9 / HBM_PEAK_GBS if kern_ms[k] > 0 else None) for k in knames}
+        lim = min((k for k in knames if fracs[k] is not None), key=lambda k: fracs[k], default=None)
+        dom_gbs = ab[dom] / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
+        call_gbs = ab["total"] / (elapsed / K) / 1e9
+        traffic, traffic_src = pmc_traffic(dom, nx, ny, nz) if world == 1 else (None, None)
+        result["roofline"] = {
             "bound": "hbm",
             "kernel": dom,
             "achieved": dom_gbs,
@@ -557,12 +610,11 @@ def main():
             "launches_per_call": ctx.last_step_report()["kernel_launches"],
             "replan": replan,
             "rank0_counters": counters,
-        },
-    }
+        }
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["secondary"] = time_setup_kernels(ctx, torch, st, coast, dt, kwin)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, ncores, parity = cpu_baseline_and_parity(st, cdist, p_full, u_full, v_full, (theta_a, theta_b), nz,
                                                      gpu_states, timestep, args.cpu_budget, prec=esz)
         result["parity"] = parity

@@ -48,7 +48,13 @@ def gpu_visible():
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    """tests/golden/<name>.npz with the parts <name>.part<k>.npz a larger fixture is split into
+    (tests/golden/split_fixture.py: no committed file exceeds 1 MiB)."""
+    import glob
+    out = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(glob.escape(GOLDEN), glob.escape(name) + ".part*.npz"))):
+        out.update(np.load(part))
+    return out
 
 
 def relerr(a, b, floor=1e-12):

@@ -21,6 +21,7 @@ sys.path.insert(0, ROOT)
 
 from oracle.pyoracle import Reference  # noqa: E402
 from seabreeze_param_amd import synth  # noqa: E402
+from split_fixture import split_fixture  # noqa: E402
 
 
 def f32(a):
@@ -62,8 +63,10 @@ def diag_case(name, nx, ny, nz, steps, maxdist, timestep_min):
         out[f"wd_final_{s}"] = wd
     path = os.path.join(HERE, f"{name}.npz")
     np.savez_compressed(path, **inp, **out)
+    size = os.path.getsize(path)
+    split_fixture(path)
     band = np.abs(out["cdist_r8"]) <= maxdist
-    print(f"{name}: {os.path.getsize(path) / 1e6:.2f} MB, coast cells {int(out['coast_r8'].sum())}, "
+    print(f"{name}: {size / 1e6:.2f} MB, coast cells {int(out['coast_r8'].sum())}, "
           f"band fraction {band.mean():.3f}, triggers in last step "
           f"{int(((out['output_r8'][-1, 0, :-1] != 0) & (out['output_r8'][-1, 0, :-1] < 1e19)).sum())}")
 
@@ -82,6 +85,7 @@ def coast_case(name, nx, ny, maxdist):
     path = os.path.join(HERE, f"{name}.npz")
     np.savez_compressed(path, **inp, **out)
     print(f"{name}: {os.path.getsize(path) / 1e6:.2f} MB, coast cells {int(out['coast_r8'].sum())}")
+    split_fixture(path)
 
 
 if __name__ == "__main__":

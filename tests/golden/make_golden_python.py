@@ -14,6 +14,8 @@ import os
 import subprocess
 import sys
 
+from split_fixture import split_fixture
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 PYREF = os.path.join(ROOT, "oracle", "_ref", "pyref")
@@ -62,3 +64,4 @@ if __name__ == "__main__":
     env.pop("PYTHONPATH", None)
     subprocess.run([sys.executable, "-c", code], check=True, env=env, cwd="/tmp")
     print(f"{os.path.getsize(path) / 1e6:.2f} MB")
+    split_fixture(path)

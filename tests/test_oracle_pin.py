@@ -2,8 +2,9 @@
 
 * against the committed golden fixtures, which hold outputs of the reference's own
   Fortran compiled unmodified (tests/golden/make_golden.py) -- runs everywhere;
-* against the compiled reference itself (oracle/_ref) where it is present -- bit-exact,
-  both precisions, several grids.
+* against the reference's outputs on several grids, both precisions, bit-exact: recorded
+  as digests (tests/golden/make_golden_refpin.py) -- runs everywhere -- and live against
+  the compiled reference itself (oracle/_ref) where it is present.
 
 The reference ships no tests or known-answer vectors of its own.
 """
@@ -62,32 +63,31 @@ def test_oracle_matches_golden_coast(oracles, prec):
     assert set(np.unique(np.abs(cdist[np.abs(cdist) > 1000]))) <= {12000.0}
 
 
-@pytest.mark.skipif(not reference_available(8), reason="oracle/_ref not built (no /root/reference here)")
+def _refpin_module():
+    import importlib.util
+    import os
+    from conftest import GOLDEN
+    spec = importlib.util.spec_from_file_location("make_golden_refpin", os.path.join(GOLDEN, "make_golden_refpin.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
 @pytest.mark.parametrize("prec", PREC)
 @pytest.mark.parametrize("shape", [(96, 72, 3), (256, 192, 4), (130, 75, 2)])
 def test_oracle_bit_exact_vs_compiled_reference(prec, shape):
-    nx, ny, nz = shape
-    orc, ref = Oracle(prec), Reference(prec)
-    dt = orc.dt
-    st = synth.static_fields(nx, ny, dt, fractional_coast=True)
-    ce_o, ce_r = orc.get_edges(st.landfrac, st.icefrac), ref.get_edges(st.landfrac, st.icefrac)
-    assert np.array_equal(ce_o, ce_r)
-    for maxdist in (180.0, 700.0):
-        cd_o = orc.get_dist(ce_o, st.landfrac, st.lon, st.lat, maxdist=maxdist)
-        cd_r = ref.get_dist(ce_r, st.landfrac, st.lon, st.lat, maxdist=maxdist)
-        assert np.array_equal(cd_o, cd_r)
-    assert np.array_equal(orc.sigmoid(st.sigma), ref.sigmoid(st.sigma))
-    p = synth.pressure_1d(nz, dt)
-    so = [np.zeros((ny, nx), dt) for _ in range(3)]
-    sr = [np.zeros((ny, nx), dt) for _ in range(3)]
-    for tn in range(1, 6):
-        th = synth.theta_step(st, tn, dt)
-        u, v = synth.wind_step(st, nz, tn, dt)
-        oo = orc.diag(tn, p, st.z, st.sigma, th, v, u, cd_o, *so, maxdist=700.0, timestep=90.0)
-        orf = ref.diag(tn, p, st.z, st.sigma, th, v, u, cd_r, *sr, maxdist=700.0, timestep=90.0)
-        assert np.array_equal(oo[:, :-1], orf[:, :-1])
-        for a, b in zip(so, sr):
-            assert np.array_equal(a, b)
+    """Bit for bit what the reference's own wrapper files return on the same inputs: against its outputs recorded as
+    digests (tests/golden/make_golden_refpin.py), and live against oracle/_ref where it is built."""
+    m = _refpin_module()
+    got = m.pin_arrays(Oracle(prec), shape)
+    want = m.recorded()[m.case_key(prec, shape)]
+    assert list(got) == list(want)
+    for k, a in got.items():
+        assert m.digest(a) == want[k], k
+    if reference_available(prec):
+        live = m.pin_arrays(Reference(prec), shape)
+        for k, a in got.items():
+            assert np.array_equal(a, live[k]), "live " + k
 
 
 def test_generic_flavour_equals_wrapper_on_interior(oracles):

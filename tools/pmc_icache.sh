@@ -3,7 +3,7 @@ set -o pipefail
 TAG=$1
 OUT=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 0"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 0"
 for pass in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" \
             "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_IFETCH SQ_IFETCH_LEVEL"; do
     name=$(echo $pass | cut -d' ' -f1)

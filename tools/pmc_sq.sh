@@ -2,7 +2,7 @@ set -o pipefail
 TAG=$1
 OUT=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 0"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --profile-passes 0"
 for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
             "SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS"; do
     name=$(echo $pass | cut -d' ' -f1)

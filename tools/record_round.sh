@@ -12,7 +12,7 @@ O=gpurun_out
 mkdir -p $O
 run() {
     name=$1; shift
-    python bench.py "$@" --cpu-budget 5 2>$O/${TAG}_$name.err | grep "^{" > $O/${TAG}_bench_$name.json
+    python bench.py --full "$@" --cpu-budget 5 2>$O/${TAG}_$name.err | grep "^{" > $O/${TAG}_bench_$name.json
     rc=$?
     python tools/kms.py $O/${TAG}_bench_$name.json
     python - $O/${TAG}_bench_$name.json <<'PY' || { echo "[record_round] PARITY RED in variant $name (bench exit $rc): $O/${TAG}_bench_$name.json" >&2; exit 4; }
