@@ -18,6 +18,10 @@
 !                                inconsistent shapes, before any device work: runs without a GPU)
 !     um                         the Unified Model hook's argument order and bounds (seabreeze_diag_um) on the
 !                                sub-domain the rim of the input fields leaves
+!     um2d                       the UM copy's whole chain on the sub-domain of `um`: get_edges_um -> get_dist_um
+!                                (window +-(halo_size + 3) cells, 2-D coordinates: the broadcast of lon and lat)
+!                                -> seabreeze_diag_um; output.bin: the distance field on tdims_l (its ghost cells
+!                                the edge cells, filled here), then per step sb_con windspeed winddir thc
 !     host                       the reference's call shape: host arrays in, host arrays out (default)
 !     dev                        the fields live on the device (sb_dev_alloc); per step only theta, u, v go up
 !                                and the four outputs come back; seabreeze_diag_dev
@@ -57,7 +61,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | status | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -100,6 +104,8 @@ program dummy_model
     call run_band()
   case ('um')
     call run_um()
+  case ('um2d')
+    call run_um2d()
   case ('status')
     call check_status()
   case default
@@ -208,6 +214,60 @@ contains
     sb_con = 0.
     sb_con(1+hl:nx-hl, 1+hl:ny-hl) = sb_i
   end subroutine run_um
+
+  !---------------------------------------------------------------------------
+  ! The UM copy's setup and diagnostic on the sub-domain of run_um: coordinates as 2-D fields (here the
+  ! broadcast of the input's 1-D lon, lat; a rotated-pole grid passes its true_latitude, true_longitude),
+  ! get_edges_um (ref: UM/vn10.7/sea_breeze_diag.F90:328-446) and get_dist_um (:448-601) with a window of
+  ! +-hl cells, the distance field's ghost cells filled by edge replication (standing in for swap_bounds at a
+  ! limited-area edge), then seabreeze_diag_um every step.
+  !---------------------------------------------------------------------------
+  subroutine run_um2d()
+    use sea_breeze_diag_mod, only : get_edges_um, get_dist_um, seabreeze_diag_um
+    integer :: hs, hl, nxi, nyi, error, i, j
+    real, allocatable :: p_i(:,:,:), u_i(:,:,:), v_i(:,:,:), th_s(:,:), z_s(:,:), sg_s(:,:)
+    real, allocatable :: ws_i(:,:), wd_i(:,:), thc_i(:,:), sb_i(:,:), lf_i(:,:), ci_i(:,:)
+    real, allocatable :: tlat(:,:), tlon(:,:), coast_l(:,:)
+    hs = halo_size + 1; hl = halo_size + 3
+    nxi = nx - 2*hl; nyi = ny - 2*hl
+    if (nxi < 1 .or. nyi < 1) error stop 'um2d mode: grid too small for the ghost frame'
+    allocate(lf_i(nxi,nyi), ci_i(nxi,nyi), tlat(nxi,nyi), tlon(nxi,nyi), coast_l(nxi+2*hl,nyi+2*hl))
+    lf_i = land_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    ci_i = ice_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    do j = 1, nyi
+      tlon(:, j) = lon(1+hl:nx-hl)
+    end do
+    do i = 1, nxi
+      tlat(i, :) = lat(1+hl:ny-hl)
+    end do
+    coast_l = 0.
+    call get_edges_um(coast_l, ci_i, lf_i)
+    call get_dist_um(lf_i, coast_l, tlat, tlon)
+    do j = 1, nyi + 2*hl                         ! ghost cells: the edge cells
+      do i = 1, nxi + 2*hl
+        coast_l(i, j) = coast_l(min(max(i, 1+hl), nxi+hl), min(max(j, 1+hl), nyi+hl))
+      end do
+    end do
+    write (uout) coast_l
+    allocate(p_i(nxi,nyi,nz), u_i(nxi,nyi,nz), v_i(nxi,nyi,nz))
+    allocate(th_s(nxi+2*hs,nyi+2*hs), z_s(nxi+2*hs,nyi+2*hs), sg_s(nxi+2*hs,nyi+2*hs))
+    allocate(ws_i(nxi,nyi), wd_i(nxi,nyi), thc_i(nxi,nyi), sb_i(nxi,nyi))
+    ws_i = 0.; wd_i = 0.; thc_i = 0.; sb_i = 0.
+    p_i = p(1+hl:nx-hl, 1+hl:ny-hl, :)
+    z_s = z(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+    sg_s = sigma(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+    do step = 1, nsteps
+      read (uin) theta, u, v
+      u_i = u(1+hl:nx-hl, 1+hl:ny-hl, :)
+      v_i = v(1+hl:nx-hl, 1+hl:ny-hl, :)
+      th_s = theta(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+      call seabreeze_diag_um(timestep, step, p_i, u_i, v_i, th_s, z_s, sg_s, coast_l, ws_i, wd_i, thc_i, sb_i, error)
+      if (error /= 0) error stop 'um2d mode: seabreeze_diag_um reported an error'
+      write (uout) sb_i, ws_i, wd_i, thc_i
+    end do
+    sb_con = 0.
+    sb_con(1+hl:nx-hl, 1+hl:ny-hl) = sb_i
+  end subroutine run_um2d
 
   !---------------------------------------------------------------------------
   ! Argument checks of the status-returning entry points: they answer error = 1 before any device work

@@ -41,6 +41,7 @@ module sea_breeze_diag_mod
   public :: seabreeze_diag, seabreeze_diag_status, get_edges, get_dist, sigmoid, sb_shutdown
   public :: band_seabreeze_diag, seabreeze_diag_dev, band_seabreeze_diag_dev
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
+  public :: get_edges_um, get_dist_um
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
 #ifdef SB_REAL8
@@ -53,6 +54,8 @@ module sea_breeze_diag_mod
 #define SB_DIAG_DEV       "sb_seabreeze_diag_f64_dev"
 #define SB_BAND_DIAG_DEV  "sb_band_seabreeze_diag_f64_dev"
 #define SB_DIAG_UM        "sb_seabreeze_diag_um_f64"
+#define SB_GET_EDGES_UM   "sb_get_edges_um_f64"
+#define SB_GET_DIST_UM    "sb_get_dist_um_f64"
 #else
   integer, parameter :: rk = c_float
 #define SB_SEABREEZE_DIAG "sb_seabreeze_diag_f32"
@@ -63,6 +66,8 @@ module sea_breeze_diag_mod
 #define SB_DIAG_DEV       "sb_seabreeze_diag_f32_dev"
 #define SB_BAND_DIAG_DEV  "sb_band_seabreeze_diag_f32_dev"
 #define SB_DIAG_UM        "sb_seabreeze_diag_um_f32"
+#define SB_GET_EDGES_UM   "sb_get_edges_um_f32"
+#define SB_GET_DIST_UM    "sb_get_dist_um_f32"
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
@@ -137,6 +142,22 @@ module sea_breeze_diag_mod
       real(rk), value :: maxdist
       real(rk), intent(in) :: coast(*), mask(*), lon(*), lat(*)
       real(rk), intent(out) :: cdist(*)
+    end function
+    integer(c_int) function c_get_edges_um(ctx, nx, ny, hi, hj, lf, ci, coast) bind(C, name=SB_GET_EDGES_UM)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj
+      real(rk), intent(in) :: lf(*), ci(*)
+      real(rk), intent(inout) :: coast(*)
+    end function
+    integer(c_int) function c_get_dist_um(ctx, nx, ny, hi, hj, coast, lf, tlat, tlon, maxdist, cdist) &
+        bind(C, name=SB_GET_DIST_UM)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
+      real(rk), intent(inout) :: cdist(*)
     end function
   end interface
 
@@ -359,6 +380,69 @@ contains
     real, intent(out), contiguous :: cdist(:,:)
     call get_dist_r(coast, landfrac, lon, lat, real(maxdist), cdist, halo_size)
   end subroutine get_dist_i
+
+  !---------------------------------------------------------------------------
+  ! The UM copy's get_edges(mask, icefrac, landfrac) (ref: UM/vn10.7/sea_breeze_diag.F90:328-446) in its argument
+  ! order and bounds: landfrac, icefrac on tdims (nx, ny), mask on tdims_l (nx+2*halo_i, ny+2*halo_j) -- the halo
+  ! widths are read off the shapes.  The land rule is applied to the interior and to the one-cell ring round it; the
+  ! ring's landfrac/icefrac are the domain's edge cells (what a single-domain run's swap_bounds of the mask gives at
+  ! a limited-area edge).  Only the interior of mask is written: its ghost cells are left to the caller's
+  ! swap_bounds (the UM's closing call, :440-442).
+  !---------------------------------------------------------------------------
+  subroutine get_edges_um(mask, icefrac, landfrac)
+    real, intent(inout), contiguous :: mask(:,:)
+    real, intent(in), contiguous :: icefrac(:,:), landfrac(:,:)
+    real, allocatable :: lf(:,:), ci(:,:)
+    integer(c_int) :: nx, ny, hi, hj, rc
+    integer :: i, j
+    nx = size(landfrac, 1); ny = size(landfrac, 2)
+    hi = (size(mask, 1) - nx) / 2; hj = (size(mask, 2) - ny) / 2
+    if (any(shape(icefrac) /= [nx, ny]) .or. hi < 1 .or. hj < 1 .or. &
+        any(shape(mask) /= [nx + 2*hi, ny + 2*hj])) &
+      call fail('get_edges_um: need landfrac, icefrac (nx, ny) and mask (nx+2*halo_i, ny+2*halo_j), halos >= 1', 1_c_int)
+    allocate(lf(nx + 2*hi, ny + 2*hj), ci(nx + 2*hi, ny + 2*hj))
+    do j = 1, ny + 2*hj
+      do i = 1, nx + 2*hi
+        lf(i, j) = landfrac(min(max(i - hi, 1), nx), min(max(j - hj, 1), ny))
+        ci(i, j) = icefrac(min(max(i - hi, 1), nx), min(max(j - hj, 1), ny))
+      end do
+    end do
+    call ensure_ctx()
+    rc = c_get_edges_um(ctx, nx, ny, hi, hj, lf, ci, mask)
+    if (rc /= 0) call fail('get_edges_um', rc)
+    deallocate(lf, ci)
+  end subroutine get_edges_um
+
+  !---------------------------------------------------------------------------
+  ! The UM copy's get_dist(landfrac, coast) (ref: UM/vn10.7/sea_breeze_diag.F90:448-601) in its argument order:
+  ! coast on tdims_l (nx+2*halo_i, ny+2*halo_j) is overwritten with the signed coast distance, as the UM does
+  ! (:590-594); landfrac and the 2-D coordinates true_latitude, true_longitude (degrees, trignometric_mod's fields,
+  ! :523-524) on tdims (nx, ny).  The window is +-halo_i columns x +-halo_j rows (:515-516), read off the shapes.
+  ! maxdist: the UM's parameter of 180 km when absent.  Only the interior of coast is written: its ghost cells are
+  ! left to the caller's swap_bounds (:598-600).
+  !---------------------------------------------------------------------------
+  subroutine get_dist_um(landfrac, coast, true_latitude, true_longitude, maxdist)
+    real, intent(in), contiguous :: landfrac(:,:), true_latitude(:,:), true_longitude(:,:)
+    real, intent(inout), contiguous :: coast(:,:)
+    real, intent(in), optional :: maxdist
+    real, allocatable :: c2(:,:)
+    real :: md
+    integer(c_int) :: nx, ny, hi, hj, rc
+    nx = size(landfrac, 1); ny = size(landfrac, 2)
+    hi = (size(coast, 1) - nx) / 2; hj = (size(coast, 2) - ny) / 2
+    if (any(shape(true_latitude) /= [nx, ny]) .or. any(shape(true_longitude) /= [nx, ny]) .or. hi < 0 .or. hj < 0 &
+        .or. any(shape(coast) /= [nx + 2*hi, ny + 2*hj])) &
+      call fail('get_dist_um: need landfrac, true_latitude, true_longitude (nx, ny), coast (nx+2*halo_i, ny+2*halo_j)', &
+                1_c_int)
+    md = 180.
+    if (present(maxdist)) md = maxdist
+    allocate(c2(size(coast, 1), size(coast, 2)))
+    c2 = coast                                   ! (the coast mask the distance field replaces)
+    call ensure_ctx()
+    rc = c_get_dist_um(ctx, nx, ny, hi, hj, c2, landfrac, true_latitude, true_longitude, real(md, rk), coast)
+    if (rc /= 0) call fail('get_dist_um', rc)
+    deallocate(c2)
+  end subroutine get_dist_um
 
   !---------------------------------------------------------------------------
   ! ref: generic/sea_breeze_diag.f90:457-481

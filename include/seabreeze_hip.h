@@ -358,6 +358,69 @@ int sb_dist_window_f64(int nlons, int nlats, const double *lon, const double *la
 int sb_dist_window_f32(int nlons, int nlats, const float *lon, const float *lat, float maxdist, int *k);
 
 /* -------------------------------------------------------------------------------- */
+/* get_edges -- UM vn10.7 layout (tdims_l), for curvilinear / rotated-pole grids      */
+/* replaces: get_edges(mask, icefrac, landfrac)                                      */
+/*           ref: UM/vn10.7/sea_breeze_diag.F90:328-446 (get_edges)                  */
+/* landfrac, icefrac, coast: (nx+2*halo_i, ny+2*halo_j), interior at offset           */
+/* (halo_i, halo_j); halo_i, halo_j >= 1.  The ghost cells of landfrac and icefrac    */
+/* are filled by the caller (what the UM's swap_bounds of the mask amounts to,        */
+/* :408-410).  The ice-aware rule (rule 1 of sb_get_edges_*, :390-403) is applied to  */
+/* the interior and the one-cell ring round it, the Sobel is sb_get_edges_*'s         */
+/* (:416-435), 0/1 goes into the interior of coast; its ghost cells are NOT touched   */
+/* (the UM's closing swap_bounds, :440-442, is the caller's).                         */
+/* -------------------------------------------------------------------------------- */
+int sb_get_edges_um_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                        const double *landfrac, const double *icefrac, double *coast);
+int sb_get_edges_um_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                        const float *landfrac, const float *icefrac, float *coast);
+int sb_get_edges_um_f64_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                        const double *landfrac, const double *icefrac, double *coast, void *stream);
+int sb_get_edges_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                        const float *landfrac, const float *icefrac, float *coast, void *stream);
+
+/* -------------------------------------------------------------------------------- */
+/* get_dist -- UM vn10.7 layout, 2-D per-cell coordinates                             */
+/* replaces: get_dist(landfrac, coast)                                               */
+/*           ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)                   */
+/* coast, cdist: (nx+2*halo_i, ny+2*halo_j); landfrac, true_lat, true_lon: interior   */
+/* (nx, ny) fields, coordinates in degrees (trignometric_mod's true_latitude,         */
+/* true_longitude, :523-524).  Window: +-halo_i columns x +-halo_j rows (:515-516),   */
+/* 0 <= halo_i, halo_j <= 31 (else SB_ERR_ARG).  Sources (coast > 0) and targets are  */
+/* interior cells only: the UM's scatter reaches into the halo but swap_bounds        */
+/* discards those writes (:584-598), so there is no wrap and no clamp, and on a       */
+/* multi-rank run every rank sees its own coast cells only.  Only the interior of     */
+/* cdist is written; its ghost cells are left to the caller's swap_bounds /           */
+/* sb_fill_ghosts_*.  cdist == coast (in place, as the UM overwrites coast) works.    */
+/* Arithmetic in the working precision with the UM's constants R = 6370.9989,         */
+/* pi = 3.1415926, r2d = 180/pi, d2r = pi/180 (:509-512): the source longitude         */
+/* l1 = d2r*(lon - 360) where lon > 180 (:552-556), the target's                      */
+/* l2 = d2r*(r2d*lam1 - 360) where r2d*lam1 > 180, lam1 = d2r*lon (:560-564),         */
+/* c = 2R atan2(sqrt(a), sqrt(1-a)) + 0.5, signed by landfrac > 0 (:565-574), and the  */
+/* sweep-order reset |cdist| > 2*maxdist -> 12000 (:578; rows outer, columns inner)   */
+/* applied to the minimum over sources swept at or before the target.  12000: no     */
+/* coast cell in the window.  maxdist is a parameter of 180 km in the UM.             */
+/* The _dev forms take device pointers for all five fields and enqueue without        */
+/* synchronising; nothing is derived from the coordinates on the host.                */
+/* The UM file cannot be compiled outside the UM: these entry points follow its text. */
+/* -------------------------------------------------------------------------------- */
+int sb_get_dist_um_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                       const double *coast, const double *landfrac,
+                       const double *true_lat, const double *true_lon,
+                       double maxdist, double *cdist);
+int sb_get_dist_um_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                       const float *coast, const float *landfrac,
+                       const float *true_lat, const float *true_lon,
+                       float maxdist, float *cdist);
+int sb_get_dist_um_f64_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                       const double *coast, const double *landfrac,
+                       const double *true_lat, const double *true_lon,
+                       double maxdist, double *cdist, void *stream);
+int sb_get_dist_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
+                       const float *coast, const float *landfrac,
+                       const float *true_lat, const float *true_lon,
+                       float maxdist, float *cdist, void *stream);
+
+/* -------------------------------------------------------------------------------- */
 /* swap_bounds -- ghost-cell fill of one latitude band of a multi-GPU run            */
 /* replaces: subroutine swap_bounds(field, halo_size)                                */
 /*           ref: generic/halo_exchange_mod.f90:12-17 (an empty stub; the UM copy    */

@@ -143,6 +143,7 @@ struct sb_ctx {
     int rep_launches = 0, rep_rccl = 0, rep_groups = 0, rep_copies = 0;
     // workspace (grow-only)
     DevBuf t0, bandbits, clsbits, tiles, vecs, nws, nwd, coastbits, tile_list, seg_list, stamps, jobcopy, plan;
+    DevBuf umbits;                      // the coast bit plane of sb_get_dist_um_*
     // the strip kernel's plan (sb_strip_kernel.hip): [64 bytes: number of the last call whose band plane changed |
     // ncu x SB_PLAN_STRIDE]; plan_key: the geometry it was made for; call_seq numbers the diag calls
     int plan_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1093,6 +1094,71 @@ int get_dist_host(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, cons
     return s.finish();
 }
 
+// UM vn10.7 coast setup on the tdims_l layout (ref: UM/vn10.7/sea_breeze_diag.F90:328-601): fields with ghost cells are
+// (nx + 2*hi) x (ny + 2*hj); the ghost cells of the outputs are left to the caller's swap_bounds
+template <typename T>
+int get_edges_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast, void *stream) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || !lf || !ci || !coast) return fail(c, SB_ERR_ARG, "bad get_edges_um arguments");
+    if (hi < 1 || hj < 1) return fail(c, SB_ERR_ARG, "get_edges_um: halo_i and halo_j must be >= 1 (the Sobel reads the ghost ring)");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, sb_launch_edges_um<T>(lf, ci, coast, nx, ny, hi, hj, st));
+    return SB_OK;
+}
+
+template <typename T>
+int get_edges_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || !lf || !ci || !coast) return fail(c, SB_ERR_ARG, "bad get_edges_um arguments");
+    if (hi < 1 || hj < 1) return fail(c, SB_ERR_ARG, "get_edges_um: halo_i and halo_j must be >= 1 (the Sobel reads the ghost ring)");
+    const size_t n = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    Stager s(c);
+    T *dl = s.in(lf, n), *dc = s.in(ci, n), *dco = s.in(coast, n);     // (coast in as well: its ghost cells stay)
+    if (s.rc) return s.rc;
+    int rc = get_edges_um_dev<T>(c, nx, ny, hi, hj, dl, dc, dco, nullptr);
+    if (rc) return rc;
+    s.back(coast, dco, n);
+    return s.finish();
+}
+
+template <typename T>
+int check_dist_um(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat, const T *tlon,
+                  T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || !coast || !lf || !tlat || !tlon || !cdist) return fail(c, SB_ERR_ARG, "bad get_dist_um arguments");
+    if (hi < 0 || hi > 31 || hj < 0 || hj > 31)
+        return fail(c, SB_ERR_ARG, "get_dist_um: the window is +-halo_i x +-halo_j with 0 <= halo_i, halo_j <= 31");
+    return SB_OK;
+}
+
+template <typename T>
+int get_dist_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat, const T *tlon,
+                    T maxdist, T *cdist, void *stream) {
+    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    // the coordinates are device fields: nothing is derived from them on the host, nothing is kept between calls
+    if ((rc = ensure(c, c->umbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, sb_launch_dist_um<T>(coast, lf, tlat, tlon, cdist, nx, ny, hi, hj, maxdist, (uint64_t *)c->umbits.p, st));
+    return SB_OK;
+}
+
+template <typename T>
+int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat,
+                     const T *tlon, T maxdist, T *cdist) {
+    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    const size_t n = (size_t)nx * ny, nl = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    Stager s(c);
+    // (cdist in as well: its ghost cells stay; with cdist == coast both copies hold the same field)
+    T *dco = s.in(coast, nl), *dl = s.in(lf, n), *dla = s.in(tlat, n), *dlo = s.in(tlon, n), *dcd = s.in((const T *)cdist, nl);
+    if (s.rc) return s.rc;
+    rc = get_dist_um_dev<T>(c, nx, ny, hi, hj, dco, dl, dla, dlo, maxdist, dcd, nullptr);
+    if (rc) return rc;
+    s.back(cdist, dcd, nl);
+    return s.finish();
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1177,7 +1243,7 @@ int sb_destroy(sb_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
-                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan})
+                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -1349,6 +1415,21 @@ int sb_last_counters(sb_ctx *c, long long counters[4]) {
     int sb_get_dist_##SFX##_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const T *lon,             \
                                 const T *lat, T maxdist, int kwin, T *cdist, void *stream) {                        \
         return get_dist_dev<T>(c, nx, ny, coast, mask, lon, lat, maxdist, kwin, cdist, stream);                     \
+    }                                                                                                              \
+    int sb_get_edges_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast) {       \
+        return get_edges_um_host<T>(c, nx, ny, hi, hj, lf, ci, coast);                                              \
+    }                                                                                                              \
+    int sb_get_edges_um_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast,  \
+                                    void *stream) {                                                                 \
+        return get_edges_um_dev<T>(c, nx, ny, hi, hj, lf, ci, coast, stream);                                       \
+    }                                                                                                              \
+    int sb_get_dist_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf,                \
+                             const T *tlat, const T *tlon, T maxdist, T *cdist) {                                   \
+        return get_dist_um_host<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, maxdist, cdist);                       \
+    }                                                                                                              \
+    int sb_get_dist_um_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf,          \
+                                   const T *tlat, const T *tlon, T maxdist, T *cdist, void *stream) {               \
+        return get_dist_um_dev<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, maxdist, cdist, stream);                \
     }                                                                                                              \
     int sb_dist_window_##SFX(int nx, int ny, const T *lon, const T *lat, T maxdist, int *k) {                       \
         return dist_window<T>(nx, ny, lon, lat, maxdist, k);                                                        \

@@ -89,6 +89,16 @@ hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *
                           int nearest,                        // 1: nearest hit per side of a source row only (see k_dist_bits)
                           hipStream_t st);
 
+// the UM vn10.7 copy's coast setup on the tdims_l layout (sb_um_coast_kernels.hip): lf, ci, coast are
+// (nx + 2hi) x (ny + 2hj) with hi, hj >= 1; coast's interior is written, its ghost cells are not
+template <typename T>
+hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st);
+// coast, cdist: (nx + 2hi) x (ny + 2hj), 0 <= hi, hj <= 31, cdist may be coast; landfrac, tlat, tlon: nx x ny (degrees);
+// bits: ny * ceil(nx/64) words of workspace
+template <typename T>
+hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
+                             int hi, int hj, T maxdist, uint64_t *bits, hipStream_t st);
+
 // local part of swap_bounds: E-W periodic ghost columns, pole-side ghost rows replicate the edge row
 template <typename T>
 hipError_t sb_launch_fill_ghosts(T *field, int nx, int ny, int h, int south, int north, hipStream_t st);

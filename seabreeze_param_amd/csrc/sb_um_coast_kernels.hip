@@ -1,0 +1,254 @@
+// sb_um_coast_kernels.hip -- the UM vn10.7 copy's coast setup on curvilinear (rotated-pole) grids, gfx950.
+//
+//   k_edges_um     binary 3x3 Sobel of the ice-aware land mask on the tdims_l layout: the rule is applied to the
+//                  interior and the one-cell ring of ghost cells round it (what swap_bounds filled), 0/1 goes into the
+//                  interior only                          ref: UM/vn10.7/sea_breeze_diag.F90:386-440 (get_edges)
+//   k_coastbits_um coast > 0 of the interior, one 64-bit word per 64 columns (a wave ballot)
+//   k_dist_um      signed haversine distance to the nearest interior coast cell within +-halo_i columns x +-halo_j
+//                  rows, from per-cell coordinates     ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)
+//
+// The UM's get_dist is a scatter from interior coast cells into a window that reaches into the halo; swap_bounds then
+// throws the halo writes away (:584-598).  So sources and targets are interior cells only -- no wrap, no clamp -- and
+// the gather below keeps the scatter's result, the sweep-order reset |cdist| > 2*maxdist -> 12000 (:578) included, by
+// keeping the minimum over sources swept at or before the target (rows outer, columns inner) apart from the minimum
+// over sources swept after it, as k_dist does (sb_coast_kernels.hip).
+#include "sb_launch.hpp"
+
+template <typename T>
+__device__ __forceinline__ int land_rule_um(T l, T c) {
+    if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
+    return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
+}
+
+// k_edges' block scheme (256 columns x UM_EDGE_ROWS rows per workgroup, land flags of the block and its ring in LDS),
+// with the interior offset by (hi, hj) inside the ghost-celled field.  The ring cells are ghost cells of the caller.
+#define UM_EDGE_ROWS 16
+#define UM_EDGE_PITCH 264
+template <typename T>
+__global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, const T *__restrict__ ci, T *__restrict__ coast,
+                                                  int nx, int ny, int hi, int hj) {
+    __shared__ unsigned char s_land[(UM_EDGE_ROWS + 2) * UM_EDGE_PITCH];
+    const int NX = nx + 2 * hi, NY = ny + 2 * hj;
+    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * UM_EDGE_ROWS;
+    constexpr int NCELL = (UM_EDGE_ROWS + 2) * 258, NIT = (NCELL + 255) / 256;
+    T l[NIT], c[NIT];
+#pragma unroll
+    for (int j = 0; j < NIT; ++j) {                      // every load issued before the first is used
+        const int i = threadIdx.x + 256 * j, r = i < NCELL ? i / 258 : 0, cc = i - (i / 258) * 258;
+        // field column / row of interior cell (x0 - 1 + cc, y0 - 1 + r); cells past the ring are clamped into the
+        // field (their flags are never read for a written cell)
+        int X = x0 - 1 + cc + hi, Y = y0 - 1 + r + hj;
+        X = X < NX ? X : NX - 1;
+        Y = Y < NY ? Y : NY - 1;
+        const size_t o = (size_t)Y * NX + X;
+        l[j] = lf[o];
+        c[j] = ci[o];
+    }
+#pragma unroll
+    for (int j = 0; j < NIT; ++j) {
+        const int i = threadIdx.x + 256 * j, r = i / 258, cc = i - r * 258;
+        if (i < NCELL) s_land[r * UM_EDGE_PITCH + cc] = (unsigned char)land_rule_um(l[j], c[j]);
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= nx) return;
+    // the Sobel of k_edges: px = sum_a (1,2,1)(a) * (m[a][2] - m[a][0]), py = sum_b (1,2,1)(b) * (m[2][b] - m[0][b])
+    // (ref: UM :420-427 with weight = reshape((/-1,-2,-1, 0,0,0, 1,2,1/),(3,3)))
+    int m[3][3];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) m[a + 1][b] = s_land[a * UM_EDGE_PITCH + threadIdx.x + b];
+#pragma unroll
+    for (int r = 0; r < UM_EDGE_ROWS; ++r) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            m[0][b] = m[1][b];
+            m[1][b] = m[2][b];
+            m[2][b] = s_land[(r + 2) * UM_EDGE_PITCH + threadIdx.x + b];
+        }
+        const int px = (m[0][2] - m[0][0]) + 2 * (m[1][2] - m[1][0]) + (m[2][2] - m[2][0]);
+        const int py = (m[2][0] - m[0][0]) + 2 * (m[2][1] - m[0][1]) + (m[2][2] - m[0][2]);
+        const int y = y0 + r;
+        if (y < ny) coast[(size_t)(y + hj) * NX + x + hi] = (px == 0 && py == 0) ? T(0) : T(1);   // ref: UM :429-435
+    }
+}
+
+// coast > 0 of the interior, one word per 64 columns of a row (bits past nx are zero)
+#define UM_BITS_ROWS 8
+template <typename T>
+__global__ __launch_bounds__(256) void k_coastbits_um(const T *__restrict__ coast, uint64_t *__restrict__ bits,
+                                                      int nx, int ny, int hi, int hj, int nw) {
+    const int NX = nx + 2 * hi;
+    const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * UM_BITS_ROWS;
+    T v[UM_BITS_ROWS];
+#pragma unroll
+    for (int r = 0; r < UM_BITS_ROWS; ++r) {
+        const int y = y0 + r < ny ? y0 + r : ny - 1;                 // (clamped: every load unconditional)
+        v[r] = coast[(size_t)(y + hj) * NX + (x < nx ? x : nx - 1) + hi];
+    }
+#pragma unroll
+    for (int r = 0; r < UM_BITS_ROWS; ++r) {
+        const uint64_t w = __ballot(x < nx && v[r] > T(0));          // ref: UM :551
+        if ((threadIdx.x & 63) == 0 && (x >> 6) < nw && y0 + r < ny) bits[(size_t)(y0 + r) * nw + (x >> 6)] = w;
+    }
+}
+
+// 64 bits of row `rw` of the plane from column p on (p may be negative; columns outside 0 .. 64*nw - 1 read as 0)
+__device__ __forceinline__ uint64_t um_row_bits64(const uint64_t *__restrict__ rw, int p, int nw) {
+    const int w0 = p >= 0 ? p >> 6 : -((63 - p) >> 6), o = p - 64 * w0;      // floor division
+    const uint64_t a = (w0 >= 0 && w0 < nw) ? rw[w0] : 0ull;
+    const uint64_t b = (w0 + 1 >= 0 && w0 + 1 < nw) ? rw[w0 + 1] : 0ull;
+    return o ? (a >> o) | (b << (64 - o)) : a;
+}
+
+// The gather.  A workgroup holds UM_DIST_TY target rows of 64 columns (one wave per row).  Its reach is the
+// (64 + 2hi) x (UM_DIST_TY + 2hj) cells round them; every reach row is one 128-bit string of coast bits in LDS, starting at
+// column x0 - hi.  There is no separability on a curvilinear grid -- no per-row cos(phi), no per-column half-angle
+// table -- so the per-cell terms of a SOURCE (sin and cos of half its latitude, cos of its latitude, its longitude l1)
+// are formed in LDS once per staged coast cell (cells without a coast bit read no coordinates), UM_DIST_CH reach rows at a
+// time; a target forms its own (cos(phi), half angles, l2) in registers.
+//
+// Cuts that hold without separability:
+//   * c = 2R atan2(sqrt(a), sqrt(1-a)) + 0.5 grows with a: min(a) per class (before / after the target in the sweep), one
+//     atan2 per class per target;
+//   * a workgroup with no coast bit in its reach writes 12000 and leaves before it reads any coordinate (four
+//     workgroups in five on the BASELINE masks); reach rows and staging chunks without a coast bit are skipped.
+// The haversine term is not monotone along a row of a curvilinear grid, so every hit in the window is visited (no
+// nearest-hit cut).
+//
+// fp64: sin((phi_s - phi_t)/2) = sin(phi_s/2) cos(phi_t/2) - cos(phi_s/2) sin(phi_t/2) from the staged half angles (two
+// rounded products, no fma: for the same latitude the difference is exactly zero); absolute error ~2e-16, i.e. ~1e-13
+// relative in a distance of one 0.1-degree cell.  The longitude difference l1 - l2 takes the sine as written: l1 and l2
+// are formed differently (UM :552-563), so a cell's own l1 - l2 need not vanish, and the half-angle identity would not
+// reproduce the few-ulp differences that decide distances near a cell.  fp32 takes both sines as written.
+#define UM_DIST_TY 4
+#define UM_DIST_CH 8
+#define UM_DIST_W (64 + 2 * 31)
+template <typename T>
+__global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                           const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                           T *__restrict__ cdist, int nx, int ny, int hi, int hj, int nw,
+                                                           T maxdist) {
+    __shared__ uint64_t s_bw[UM_DIST_TY + 62][2];
+    __shared__ T s_sh[UM_DIST_CH][UM_DIST_W], s_ch[UM_DIST_CH][UM_DIST_W], s_cp[UM_DIST_CH][UM_DIST_W], s_l1[UM_DIST_CH][UM_DIST_W];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, tid = threadIdx.x;
+    const int x0 = blockIdx.x * 64, y0 = blockIdx.y * UM_DIST_TY;
+    const int xx = x0 + tx, yy = y0 + ty;
+    const bool valid = xx < nx && yy < ny;
+    const int NX = nx + 2 * hi;
+    const int RR = UM_DIST_TY + 2 * hj, W = 64 + 2 * hi, L = 2 * hi + 1;
+    const T big = T(12000.);
+    // ---- the coast bits of the reach, and which reach rows hold any ----
+    bool any = false;
+    for (int i = tid; i < 2 * RR; i += 64 * UM_DIST_TY) {
+        const int r = i >> 1, j = i & 1, ys = y0 - hj + r;
+        uint64_t v = 0;
+        if (ys >= 0 && ys < ny) {
+            v = um_row_bits64(bits + (size_t)ys * nw, x0 - hi + 64 * j, nw);
+            if (j) v &= hi ? (1ull << (2 * hi)) - 1ull : 0ull;      // (reach: W = 64 + 2hi columns)
+        }
+        s_bw[r][j] = v;
+        any |= v != 0;
+    }
+    if (!__syncthreads_or(any ? 1 : 0)) {                          // no coast cell in reach: no coordinates, no trigonometry
+        if (valid) cdist[(size_t)(yy + hj) * NX + xx + hi] = big;
+        return;
+    }
+    // ---- this target's own terms ----
+    const T pi = T(3.1415926), r2d = T(180.0) / pi, d2r = pi / T(180.0);      // ref: UM :509-512
+    const T R = T(6370.9989);
+    T phit = T(0), cost = T(0), sht = T(0), cht = T(0), l2 = T(0), lf = T(0);
+    if (valid) {
+        const size_t o = (size_t)yy * nx + xx;
+        phit = tlat[o] * d2r;                                      // phi1 (ref: UM :524)
+        const T lam1 = tlon[o] * d2r;                              // lam1 (:523)
+        l2 = ((r2d * lam1) > T(180.)) ? d2r * ((r2d * lam1) - T(360.)) : lam1;   // ref: UM :560-564
+        cost = cos(phit);
+        if constexpr (sizeof(T) == 8) { sht = sin(phit / T(2)); cht = cos(phit / T(2)); }
+        lf = landfrac[o];
+    }
+    const T none = T(4);                                           // a <= 1: "no source in this class"
+    T a_early = none, a_late = none;
+    const uint64_t lmask = (1ull << L) - 1ull;                     // (L <= 63)
+    // ---- UM_DIST_CH reach rows at a time: stage the coast cells' terms, then every wave walks the rows of its window ----
+    for (int r0 = 0; r0 < RR; r0 += UM_DIST_CH) {
+        const int nr = RR - r0 < UM_DIST_CH ? RR - r0 : UM_DIST_CH;
+        bool chunk = false;                                        // workgroup-uniform: the bits are in LDS
+        for (int r = 0; r < nr; ++r) chunk |= (s_bw[r0 + r][0] | s_bw[r0 + r][1]) != 0;
+        if (!chunk) continue;
+        __syncthreads();                                           // (the chunk before is read by every wave)
+        for (int i = tid; i < nr * W; i += 64 * UM_DIST_TY) {
+            const int r = i / W, cc = i - r * W;
+            if (!((s_bw[r0 + r][cc >> 6] >> (cc & 63)) & 1ull)) continue;
+            const size_t o = (size_t)(y0 - hj + r0 + r) * nx + (x0 - hi + cc);   // (a set bit is an interior cell)
+            const T lat = tlat[o], lon = tlon[o];
+            const T phis = lat * d2r;
+            s_l1[r][cc] = (lon > T(180)) ? d2r * (lon - T(360.)) : d2r * lon;     // ref: UM :552-556
+            s_cp[r][cc] = cos(phis);
+            if constexpr (sizeof(T) == 8) { s_sh[r][cc] = sin(phis / T(2)); s_ch[r][cc] = cos(phis / T(2)); }
+            else s_sh[r][cc] = phis;
+        }
+        __syncthreads();
+        if (!valid) continue;
+        // reach rows ty .. ty + 2hj are this wave's window (source row ys = yy + ii, ii = r - ty - hj)
+        const int lo = ty > r0 ? ty : r0, hiw = (ty + 2 * hj < r0 + nr - 1) ? ty + 2 * hj : r0 + nr - 1;
+        for (int r = lo; r <= hiw; ++r) {
+            const uint64_t s0 = s_bw[r][0], s1 = s_bw[r][1];
+            if ((s0 | s1) == 0) continue;                          // workgroup-uniform
+            uint64_t wb = (s0 >> tx) | (tx ? s1 << (64 - tx) : 0ull);
+            wb &= lmask;
+            const int rc = r - r0, ii = r - ty - hj;
+            while (wb) {
+                const int b = __builtin_ctzll(wb);
+                wb &= wb - 1ull;
+                const int cc = tx + b;                             // reach column of source column xx - hi + b
+                T sp;
+                if constexpr (sizeof(T) == 8) sp = s_sh[rc][cc] * cht - s_ch[rc][cc] * sht;
+                else sp = sin((s_sh[rc][cc] - phit) / T(2));
+                const T dlam = s_l1[rc][cc] - l2;                  // l1 - l2 (ref: UM :565)
+                const T sl = sin(dlam / T(2));
+                const T a = sp * sp + (s_cp[rc][cc] * (cost * (sl * sl)));    // ref: UM :566
+                const bool early = ii < 0 || (ii == 0 && b <= hi);
+                if (early) a_early = a < a_early ? a : a_early;
+                else a_late = a < a_late ? a : a_late;
+            }
+        }
+    }
+    if (!valid) return;
+    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref: UM :567
+    T m_early = a_early < none ? dist_of(a_early) : big;
+    const T m_late = a_late < none ? dist_of(a_late) : big;
+    if (m_early > T(2) * maxdist) m_early = big;                   // ref: UM :578 at the target's sweep position
+    const T m = m_early < m_late ? m_early : m_late;
+    const size_t o = (size_t)(yy + hj) * NX + xx + hi;
+    if (m >= big) cdist[o] = big;
+    else cdist[o] = (lf > T(0)) ? m : -m;                          // ref: UM :568-574
+}
+
+template <typename T>
+hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st) {
+    hipLaunchKernelGGL(k_edges_um<T>, dim3((nx + 255) / 256, (ny + UM_EDGE_ROWS - 1) / UM_EDGE_ROWS), dim3(256), 0, st,
+                       lf, ci, coast, nx, ny, hi, hj);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
+                             int hi, int hj, T maxdist, uint64_t *bits, hipStream_t st) {
+    if (hi < 0 || hi > 31 || hj < 0 || hj > 31) return hipErrorInvalidValue;
+    const int nw = (nx + 63) / 64;
+    // (two launches: the bit plane is complete before any cdist cell is written, so cdist may be coast)
+    hipLaunchKernelGGL(k_coastbits_um<T>, dim3((nx + 255) / 256, (ny + UM_BITS_ROWS - 1) / UM_BITS_ROWS), dim3(256), 0, st,
+                       coast, bits, nx, ny, hi, hj, nw);
+    hipLaunchKernelGGL(k_dist_um<T>, dim3((nx + 63) / 64, (ny + UM_DIST_TY - 1) / UM_DIST_TY), dim3(64 * UM_DIST_TY), 0, st,
+                       bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, nw, maxdist);
+    return hipGetLastError();
+}
+
+template hipError_t sb_launch_edges_um<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edges_um<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_dist_um<float>(const float *, const float *, const float *, const float *, float *, int, int,
+                                             int, int, float, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um<double>(const double *, const double *, const double *, const double *, double *, int,
+                                              int, int, int, double, uint64_t *, hipStream_t);

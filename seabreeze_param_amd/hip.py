@@ -269,6 +269,45 @@ class Context:
         self._chk(rc, "sb_get_dist")
         return cdist
 
+    def get_edges_um(self, landfrac_l, icefrac_l, halo_i, halo_j, out=None):
+        """UM vn10.7 get_edges(mask, icefrac, landfrac) on the tdims_l layout: landfrac_l, icefrac_l are
+        (ny + 2*halo_j, nx + 2*halo_i) with their ghost cells filled; returns coast of that shape with 0/1 in the
+        interior.  Its ghost cells are those of `out` (zeros without it): they are not touched."""
+        landfrac_l = np.ascontiguousarray(landfrac_l)
+        dt = np.dtype(landfrac_l.dtype)
+        icefrac_l = _host(icefrac_l, dt)
+        ny, nx = landfrac_l.shape[0] - 2 * halo_j, landfrac_l.shape[1] - 2 * halo_i
+        if icefrac_l.shape != landfrac_l.shape:
+            raise ValueError("landfrac_l and icefrac_l must have the same shape")
+        coast = np.zeros_like(landfrac_l) if out is None else out
+        if coast.shape != landfrac_l.shape or coast.dtype != dt or not coast.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of the input's shape and dtype")
+        rc = getattr(self.lib, f"sb_get_edges_um_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i),
+                                                             C.c_int(halo_j), _p(landfrac_l), _p(icefrac_l), _p(coast))
+        self._chk(rc, "sb_get_edges_um")
+        return coast
+
+    def get_dist_um(self, coast_l, landfrac, true_lat, true_lon, halo_i, halo_j, maxdist=180.0, out=None):
+        """UM vn10.7 get_dist(landfrac, coast): coast_l (ny + 2*halo_j, nx + 2*halo_i), landfrac and the 2-D
+        coordinates true_lat, true_lon (degrees) (ny, nx).  Returns the signed coast distance on coast_l's layout:
+        the interior is written, the ghost cells are those of `out` (zeros without it).  out may be coast_l itself."""
+        coast_l = np.ascontiguousarray(coast_l)
+        dt = np.dtype(coast_l.dtype)
+        landfrac = _host(landfrac, dt); true_lat = _host(true_lat, dt); true_lon = _host(true_lon, dt)
+        ny, nx = landfrac.shape
+        if coast_l.shape != (ny + 2 * halo_j, nx + 2 * halo_i):
+            raise ValueError(f"coast_l shape {coast_l.shape} != {(ny + 2 * halo_j, nx + 2 * halo_i)}")
+        if true_lat.shape != (ny, nx) or true_lon.shape != (ny, nx):
+            raise ValueError("true_lat, true_lon must be (ny, nx) like landfrac")
+        cdist = np.zeros_like(coast_l) if out is None else out
+        if cdist.shape != coast_l.shape or cdist.dtype != dt or not cdist.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of coast_l's shape and dtype")
+        rc = getattr(self.lib, f"sb_get_dist_um_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i),
+                                                            C.c_int(halo_j), _p(coast_l), _p(landfrac), _p(true_lat),
+                                                            _p(true_lon), _CT[dt](maxdist), _p(cdist))
+        self._chk(rc, "sb_get_dist_um")
+        return cdist
+
     # ------------------------------------------------------------------ device-pointer API
     def sigmoid_dev(self, dtype, nx, ny, ary, sm, stream=None):
         """sm = 1/(1+exp(-std*(ary-r))) on device arrays (raw addresses); enqueues without synchronising."""
@@ -300,6 +339,21 @@ class Context:
         fn = getattr(self.lib, f"sb_get_dist_{_SFX[dt]}_dev")
         self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), _p(coast), _p(mask), _p(lon), _p(lat), _CT[dt](maxdist),
                      C.c_int(kwin), _p(cdist), C.c_void_p(stream) if stream else None), "sb_get_dist_dev")
+
+    def get_edges_um_dev(self, dtype, nx, ny, halo_i, halo_j, landfrac_l, icefrac_l, coast, stream=None):
+        """UM-layout get_edges on device arrays (raw addresses); enqueues without synchronising."""
+        fn = getattr(self.lib, f"sb_get_edges_um_{_SFX[np.dtype(dtype)]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), _p(landfrac_l), _p(icefrac_l),
+                     _p(coast), C.c_void_p(stream) if stream else None), "sb_get_edges_um_dev")
+
+    def get_dist_um_dev(self, dtype, nx, ny, halo_i, halo_j, coast_l, landfrac, true_lat, true_lon, cdist,
+                        maxdist=180.0, stream=None):
+        """UM-layout get_dist on device arrays (raw addresses, coordinates included); enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        fn = getattr(self.lib, f"sb_get_dist_um_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), _p(coast_l), _p(landfrac),
+                     _p(true_lat), _p(true_lon), _CT[dt](maxdist), _p(cdist), C.c_void_p(stream) if stream else None),
+                  "sb_get_dist_um_dev")
 
     def sigma_moments_dev(self, dtype, nx, ny, halo, sigma, moments5, stream=None):
         """Band-local sigma moments -> 5 doubles at device address moments5."""
