@@ -111,6 +111,33 @@ __device__ __forceinline__ int thc_block_excl_scan(int v, int *s_w, int &total) 
     return incl - v + __shfl(wincl, wv) - __shfl(wt, wv);
 }
 
+// k_wind's segment lists (k_prep's work on single-domain host-model calls), compacted by the last workgroups of a grid
+// of G: sub-list `part` holds the segments with band cells of its contiguous range of the band plane, in ascending
+// order -- exactly what k_prep writes.  s_scan: one int per wave.
+template <int NT>
+__device__ __forceinline__ void sb_compact_segments(const Geo &g, const uint64_t *bandbits, SbSegEntry *seg_list, int *seg_count,
+                                                    int seg_cap, int G, int *s_scan) {
+    const int tid = threadIdx.x;
+    const unsigned nseg = (unsigned)g.nyh * (unsigned)g.nw;
+    const unsigned cap = (unsigned)seg_cap;
+    for (int part = G - 1 - (int)blockIdx.x; part < SB_SEG_PARTS; part += G) {
+        if (part < 0) break;
+        const unsigned s0 = (unsigned)part * cap, s1 = min(s0 + cap, nseg);
+        const unsigned per = (cap + NT - 1) / NT;
+        const unsigned a0 = min(s0 + (unsigned)tid * per, s1), a1 = min(a0 + per, s1);
+        int cnt = 0;
+        for (unsigned sg = a0; sg < a1; ++sg) cnt += bandbits[sg] != 0 ? 1 : 0;
+        int total;
+        int at = thc_block_excl_scan<NT>(cnt, s_scan, total);
+        SbSegEntry *list = seg_list + (size_t)part * cap;
+        for (unsigned sg = a0; sg < a1; ++sg) {
+            const uint64_t w = bandbits[sg];
+            if (w) { SbSegEntry e; e.word = w; e.seg = sg; e.pad = 0; list[at++] = e; }
+        }
+        if (tid == 0) seg_count[part] = total;
+    }
+}
+
 template <bool FLY>
 struct ThcBufs {
     __amdgpu_buffer_rsrc_t th, zz, sg, cls;       // theta (FLY) or t0; z; sigma; land-side plane

@@ -740,26 +740,7 @@ __global__ __launch_bounds__(NT) void k_thc3(const int *__restrict__ tile_list, 
         par ^= 1;
     }
     if constexpr (FOLD) {
-        // ---- k_wind's segment lists: sub-list `part` holds the segments with band cells of its contiguous range of the
-        // band plane, in ascending order (exactly what k_prep writes) ----
-        const unsigned nseg = (unsigned)g.nyh * (unsigned)g.nw;
-        const unsigned cap = (unsigned)job.seg_cap;
-        for (int part = G - 1 - (int)blockIdx.x; part < SB_SEG_PARTS; part += G) {
-            if (part < 0) break;
-            const unsigned s0 = (unsigned)part * cap, s1 = min(s0 + cap, nseg);
-            const unsigned per = (cap + NT - 1) / NT;
-            const unsigned a0 = min(s0 + (unsigned)tid * per, s1), a1 = min(a0 + per, s1);
-            int cnt = 0;
-            for (unsigned sg = a0; sg < a1; ++sg) cnt += job.bandbits[sg] != 0 ? 1 : 0;
-            int total;
-            int at = thc_block_excl_scan<NT>(cnt, s_scan, total);
-            SbSegEntry *list = job.seg_list + (size_t)part * cap;
-            for (unsigned sg = a0; sg < a1; ++sg) {
-                const uint64_t w = job.bandbits[sg];
-                if (w) { SbSegEntry e; e.word = w; e.seg = sg; e.pad = 0; list[at++] = e; }
-            }
-            if (tid == 0) job.seg_count[part] = total;
-        }
+        sb_compact_segments<NT>(g, job.bandbits, job.seg_list, job.seg_count, job.seg_cap, G, s_scan);
     }
 #ifdef SB_STAMPS
     if (tid == 0) {
