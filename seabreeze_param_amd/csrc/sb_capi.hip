@@ -227,21 +227,15 @@ Geo make_geo(int nx, int ny, int h, int bnd, int rows) {
     return g;
 }
 
-int pick_halo(const sb_ctx *c) {
-    int r = c->radius_hint;
-    if (r <= 8) return 8;
-    if (r <= 16) return 16;
-    if (r <= 24) return 24;
-    return SB_MAX_LDS_HALO;
-}
-
-// does a marching-strip kernel run the contrast for this precision and domain (else: the tile kernel)?  As run_diag decides.
+// the launch plan's input (sb_diag_plan.hpp) as far as the context and the domain give it: all the contrast kernel's choice needs
 template <typename T>
-static bool strip_kernel_runs(const sb_ctx *c, int nx, int rows) {
-    const int H = pick_halo(c);
-    int tx, ty;
-    if (H > 16) return sizeof(T) == 4 && !c->no_wide_strip && sb_strip32_shape(nx, rows, &tx, &ty);
-    return sb_strip_shape(nx, rows, &tx, &ty);
+static SbPlanIn plan_input(const sb_ctx *c, int nx, int rows) {
+    SbPlanIn in{};
+    in.esize = (int)sizeof(T); in.nx = nx; in.rows = rows; in.halo = sb_pick_halo(c->radius_hint);
+    in.no_wide_strip = c->no_wide_strip != 0; in.no_fold = c->no_fold != 0; in.no_plan_cache = c->no_plan_cache != 0;
+    in.band_late_wind = c->band_late_wind != 0; in.gathered = c->gathered != nullptr;
+    in.shapes = sb_contrast_shapes(nx, rows);
+    return in;
 }
 
 // sigma's statistics of an earlier complete call still stand (opt-in, same array, same shape)
@@ -261,27 +255,14 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     int rc;
     if ((rc = ensure(c, c->bandbits, nbits))) return rc;
     if ((rc = ensure(c, c->clsbits, nbits))) return rc;
-    const int H = pick_halo(c);
-    // contrast kernel: marching strips (32 owned longitudes x 16-row blocks, flags strip-major with a virtual block
-    // above and below every strip) for LDS halos up to 16 cells, LDS tiles (row-major flags) beyond
-    int txw, tyrows, tx, ty;
-    // (radii beyond 16: in single precision the 96-column strip kernel answers up to 31 from LDS -- what a distance field
-    // made with a window of up to 30 cells needs; double precision, and sb_set_wide_strip(ctx, 0), keep the tile kernel)
-    const bool strip32 = H > 16 && sizeof(T) == 4 && !c->no_wide_strip && sb_strip32_shape(g.nx, g.rows, &tx, &ty);
-    const bool strip = strip32 || (H <= 16 && sb_strip_shape(g.nx, g.rows, &tx, &ty));
-    const int vb = strip32 ? 2 : 1;                  // virtual blocks above and below every strip in the flags
-    if (strip) { txw = 32; tyrows = 16; }
-    else {
-        sb_thc_tile_shape(H > 16 ? H : 24, &txw, &tyrows);
-        tx = (g.nx + txw - 1) / txw; ty = (g.rows + tyrows - 1) / tyrows;
-    }
-    const int Hk = strip32 ? 32 : strip ? 16 : (H > 16 ? H : 24);   // halo of the kernel that runs
+    SbPlanIn in = plan_input<T>(c, g.nx, g.rows);
+    const SbContrast k = sb_plan_contrast(in);
+    const bool strip = k.strip != 0;
+    const int tx = k.tx, ty = k.ty, vb = k.vb, ntile = k.ntile, nflag = k.nflag;
     // Two buffers of [per-tile flags | 2 slow-path counters], used by alternate calls: k_scan
     // raises flags in this call's buffer, k_wind clears the other one for the next call, so no
     // memset sits on the critical path and the last call's values stay readable.
-    const int ntile = strip ? tx * (ty + 2 * vb) : tx * ty;
-    const int nflag = ntile + 2;
-    if (c->tiles.cap < (size_t)2 * nflag * sizeof(int) || c->tiles_n != nflag || c->tiles_strip != (strip ? vb : 0)) {
+    if (c->tiles.cap < (size_t)2 * nflag * sizeof(int) || c->tiles_n != nflag || c->tiles_strip != vb) {
         if ((rc = ensure(c, c->tiles, (size_t)2 * nflag * sizeof(int)))) return rc;
         // (in stream order, on the call's own stream: a plain hipMemset runs on the null stream, which the non-blocking
         // streams kernels are enqueued on do not wait for -- a late memset could wipe flags k_scan had already raised.  No
@@ -289,14 +270,13 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         // above has synchronised already)
         HIPCHK(c, hipMemsetAsync(c->tiles.p, 0, (size_t)2 * nflag * sizeof(int), st));
         c->tiles_n = nflag;
-        c->tiles_strip = strip ? vb : 0;
+        c->tiles_strip = vb;
         c->flag_parity = 0;
     }
     int *flags_now = (int *)c->tiles.p + (size_t)c->flag_parity * nflag;
     int *flags_next = (int *)c->tiles.p + (size_t)(1 - c->flag_parity) * nflag;
-    job.thc_ty = tyrows; job.thc_ntx = tx; job.thc_nty = ty;
-    job.thc_txs = txw == 32 ? 5 : 6;
-    job.strip = strip32 ? 2 : strip ? 1 : 0;
+    job.thc_ty = k.tyrows; job.thc_ntx = tx; job.thc_nty = ty; job.thc_txs = k.txw == 32 ? 5 : 6;
+    job.strip = k.strip;
     if (strip) { job.tile_sx = ty + 2 * vb; job.tile_sy = 1; job.tile_off = vb; }
     else { job.tile_sx = 1; job.tile_sy = tx; job.tile_off = 0; }
     job.bandbits = (uint64_t *)c->bandbits.p;
@@ -320,31 +300,13 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     job.seg_cap = (int)seg_cap;
     // the host-model flavour derives t0 inside k_thc3; the f2py flavour returns the t0 plane
     job.t0_fly = (job.flavour == SB_FLAVOUR_GENERIC) ? 1 : 0;
-    // Whole single-domain calls run the contrast first and let k_wind apply the update.  A band step runs k_scan and
-    // k_wind ahead of the join with the communication stream and applies the update in the contrast kernel.  (The
-    // single-domain order in a band step -- k_scan | join | contrast, k_wind: six launches instead of seven -- was
-    // measured and is slower: only k_scan's 12 us then cover the 25 us of the communication stream's small kernels,
-    // 69.5 against 55.5 us for a 2560 x 240 x 56 band step; profiles/r03_band_step_cost.log.  sb_set_band_order.)
-    const bool late_wind = c->band_late_wind && c->gathered && strip && job.t0_fly && !c->no_fold;
-    job.wind_final = ((phases == 3 && !c->gathered) || late_wind) ? 1 : 0;
-    // this call's wind speed / direction at band cells, where k_wind runs ahead of the contrast (k_wind -> k_thc3)
-    job.nws = job.nwd = nullptr;
-    if (!job.wind_final) {
-        if ((rc = ensure(c, c->nws, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
-        if ((rc = ensure(c, c->nwd, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
-        job.nws = (T *)c->nws.p;
-        job.nwd = (T *)c->nwd.p;
-    }
     // the t0 plane with its ghost cells: f2py flavour only (k_t0 -> k_thc3)
-    job.t0 = nullptr;
     if (!job.t0_fly) {
         if ((rc = ensure(c, c->t0, ncell * sizeof(T)))) return rc;
         job.t0 = (T *)c->t0.p;
     }
     if ((rc = ensure(c, c->jobcopy, sizeof(DiagJob<double>)))) return rc;
     job.self = (DiagJob<T> *)c->jobcopy.p;
-    job.plan = nullptr; job.plan_gen = nullptr; job.call_id = 0; job.plan_use = 0; job.seg_trust = 0;
-    job.moments_out = nullptr; job.stats_ticket = nullptr; job.strip_update = 0;
     if (strip) {
         const size_t need = 64 + (size_t)c->ncu * SB_PLAN_STRIDE;
         if (c->plan.cap < need) {
@@ -371,38 +333,35 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         job.call_id = c->call_seq;
         job.plan_use = c->no_plan_cache ? 0 : c->plan_use;
     } else if (phases & 1) c->plan_bits = nullptr;           // (the tile kernel rewrites nothing of the plan, but k_scan does not watch the plane for it)
-    job.stamps = nullptr;
 #ifdef SB_STAMPS
     if ((rc = ensure(c, c->stamps, (size_t)4096 * SB_NSTAMP * sizeof(long long)))) return rc;
     job.stamps = (long long *)c->stamps.p;
 #endif
-    SbLaunchCtx lc;
-    lc.stream = st;
-    lc.prof = nullptr;
-    lc.prof_mask = nullptr;
+    SbLaunchCtx lc{};
     if (phases == 3 && c->prof_calls < c->prof_max) {
         lc.prof_mask = &c->prof_mask[(size_t)c->prof_calls];
         lc.prof = &c->prof_ev[(size_t)SB_PROF_EVENTS * c->prof_calls++];
     }
-    lc.partials = c->partials; lc.stats = c->stats;
+    lc.stream = st; lc.partials = c->partials; lc.stats = c->stats;
     lc.gathered = c->gathered; lc.ngathered = c->ngathered; lc.ncu = c->ncu;
     lc.moments_out = (phases == 1) ? c->band_moments_out : nullptr;   // (a band step: k_scan publishes this band's moments)
     lc.moments_event = (phases == 1 && c->nranks > 1) ? c->ev_mom : nullptr;   // (one rank: nobody waits for them)
     lc.stats_ticket = (int *)c->ticket + 1;
-    lc.phases = phases;
-    lc.reuse_stats = reuse_stats<T>(c, job.sigma, g.nx, g.ny, g.h);
-    lc.no_fold = c->no_fold != 0;
-    const bool strip_folds = strip && job.t0_fly && !c->no_fold;
-    lc.segs_stand = strip_folds && c->gathered && c->plan_use && c->segs_built && !c->no_plan_cache;
-    job.fold = 0; job.fold_partials = nullptr; job.fold_nparts = 0; job.stats_out = nullptr;
-    // (single-domain calls: the lists the strip kernel of the call before compacted belong to the same planes as its plan)
-    job.lists_stand = (strip_folds && !c->gathered && phases == 3 && c->plan_use && c->segs_built && !c->no_plan_cache) ? 1 : 0;
-    job.gath = nullptr; job.ngath = 0;
-    int launched = 0;
-    lc.launches = &launched;
+    // every decision about the kernels of this call: the plan's (the job's mode fields are the executor's to set)
+    in.phases = phases; in.t0_fly = job.t0_fly != 0; in.moments_out = lc.moments_out != nullptr;
+    in.reuse_stats = reuse_stats<T>(c, job.sigma, g.nx, g.ny, g.h);
+    in.plan_use = c->plan_use != 0; in.segs_built = c->segs_built;
+    in.scan_wgs = sb_scan_workgroups((unsigned)g.nyh * (unsigned)g.nw, c->ncu);
+    const SbDiagPlan plan = sb_plan_diag(in);
+    // this call's wind speed / direction at band cells, where k_wind runs ahead of the contrast (k_wind -> k_thc3)
+    if (plan.wind_scratch) {
+        if ((rc = ensure(c, c->nws, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
+        if ((rc = ensure(c, c->nwd, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
+        job.nws = (T *)c->nws.p; job.nwd = (T *)c->nwd.p;
+    }
     if (phases == 3) c->rep_launches = c->rep_rccl = c->rep_groups = c->rep_copies = 0;   // a band step resets them itself
     {
-        const hipError_t le = sb_launch_diag<T>(job, Hk, lc);
+        const hipError_t le = sb_launch_diag<T>(job, plan, lc);
         if (le != hipSuccess) {
             // nothing the host noted for later calls stands: the stored plan and the segment lists were not (all) made
             c->plan_bits = nullptr;
@@ -412,10 +371,10 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         if (le == hipErrorInvalidValue) return fail(c, SB_ERR_ARG, "no contrast kernel instance for this halo / tile shape");
         if (le != hipSuccess) return hipfail(c, le, "sb_launch_diag");
     }
-    c->rep_launches += launched;
+    c->rep_launches += plan.nsteps;
     if (!(phases & 2)) return SB_OK;          // the flag buffers swap when the call is complete
-    c->segs_built = strip_folds;
-    if (c->static_sigma && c->host_depth == 0 && !lc.reuse_stats) {
+    c->segs_built = plan.segs_built;
+    if (c->static_sigma && c->host_depth == 0 && !in.reuse_stats) {
         c->stats_valid = true;
         c->stats_sigma = (const void *)job.sigma;
         c->stats_dims[0] = g.nx; c->stats_dims[1] = g.ny; c->stats_dims[2] = g.h; c->stats_dims[3] = (int)sizeof(T);
@@ -522,7 +481,7 @@ int band_diag_dev(sb_ctx *c, T timestep_s, int tn, int nx, int ny, int nz, int h
     // arithmetic (Geo::band) -- no fill kernel on the communication stream, three launches per band step (round 3: four,
     // and the fill, running behind the caller's stream's kernels rather than beside them, held the join up).  The tile
     // kernel (double precision, radii beyond 16) reads every ghost cell as filled: the whole swap_bounds for it.
-    const bool folds = strip_kernel_runs<T>(c, nx, ny) && nx > 96 + 2;
+    const bool folds = sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
     const int band_geo = folds ? (GEO_BAND_EW | (c->rank == 0 ? GEO_BAND_SOUTH : 0) | (c->rank == c->nranks - 1 ? GEO_BAND_NORTH : 0)) : 0;
     rc = folds ? exchange_rows_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream)
                : swap_bounds_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream);

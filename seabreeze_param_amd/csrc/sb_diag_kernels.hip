@@ -638,158 +638,37 @@ static hipError_t launch_contrast(const DiagJob<T> &job, int H, int ncu, hipStre
     return job.strip ? sb_launch_strip<T>(job, ncu, st) : sb_launch_thc<T>(job, H, ncu, st);
 }
 
+// One diag call: the steps of its plan (sb_diag_plan.hpp), each with its own copy of the job in the step's mode.
 template <typename T>
-hipError_t sb_launch_diag(const DiagJob<T> &job, int H, const SbLaunchCtx &lc) {
-    const Geo &g = job.g;
+hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const SbLaunchCtx &lc) {
     hipStream_t st = lc.stream;
-    hipEvent_t *ev = lc.prof;
-    const bool gathered = lc.gathered != nullptr;
-    const bool ph1 = (lc.phases & 1) != 0, ph2 = (lc.phases & 2) != 0;
-    const bool reuse = lc.reuse_stats;
     hipError_t e = hipSuccess;
-    int nl = 0;                                                  // kernels enqueued
-    const unsigned nseg = (unsigned)g.nyh * (unsigned)g.nw;
-    int nblk = (int)((nseg + 31) / 32);                          // 16 waves x one trip of 2 segments: a small domain (a band of
-                                                                 // a multi-GPU run) is spread over all CUs, its waves make few
-                                                                 // dependent trips -- k_scan is latency, not bytes, there
-    if (nblk < 1) nblk = 1;
-    if (nblk > lc.ncu) nblk = lc.ncu;                            // one 1024-thread workgroup per CU, two trips of loads in flight
-                                                                 // (two workgroups per CU, 8 waves per SIMD, measured slower in round 4:
-                                                                 // k_scan 25.0 -> 28.7 us at 2560x1920 fp64, 60.1 -> 65.0 at 5120x3840 fp32)
-    const dim3 pg(2 + SB_SEG_PARTS), pb(PREP_NT);
-    // Single-domain calls run the contrast first and let k_wind apply the thresholds and the state update
-    // (job.wind_final); a band step must run k_scan + k_wind before its ghost rows arrive, so there the contrast
-    // kernel applies them.
-    if (job.wind_final && ph1 && ph2 && !gathered) {
-        SB_EV_BEGIN(SB_PROF_SCAN);
-        launch_scan<T>(job, nblk, lc.partials, !reuse, st);
-        SB_EV_END(SB_PROF_SCAN);
-        // host-model flavour: the strip kernel does k_prep's work itself (one dependent launch less on the critical path)
-        if (job.strip && job.t0_fly && !lc.no_fold && nblk <= 1024) {
-            DiagJob<T> fj = job;
-            fj.fold = 1;
-            fj.fold_partials = lc.partials;
-            fj.fold_nparts = reuse ? 0 : nblk;
-            fj.stats_out = (T *)lc.stats;
-            SB_EV_BEGIN(SB_PROF_THC);
-            if ((e = launch_contrast<T>(fj, H, lc.ncu, st)) != hipSuccess) return e;
-            SB_EV_END(SB_PROF_THC);
-            SB_EV_BEGIN(SB_PROF_WIND);
-            launch_wind<T>(job, lc.ncu, st);
-            SB_EV_END(SB_PROF_WIND);
-            if (lc.launches) *lc.launches += 3;
-            return hipGetLastError();
+    for (int i = 0; i < plan.nsteps; ++i) {
+        const SbStep &s = plan.steps[i];
+        hipEvent_t *ev = s.prof == SB_PROF_NONE ? nullptr : lc.prof;
+        DiagJob<T> j = job;
+        j.wind_final = s.wind_final; j.strip_update = s.strip_update; j.lists_stand = s.lists_stand; j.seg_trust = s.seg_trust; j.fold = s.fold;
+        if (s.publish) { j.moments_out = lc.moments_out; j.stats_ticket = lc.stats_ticket; }
+        if (s.kernel == SB_K_CONTRAST) {
+            if (s.stats == SB_STATS_PARTIALS) { j.fold_partials = lc.partials; j.fold_nparts = s.nparts; }
+            if (s.stats == SB_STATS_GATHERED) { j.gath = lc.gathered; j.ngath = lc.ngathered; }
+            if (s.fold || s.stats == SB_STATS_GATHERED) j.stats_out = (T *)lc.stats;     // it publishes the sigmoid scalars
         }
-        SB_EV_BEGIN(SB_PROF_PREP);
-        hipLaunchKernelGGL(k_prep<T>, pg, pb, 0, st, job, (const Moments *)lc.partials, reuse ? 0 : nblk, (T *)lc.stats, (Moments *)nullptr);
-        SB_EV_END(SB_PROF_PREP);
-        nl += 2;
-        if (!job.t0_fly) {
-            SB_EV_BEGIN(SB_PROF_T0);
-            hipLaunchKernelGGL(k_t0<T>, dim3((g.nxh + 255) / 256, g.nyh), dim3(256), 0, st, job);
-            SB_EV_END(SB_PROF_T0);
-            ++nl;
-        }
-        SB_EV_BEGIN(SB_PROF_THC);
-        if ((e = launch_contrast<T>(job, H, lc.ncu, st)) != hipSuccess) return e;
-        SB_EV_END(SB_PROF_THC);
-        SB_EV_BEGIN(SB_PROF_WIND);
-        launch_wind<T>(job, lc.ncu, st);
-        SB_EV_END(SB_PROF_WIND);
-        nl += 2;
-        if (lc.launches) *lc.launches += nl;
-        return hipGetLastError();
-    }
-    // ---- a band step on the strip kernel: k_scan ahead of the join; behind it the contrast -- it merges the moments
-    // gathered from all ranks and compacts k_wind's segment lists itself -- and k_wind with the update: the three
-    // kernels of a single-domain call
-    if (job.wind_final) {
-        if (ph1) {
-            const bool publish = gathered && lc.moments_out != nullptr && !reuse;     // this band's moments, for the all-gather
-            DiagJob<T> sj = job;
-            if (publish) { sj.moments_out = lc.moments_out; sj.stats_ticket = lc.stats_ticket; }
-            launch_scan<T>(sj, nblk, lc.partials, publish, st);
-            if (publish && lc.moments_event && (e = hipEventRecord(lc.moments_event, st)) != hipSuccess) return e;
-            ++nl;
-        }
-        if (ph2) {
-            DiagJob<T> fj = job;
-            fj.fold = 1;
-            fj.fold_partials = nullptr;
-            fj.fold_nparts = 0;
-            if (gathered && !reuse) { fj.gath = lc.gathered; fj.ngath = lc.ngathered; }
-            fj.stats_out = (T *)lc.stats;
-            if ((e = launch_contrast<T>(fj, H, lc.ncu, st)) != hipSuccess) return e;
-            launch_wind<T>(job, lc.ncu, st);
-            nl += 2;
-        }
-        if (lc.launches) *lc.launches += nl;
-        return hipGetLastError();
-    }
-    // ---- phase 1: needs neither theta's ghost cells nor the statistics of the other bands ---------
-    if (ph1) {
-        // a band step takes this band's own sigma moments from the same pass (lc.moments_out), publishes
-        // them for the all-gather and signals the communication stream
-        const bool own_stats = (!gathered || lc.moments_out != nullptr) && !reuse;
-        // (a band step: k_scan's last workgroup merges and publishes the moments itself -- the all-gather can start
-        // behind this one kernel)
-        const bool scan_publishes = own_stats && gathered && lc.moments_out != nullptr;
-        DiagJob<T> sj = job;
-        if (scan_publishes) { sj.moments_out = lc.moments_out; sj.stats_ticket = lc.stats_ticket; }
-        SB_EV_BEGIN(SB_PROF_SCAN);
-        launch_scan<T>(sj, nblk, lc.partials, own_stats, st);
-        SB_EV_END(SB_PROF_SCAN);
-        if (scan_publishes && lc.moments_event && (e = hipEventRecord(lc.moments_event, st)) != hipSuccess) return e;
-        const bool lists_stand = lc.segs_stand;
-        if (!lists_stand) {
-            SB_EV_BEGIN(SB_PROF_PREP);
-            hipLaunchKernelGGL(k_prep<T>, pg, pb, 0, st, job, (const Moments *)lc.partials, own_stats && !scan_publishes ? nblk : 0,
+        SB_EV_BEGIN(s.prof);
+        switch (s.kernel) {
+        case SB_K_SCAN: launch_scan<T>(j, plan.scan_wgs, lc.partials, s.stats == SB_STATS_PARTIALS, st); break;
+        case SB_K_PREP:
+            hipLaunchKernelGGL(k_prep<T>, dim3(2 + SB_SEG_PARTS), dim3(PREP_NT), 0, st, j, (const Moments *)lc.partials, s.nparts,
                                (T *)lc.stats, (Moments *)nullptr);
-            SB_EV_END(SB_PROF_PREP);
-            ++nl;
+            break;
+        case SB_K_MERGE: hipLaunchKernelGGL(k_merge_moments<T>, dim3(1), dim3(SB_WAVE), 0, st, lc.gathered, lc.ngathered, (T *)lc.stats); break;
+        case SB_K_T0: hipLaunchKernelGGL(k_t0<T>, dim3((j.g.nxh + 255) / 256, j.g.nyh), dim3(256), 0, st, j); break;
+        case SB_K_CONTRAST: if ((e = launch_contrast<T>(j, plan.contrast.Hk, lc.ncu, st)) != hipSuccess) return e; break;
+        case SB_K_WIND: launch_wind<T>(j, lc.ncu, st); break;
         }
-        DiagJob<T> wj = job;
-        wj.seg_trust = lists_stand ? 1 : 0;
-        SB_EV_BEGIN(SB_PROF_WIND);
-        launch_wind<T>(wj, lc.ncu, st);
-        SB_EV_END(SB_PROF_WIND);
-        nl += 2;
+        SB_EV_END(s.prof);
+        if (s.publish && lc.moments_event && (e = hipEventRecord(lc.moments_event, st)) != hipSuccess) return e;
     }
-    // ---- phase 2: statistics of all bands, theta with its ghost cells -------------------------
-    if (ph2) {
-        DiagJob<T> pj = job;
-        if (gathered && !reuse) {
-            if (job.t0_fly) {                                    // the contrast kernel merges the gathered moments in its prologue
-                pj.gath = lc.gathered;
-                pj.ngath = lc.ngathered;
-                pj.stats_out = (T *)lc.stats;
-            } else {                                             // k_t0 needs the scalars first
-                hipLaunchKernelGGL(k_merge_moments<T>, dim3(1), dim3(SB_WAVE), 0, st, lc.gathered, lc.ngathered, (T *)lc.stats);
-                ++nl;
-            }
-        }
-        if (!job.t0_fly) {
-            SB_EV_BEGIN(SB_PROF_T0);
-            hipLaunchKernelGGL(k_t0<T>, dim3((g.nxh + 255) / 256, g.nyh), dim3(256), 0, st, job);
-            SB_EV_END(SB_PROF_T0);
-            ++nl;
-        }
-        // (the strip kernel leaves the contrast in thc whatever the order -- a loop that loads a cell's winds and state
-        // next to the prefetched blocks of the march drains them at every step -- and applies thresholds and state
-        // update behind its march, cell list by cell list)
-        if (job.strip) {
-            pj.wind_final = 1;
-            pj.strip_update = 1;
-            // ... and compacts the segment lists: this call's update kernel reads them, and the next call's k_wind
-            // if the planes stand (no k_prep then)
-            if (job.t0_fly && !lc.no_fold) { pj.fold = 1; pj.fold_partials = nullptr; pj.fold_nparts = 0; if (!pj.stats_out) pj.stats_out = (T *)lc.stats; }
-        }
-        SB_EV_BEGIN(SB_PROF_THC);
-        if ((e = launch_contrast<T>(pj, H, lc.ncu, st)) != hipSuccess) return e;
-        SB_EV_END(SB_PROF_THC);
-        ++nl;
-    }
-    if (lc.launches) *lc.launches += nl;
     return hipGetLastError();
 }
 
@@ -799,5 +678,5 @@ template hipError_t sb_launch_stats<double>(const double *, int, int, int, size_
                                             hipStream_t);
 template hipError_t sb_launch_sigmoid_apply<float>(const float *, float *, size_t, const float *, hipStream_t);
 template hipError_t sb_launch_sigmoid_apply<double>(const double *, double *, size_t, const double *, hipStream_t);
-template hipError_t sb_launch_diag<float>(const DiagJob<float> &, int, const SbLaunchCtx &);
-template hipError_t sb_launch_diag<double>(const DiagJob<double> &, int, const SbLaunchCtx &);
+template hipError_t sb_launch_diag<float>(const DiagJob<float> &, const SbDiagPlan &, const SbLaunchCtx &);
+template hipError_t sb_launch_diag<double>(const DiagJob<double> &, const SbDiagPlan &, const SbLaunchCtx &);

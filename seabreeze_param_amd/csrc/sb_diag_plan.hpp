@@ -1,0 +1,159 @@
+// sb_diag_plan.hpp -- which kernels a diag call enqueues, in which order and in which mode: decided here, in one pure
+// function, and nowhere else.  run_diag (sb_capi.hip) sizes its workspace from the plan, sb_launch_diag (sb_diag_kernels.hip)
+// walks its steps, band_diag_dev asks it for the contrast kernel.  Plain C++17: no HIP, no pointers, no heap -- a host
+// compiler builds it alone (tests/diag_plan_dump.cpp).
+#pragma once
+
+// kernels of a diag call that sb_profile_begin / sb_profile_end time, each with its own pair of events
+enum { SB_PROF_NONE = -1, SB_PROF_SCAN = 0, SB_PROF_WIND = 1, SB_PROF_T0 = 2, SB_PROF_THC = 3, SB_PROF_PREP = 4, SB_PROF_KERNELS = 5 };
+enum SbKernel { SB_K_SCAN, SB_K_PREP, SB_K_MERGE, SB_K_T0, SB_K_CONTRAST, SB_K_WIND };
+// sigma's statistics in a step.  k_scan: PARTIALS = it forms them; k_prep and the contrast kernel merge k_scan's `nparts`
+// partial moments (0: the scalars stand) or, as k_merge_moments does, the moments GATHERED from every band
+enum SbStatsSrc { SB_STATS_NONE, SB_STATS_PARTIALS, SB_STATS_GATHERED };
+// the LDS halo for a search-radius hint (32: the largest a contrast kernel is instantiated for)
+inline int sb_pick_halo(int r) { return r <= 8 ? 8 : r <= 16 ? 16 : r <= 24 ? 24 : 32; }
+// A strip kernel that does k_prep's work merges k_scan's partial moments with one thread each.  k_scan runs at most one
+// workgroup per compute unit, so the bound cannot fire on any device; it is part of the one predicate (`folds`) all the same.
+enum { SB_FOLD_MAX_PARTS = 1024, SB_PLAN_MAX_STEPS = 6 };
+
+// what sb_strip_shape, sb_strip32_shape and sb_thc_tile_shape answer for the domain (sb_contrast_shapes, sb_launch.hpp)
+struct SbShapes {
+    bool strip_fits, strip32_fits;  // the strip kernels' position planes hold the block grid
+    int strip_ntx, strip_nty, strip32_ntx, strip32_nty;
+    int tile_w, tile_rows24, tile_rows32;   // the tile kernel's tiles for LDS halos of 24 and 32 cells
+};
+
+struct SbPlanIn {
+    int phases;                     // bit 0: k_scan, k_prep, k_wind (no ghost cells, no statistics of other bands needed);
+                                    // bit 1: the statistics of all bands, k_t0, the contrast.  3: the whole call
+    int esize, nx, rows, halo;      // sizeof(T); interior cells; the LDS halo (sb_pick_halo)
+    bool t0_fly;                    // host-model flavour: the contrast kernel derives t0 (f2py flavour: k_t0 writes the plane)
+    bool no_wide_strip, no_fold, no_plan_cache, band_late_wind;     // sb_set_wide_strip / _fold / _plan_cache / _band_order
+    bool gathered;                  // sigma moments of every band are set (sb_use_gathered_moments, a band step)
+    bool moments_out;               // phase 1 of a band step: this band's moments are published for the all-gather
+    bool reuse_stats;               // static sigma: the sigmoid scalars of an earlier call stand
+    bool plan_use, segs_built;      // the strip kernel's stored plan was made for this geometry; the last complete call's
+                                    // strip kernel compacted k_wind's segment lists
+    int scan_wgs;                   // k_scan's workgroups (sb_scan_workgroups, sb_launch.hpp)
+    SbShapes shapes;
+};
+
+// the contrast kernel of the call and its block / tile grid
+struct SbContrast {
+    int strip;                      // 0: LDS tiles (k_thc3); 1: marching strips (k_strip); 2: the 96-column strips (k_strip32)
+    int Hk;                         // LDS halo of the kernel that runs
+    int txw, tyrows, tx, ty;        // owned columns and rows of a block / tile; blocks / tiles along x and y
+    int vb;                         // virtual blocks above and below every strip in the flags (0: tiles, row-major flags)
+    int ntile, nflag;               // flags of the blocks / tiles; the same plus the two slow-path counters
+};
+
+struct SbStep {
+    signed char kernel, prof, stats;    // SbKernel; the SB_PROF_* pair that brackets it in a profiled call; SbStatsSrc
+    int nparts;                     // k_prep, contrast with PARTIALS: partial moments to merge
+    bool publish;                   // k_scan leaves this band's moments for the all-gather; the moments event is recorded behind it
+    bool fold;                      // the strip kernel does k_prep's work: ranks the flags, publishes the scalars, compacts the lists
+    bool wind_final;                // DiagJob::wind_final as this kernel sees it
+    bool strip_update;              // the strip kernel applies thresholds and state update behind its march
+    bool lists_stand;               // DiagJob::lists_stand: a march by the stored plan does not compact the segment lists again
+    bool seg_trust;                 // k_wind reads the lists of the call before (no k_prep in this call)
+};
+
+struct SbDiagPlan {
+    SbContrast contrast;
+    int scan_wgs, nsteps;
+    SbStep steps[SB_PLAN_MAX_STEPS];
+    bool wind_scratch;              // k_wind runs ahead of the contrast and leaves its winds in the nws / nwd planes
+    bool segs_built;                // after a complete call: the contrast step carried `fold`
+};
+
+// Marching strips (32 owned longitudes x 16-row blocks, flags strip-major with virtual blocks above and below every strip)
+// for LDS halos up to 16 cells; beyond, in single precision, the 96-column strip kernel answers radii up to 31 from LDS
+// -- what a distance field made with a window of up to 30 cells needs; double precision, sb_set_wide_strip(ctx, 0) and
+// grids the strip kernels' position planes cannot hold take LDS tiles (halos of 24 and 32 cells, row-major flags).
+inline SbContrast sb_plan_contrast(const SbPlanIn &in) {
+    const SbShapes &s = in.shapes;
+    SbContrast k{};
+    if (in.halo > 16 && in.esize == 4 && !in.no_wide_strip && s.strip32_fits) k.strip = 2;
+    else if (in.halo <= 16 && s.strip_fits) k.strip = 1;
+    if (k.strip) {
+        k.Hk = 16 * k.strip; k.vb = k.strip; k.txw = 32; k.tyrows = 16;
+        k.tx = k.strip == 2 ? s.strip32_ntx : s.strip_ntx;
+        k.ty = k.strip == 2 ? s.strip32_nty : s.strip_nty;
+        k.ntile = k.tx * (k.ty + 2 * k.vb);
+    } else {
+        k.Hk = in.halo > 16 ? in.halo : 24;
+        k.txw = s.tile_w; k.tyrows = k.Hk <= 24 ? s.tile_rows24 : s.tile_rows32;
+        k.tx = (in.nx + k.txw - 1) / k.txw; k.ty = (in.rows + k.tyrows - 1) / k.tyrows;
+        k.ntile = k.tx * k.ty;
+    }
+    k.nflag = k.ntile + 2;
+    return k;
+}
+
+inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
+    SbDiagPlan p{};
+    p.contrast = sb_plan_contrast(in);
+    p.scan_wgs = in.scan_wgs;
+    const bool strip = p.contrast.strip != 0, reuse = in.reuse_stats, ph1 = (in.phases & 1) != 0, ph2 = (in.phases & 2) != 0;
+    // the strip kernel does k_prep's work itself (host-model flavour: one dependent launch less on the critical path)
+    const bool folds = strip && in.t0_fly && !in.no_fold && in.scan_wgs <= SB_FOLD_MAX_PARTS;
+    // the segment lists the strip kernel of the call before compacted belong to the planes its stored plan belongs to
+    const bool stand = folds && in.plan_use && in.segs_built && !in.no_plan_cache;
+    // Whole single-domain calls run the contrast first and let k_wind apply the update.  A band step runs k_scan and
+    // k_wind ahead of the join with the communication stream and applies the update in the contrast kernel; its
+    // single-domain order (sb_set_band_order) was measured and is slower.
+    const bool whole = in.phases == 3 && !in.gathered;
+    const bool late_wind = in.band_late_wind && in.gathered && folds;
+    p.wind_scratch = !(whole || late_wind);
+    SbStep *contrast = nullptr;
+    auto add = [&p](SbKernel k, int prof, bool stats = false, int nparts = 0) -> SbStep & {
+        SbStep &s = p.steps[p.nsteps++];
+        s.kernel = (signed char)k; s.prof = (signed char)prof; s.wind_final = !p.wind_scratch;
+        s.stats = stats ? SB_STATS_PARTIALS : SB_STATS_NONE; s.nparts = nparts;
+        return s;
+    };
+    if (whole) {
+        const int nparts = reuse ? 0 : in.scan_wgs;
+        add(SB_K_SCAN, SB_PROF_SCAN, !reuse);
+        if (!folds) add(SB_K_PREP, SB_PROF_PREP, !reuse, nparts);
+        if (!in.t0_fly) add(SB_K_T0, SB_PROF_T0);
+        contrast = &add(SB_K_CONTRAST, SB_PROF_THC, folds, folds ? nparts : 0);
+        contrast->fold = folds;
+        add(SB_K_WIND, SB_PROF_WIND);
+        for (int i = 0; i < p.nsteps; ++i) p.steps[i].lists_stand = stand;
+    } else if (late_wind) {
+        // a band step in the single-domain order: k_scan ahead of the join; behind it the strip kernel -- it merges the
+        // gathered moments and compacts k_wind's segment lists itself -- and k_wind with the update.  (Never profiled.)
+        const bool publishes = in.moments_out && !reuse;
+        if (ph1) add(SB_K_SCAN, SB_PROF_NONE, publishes).publish = publishes;
+        if (ph2) {
+            contrast = &add(SB_K_CONTRAST, SB_PROF_NONE);
+            contrast->fold = true;
+            if (!reuse) contrast->stats = SB_STATS_GATHERED;
+            add(SB_K_WIND, SB_PROF_NONE);
+        }
+    } else {
+        if (ph1) {
+            // a band step: k_scan's last workgroup merges and publishes this band's moments (the all-gather starts behind it)
+            const bool own = (!in.gathered || in.moments_out) && !reuse, publishes = own && in.gathered;
+            const bool trust = stand && in.gathered;
+            add(SB_K_SCAN, SB_PROF_SCAN, own).publish = publishes;
+            if (!trust) add(SB_K_PREP, SB_PROF_PREP, own && !publishes, own && !publishes ? in.scan_wgs : 0);
+            add(SB_K_WIND, SB_PROF_WIND).seg_trust = trust;
+        }
+        if (ph2) {
+            const bool merge = in.gathered && !reuse;
+            // k_t0 needs the scalars first; the contrast kernel that derives t0 merges the gathered moments in its prologue
+            if (merge && !in.t0_fly) add(SB_K_MERGE, SB_PROF_NONE).stats = SB_STATS_GATHERED;
+            if (!in.t0_fly) add(SB_K_T0, SB_PROF_T0);
+            contrast = &add(SB_K_CONTRAST, SB_PROF_THC);
+            if (merge && in.t0_fly) contrast->stats = SB_STATS_GATHERED;
+            // the strip kernel applies thresholds and state update behind its march whatever the order (it leaves the
+            // contrast in thc) and compacts the segment lists: this call's update reads them, and the next call's k_wind
+            // if the planes stand (no k_prep then)
+            if (strip) { contrast->wind_final = contrast->strip_update = true; contrast->fold = folds; }
+        }
+    }
+    p.segs_built = contrast && contrast->fold;
+    return p;
+}

@@ -1,12 +1,10 @@
 // sb_launch.hpp -- host-side launcher declarations shared by the kernel files and the C ABI.
 #pragma once
 #include "sb_device.hpp"
+#include "sb_diag_plan.hpp"
 
 #define SB_STATS_MAX_BLOCKS 2048
-#define SB_MAX_LDS_HALO 32          // largest LDS halo the contrast kernel (k_thc3) is instantiated for
 #define SB_DIST_TY 4                // rows per k_dist tile
-// kernels of a diag call that sb_profile_begin / sb_profile_end time, each with its own pair of events
-enum { SB_PROF_SCAN = 0, SB_PROF_WIND = 1, SB_PROF_T0 = 2, SB_PROF_THC = 3, SB_PROF_PREP = 4, SB_PROF_KERNELS = 5 };
 #define SB_PROF_EVENTS (2 * SB_PROF_KERNELS)
 #ifndef SB_WIND_UN
 #define SB_WIND_UN 8                // levels of a p column in flight per lane of k_wind
@@ -36,13 +34,6 @@ struct SbLaunchCtx {
     hipEvent_t moments_event;       // ... and this event is recorded behind k_scan, or nullptr
     int *stats_ticket;              // ... with this device word (zero between launches) as the workgroups' ticket
     int ncu;                        // compute units (k_scan and the contrast kernel run one workgroup per CU)
-    int phases;                     // bit 0: k_scan + k_prep + k_wind (no ghost cells, no statistics needed);
-                                    // bit 1: statistics of all bands, k_t0, k_thc3.  3 = the whole call
-    bool reuse_stats;               // the sigmoid scalars in `stats` stand (static sigma): no moments, no merge
-    bool no_fold;                   // keep k_prep as a kernel of its own (sb_set_fold(ctx, 0): measurement and tests)
-    bool segs_stand;                // band step on the strip kernel: the segment lists of the call before are in place
-                                    // (same geometry; k_wind checks on the device that the planes did not change): no k_prep
-    int *launches;                  // += kernels enqueued by the call, or nullptr
 };
 
 template <typename T>
@@ -51,8 +42,17 @@ hipError_t sb_launch_stats(const T *ary, int nx, int ny, int ld, size_t off0, Mo
                                                                                 // ticket: a device word that is zero between launches
 template <typename T>
 hipError_t sb_launch_sigmoid_apply(const T *ary, T *sm, size_t n, const T *stats, hipStream_t st);
+// workgroups of k_scan for nseg 64-cell segments: 16 waves x one trip of 2 segments each, so that a small domain (a band of
+// a multi-GPU run) is spread over all CUs and its waves make few dependent trips -- k_scan is latency, not bytes, there;
+// at most one 1024-thread workgroup per CU, two trips of loads in flight (two workgroups per CU, 8 waves per SIMD, measured
+// slower in round 4: k_scan 25.0 -> 28.7 us at 2560x1920 fp64, 60.1 -> 65.0 at 5120x3840 fp32)
+inline int sb_scan_workgroups(unsigned nseg, int ncu) {
+    const int nblk = (int)((nseg + 31) / 32);
+    return nblk < 1 ? 1 : nblk > ncu ? ncu : nblk;
+}
+// enqueues the steps of `plan` (sb_diag_plan.hpp), each with the job in the step's mode
 template <typename T>
-hipError_t sb_launch_diag(const DiagJob<T> &job, int H, const SbLaunchCtx &lc);
+hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const SbLaunchCtx &lc);
 // tile size of the tile contrast kernel (k_thc3) for an LDS halo of H = 24 or 32 cells
 void sb_thc_tile_shape(int H, int *tx, int *ty);
 // the tile contrast kernel (halos of 24 and 32 cells): reads the list of active tiles and the sigmoid scalars k_prep left
@@ -73,6 +73,15 @@ hipError_t sb_launch_strip32<float>(const DiagJob<float> &job, int ncu, hipStrea
 template <>
 hipError_t sb_launch_strip32<double>(const DiagJob<double> &job, int ncu, hipStream_t st);
 bool sb_strip32_shape(int nx, int rows, int *ntx, int *nty);
+// what the three contrast kernels answer for a domain of nx x rows interior cells: the plan's input
+inline SbShapes sb_contrast_shapes(int nx, int rows) {
+    SbShapes s;
+    s.strip_fits = sb_strip_shape(nx, rows, &s.strip_ntx, &s.strip_nty);
+    s.strip32_fits = sb_strip32_shape(nx, rows, &s.strip32_ntx, &s.strip32_nty);
+    sb_thc_tile_shape(24, &s.tile_w, &s.tile_rows24);
+    sb_thc_tile_shape(32, &s.tile_w, &s.tile_rows32);
+    return s;
+}
 
 // theta <- theta - (gmma*z)*sigmoid(sigma) over n cells, with the scalars the last diag call left in `stats`
 template <typename T>
