@@ -22,7 +22,7 @@ module sb_context_mod
   private
   public :: sb_ctx, sb_ensure_ctx, sb_fail, sb_release_ctx
   public :: sb_comm_get_unique_id, sb_comm_init, sb_comm_finalize, sb_comm_active, sb_comm_rank
-  public :: sb_set_static_sigma, sb_last_step_report
+  public :: sb_set_static_sigma, sb_set_table_contrast, sb_last_step_report
   public :: sb_dev_alloc, sb_dev_free, sb_dev_upload, sb_dev_download, sb_device_synchronize
 
   type(c_ptr), save :: sb_ctx = c_null_ptr
@@ -60,6 +60,11 @@ module sb_context_mod
       type(c_ptr), value :: ctx
     end function
     integer(c_int) function c_set_static_sigma(ctx, on) bind(C, name="sb_set_static_sigma")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function c_set_table_contrast(ctx, on) bind(C, name="sb_set_table_contrast")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
       integer(c_int), value :: on
@@ -194,6 +199,17 @@ contains
     rc = c_set_static_sigma(sb_ctx, merge(1_c_int, 0_c_int, on))
     if (rc /= 0) call sb_fail('sb_set_static_sigma', rc)
   end subroutine sb_set_static_sigma
+
+  !> Opt-in: whole single-domain seabreeze_diag calls take the land-sea contrast from device-wide summed-area tables --
+  !! radii up to 127 at a cost that does not depend on the radius (regional grids of a few km).
+  !! include/seabreeze_hip.h: sb_set_table_contrast.
+  subroutine sb_set_table_contrast(on)
+    logical, intent(in) :: on
+    integer(c_int) :: rc
+    call sb_ensure_ctx()
+    rc = c_set_table_contrast(sb_ctx, merge(1_c_int, 0_c_int, on))
+    if (rc /= 0) call sb_fail('sb_set_table_contrast', rc)
+  end subroutine sb_set_table_contrast
 
   !> What the last diag call / band step enqueued: kernel launches, RCCL operations, RCCL groups, device copies.
   subroutine sb_last_step_report(launches, rccl_ops, rccl_groups, copies)

@@ -120,6 +120,25 @@ int  sb_set_workgroups(sb_ctx *ctx, int n);
    all-gather and the merge.  Results are those of the default path as long as the statement holds; any other
    sigma array, or switching the option again, forms the statistics anew.                                  */
 int  sb_set_static_sigma(sb_ctx *ctx, int on);
+/* Opt-in, off by default: the land-sea contrast from device-wide summed-area tables, at a cost per band cell that does not
+   depend on the radius of its window -- for grids on which band cells lie further from the other class than the LDS
+   kernels reach (radius hint 32 at the most), where every such cell otherwise takes the global-memory path: regional
+   grids of a few km, whose 180 km band is 45 (4 km) to 120 (1.5 km) cells wide.  Every call builds three tables over the
+   whole ghost-celled frame -- prefix sums of t0 in 64-bit fixed point (2^-36 K, rounded once), of the same over
+   land-side cells and of the land-side count: 20 bytes per frame cell of grow-only workspace, allocated by the first
+   call that uses them -- and answers every band cell from them: the radius by bisection on the count table, the two
+   window sums exactly.  Reach: radii up to 127; domain: |t0| < 2048 K (beyond, or NaN, the windows that hold the cell
+   are garbage, not a fault).  Cells beyond the reach, cells whose window is wider than the longitude circle and cells
+   that find one class only as far as they may search take the global-memory path as ever and are counted as ever
+   (sb_last_counters).  thc agrees with the other kernels to the rounding of the window means (fp64: within the 1e-7
+   the tests hold against the reference; the fixed-point rounding moves sb_con by 2.1e-10 at the most).
+   Takes effect for WHOLE SINGLE-DOMAIN calls of the host-model flavour -- sb_seabreeze_diag_*[_dev],
+   sb_seabreeze_diag_um_*[_dev] -- with SB_BND_GLOBAL or SB_BND_HALO: six launches (k_scan, k_prep, two table passes, the
+   query, k_wind).  Silently ignored, i.e. exactly what runs without it, for the f2py flavour (sb_diag_*, sb_diag_stream_*),
+   for SB_BND_WRAPPER, for band steps (sb_band_seabreeze_diag_*) and while gathered moments are in use.  It is never
+   chosen automatically, whatever the radius hint.  sb_profile_end reports the row pass under [2] and the column pass
+   and the query together under [3] for such calls.                                                                 */
+int  sb_set_table_contrast(sb_ctx *ctx, int on);
 /* What the last diag call or band step enqueued on this rank: [0] kernel launches, [1] RCCL operations (sends,
    receives, all-gathers), [2] RCCL groups, [3] device-to-device copies.  No synchronisation.               */
 int  sb_last_step_report(sb_ctx *ctx, int report[4]);

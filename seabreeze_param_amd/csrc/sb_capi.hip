@@ -136,6 +136,7 @@ struct sb_ctx {
     int no_plan_cache = 0;              // sb_set_plan_cache(ctx, 0): the strip kernel plans its march afresh every call
     int no_wide_strip = 0;              // sb_set_wide_strip(ctx, 0): radii beyond 16 take the tile kernel in single precision too
     int band_late_wind = 0;             // sb_set_band_order(ctx, 1): a band step runs the contrast before k_wind (measurement)
+    int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
     const void *stats_sigma = nullptr;
     int stats_dims[4] = {0, 0, 0, 0};   // nx, ny, halo, sizeof(T)
     int stats_ngathered = 0;            // bands whose moments the kept scalars were merged from (0: this domain's own)
@@ -144,6 +145,7 @@ struct sb_ctx {
     // workspace (grow-only)
     DevBuf t0, bandbits, clsbits, tiles, vecs, nws, nwd, coastbits, tile_list, seg_list, stamps, jobcopy, plan;
     DevBuf umbits;                      // the coast bit plane of sb_get_dist_um_*
+    DevBuf tabA, tabL, tabC, tabS;      // the device-wide summed-area tables (SbTables), allocated by the first call that builds them
     // the strip kernel's plan (sb_strip_kernel.hip): [64 bytes: number of the last call whose band plane changed |
     // ncu x SB_PLAN_STRIDE]; plan_key: the geometry it was made for; call_seq numbers the diag calls
     int plan_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -352,7 +354,18 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     in.reuse_stats = reuse_stats<T>(c, job.sigma, g.nx, g.ny, g.h);
     in.plan_use = c->plan_use != 0; in.segs_built = c->segs_built;
     in.scan_wgs = sb_scan_workgroups((unsigned)g.nyh * (unsigned)g.nw, c->ncu);
+    in.table = c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0;
     const SbDiagPlan plan = sb_plan_diag(in);
+    if (plan.table) {
+        // 20 bytes per frame cell, and the row pass' block sums: 20 bytes per column and block of SB_TAB_RB rows
+        const size_t nsum = (size_t)((g.nyh + SB_TAB_RB - 1) / SB_TAB_RB) * g.nxh;
+        if ((rc = ensure(c, c->tabA, ncell * sizeof(unsigned long long)))) return rc;
+        if ((rc = ensure(c, c->tabL, ncell * sizeof(unsigned long long)))) return rc;
+        if ((rc = ensure(c, c->tabC, ncell * sizeof(unsigned)))) return rc;
+        if ((rc = ensure(c, c->tabS, nsum * (2 * sizeof(unsigned long long) + sizeof(unsigned))))) return rc;
+        lc.tables.A = (unsigned long long *)c->tabA.p; lc.tables.L = (unsigned long long *)c->tabL.p; lc.tables.C = (unsigned *)c->tabC.p;
+        lc.tables.SA = (unsigned long long *)c->tabS.p; lc.tables.SL = lc.tables.SA + nsum; lc.tables.SC = (unsigned *)(lc.tables.SL + nsum);
+    }
     // this call's wind speed / direction at band cells, where k_wind runs ahead of the contrast (k_wind -> k_thc3)
     if (plan.wind_scratch) {
         if ((rc = ensure(c, c->nws, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
@@ -1202,7 +1215,7 @@ int sb_destroy(sb_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
-                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits})
+                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -1763,6 +1776,12 @@ int sb_set_static_sigma(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->static_sigma = on ? 1 : 0;
     c->stats_valid = false;
+    return SB_OK;
+}
+
+int sb_set_table_contrast(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->table_contrast = on ? 1 : 0;
     return SB_OK;
 }
 

@@ -654,7 +654,9 @@ hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const S
             if (s.stats == SB_STATS_GATHERED) { j.gath = lc.gathered; j.ngath = lc.ngathered; }
             if (s.fold || s.stats == SB_STATS_GATHERED) j.stats_out = (T *)lc.stats;     // it publishes the sigmoid scalars
         }
-        SB_EV_BEGIN(s.prof);
+        // (neighbouring steps that share a pair of events -- the column pass and the query of the tables -- are timed together)
+        const bool ev_open = i == 0 || plan.steps[i - 1].prof != s.prof, ev_close = i + 1 == plan.nsteps || plan.steps[i + 1].prof != s.prof;
+        if (ev_open) SB_EV_BEGIN(s.prof);
         switch (s.kernel) {
         case SB_K_SCAN: launch_scan<T>(j, plan.scan_wgs, lc.partials, s.stats == SB_STATS_PARTIALS, st); break;
         case SB_K_PREP:
@@ -663,10 +665,14 @@ hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const S
             break;
         case SB_K_MERGE: hipLaunchKernelGGL(k_merge_moments<T>, dim3(1), dim3(SB_WAVE), 0, st, lc.gathered, lc.ngathered, (T *)lc.stats); break;
         case SB_K_T0: hipLaunchKernelGGL(k_t0<T>, dim3((j.g.nxh + 255) / 256, j.g.nyh), dim3(256), 0, st, j); break;
-        case SB_K_CONTRAST: if ((e = launch_contrast<T>(j, plan.contrast.Hk, lc.ncu, st)) != hipSuccess) return e; break;
+        case SB_K_CONTRAST:
+            if ((e = s.table ? sb_launch_table_query<T>(j, lc.tables, lc.ncu, st) : launch_contrast<T>(j, plan.contrast.Hk, lc.ncu, st)) != hipSuccess) return e;
+            break;
         case SB_K_WIND: launch_wind<T>(j, lc.ncu, st); break;
+        case SB_K_TABLE_ROWS: if ((e = sb_launch_table_rows<T>(j, lc.tables, st)) != hipSuccess) return e; break;
+        case SB_K_TABLE_COLS: if ((e = sb_launch_table_cols(j.g, lc.tables, st)) != hipSuccess) return e; break;
         }
-        SB_EV_END(s.prof);
+        if (ev_close) SB_EV_END(s.prof);
         if (s.publish && lc.moments_event && (e = hipEventRecord(lc.moments_event, st)) != hipSuccess) return e;
     }
     return hipGetLastError();

@@ -6,7 +6,8 @@
 
 // kernels of a diag call that sb_profile_begin / sb_profile_end time, each with its own pair of events
 enum { SB_PROF_NONE = -1, SB_PROF_SCAN = 0, SB_PROF_WIND = 1, SB_PROF_T0 = 2, SB_PROF_THC = 3, SB_PROF_PREP = 4, SB_PROF_KERNELS = 5 };
-enum SbKernel { SB_K_SCAN, SB_K_PREP, SB_K_MERGE, SB_K_T0, SB_K_CONTRAST, SB_K_WIND };
+// (SB_K_TABLE_ROWS, SB_K_TABLE_COLS: the two passes that build the device-wide summed-area tables, sb_table_kernels.hip)
+enum SbKernel { SB_K_SCAN, SB_K_PREP, SB_K_MERGE, SB_K_T0, SB_K_CONTRAST, SB_K_WIND, SB_K_TABLE_ROWS, SB_K_TABLE_COLS };
 // sigma's statistics in a step.  k_scan: PARTIALS = it forms them; k_prep and the contrast kernel merge k_scan's `nparts`
 // partial moments (0: the scalars stand) or, as k_merge_moments does, the moments GATHERED from every band
 enum SbStatsSrc { SB_STATS_NONE, SB_STATS_PARTIALS, SB_STATS_GATHERED };
@@ -36,6 +37,8 @@ struct SbPlanIn {
                                     // strip kernel compacted k_wind's segment lists
     int scan_wgs;                   // k_scan's workgroups (sb_scan_workgroups, sb_launch.hpp)
     SbShapes shapes;
+    bool table;                     // sb_set_table_contrast is on and the call is one it serves as far as the caller can tell: host-model
+                                    // flavour, SB_BND_GLOBAL or SB_BND_HALO, Geo::band == 0 (whole call, no gathered moments: checked here)
 };
 
 // the contrast kernel of the call and its block / tile grid
@@ -56,6 +59,7 @@ struct SbStep {
     bool strip_update;              // the strip kernel applies thresholds and state update behind its march
     bool lists_stand;               // DiagJob::lists_stand: a march by the stored plan does not compact the segment lists again
     bool seg_trust;                 // k_wind reads the lists of the call before (no k_prep in this call)
+    bool table;                     // the contrast is the query of the device-wide tables (k_table_query), not a strip / tile kernel
 };
 
 struct SbDiagPlan {
@@ -64,6 +68,7 @@ struct SbDiagPlan {
     SbStep steps[SB_PLAN_MAX_STEPS];
     bool wind_scratch;              // k_wind runs ahead of the contrast and leaves its winds in the nws / nwd planes
     bool segs_built;                // after a complete call: the contrast step carried `fold`
+    bool table;                     // the call builds and queries the device-wide tables: run_diag sizes their workspace
 };
 
 // Marching strips (32 owned longitudes x 16-row blocks, flags strip-major with virtual blocks above and below every strip)
@@ -112,7 +117,20 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
         s.stats = stats ? SB_STATS_PARTIALS : SB_STATS_NONE; s.nparts = nparts;
         return s;
     };
-    if (whole) {
+    // Opt-in (sb_set_table_contrast), whole single-domain host-model calls only: the contrast of every band cell from
+    // device-wide summed-area tables, whatever its radius.  k_prep merges the moments, publishes the scalars the row pass
+    // forms t0 with and compacts the segment lists the query takes its band cells from.  A profiled call times the row
+    // pass in k_t0's pair (the host-model flavour has no k_t0), the column pass and the query together in the contrast's.
+    p.table = in.table && whole && in.t0_fly;
+    if (p.table) {
+        add(SB_K_SCAN, SB_PROF_SCAN, !reuse);
+        add(SB_K_PREP, SB_PROF_PREP, !reuse, reuse ? 0 : in.scan_wgs);
+        add(SB_K_TABLE_ROWS, SB_PROF_T0);
+        add(SB_K_TABLE_COLS, SB_PROF_THC);
+        contrast = &add(SB_K_CONTRAST, SB_PROF_THC);
+        contrast->table = true;
+        add(SB_K_WIND, SB_PROF_WIND);
+    } else if (whole) {
         const int nparts = reuse ? 0 : in.scan_wgs;
         add(SB_K_SCAN, SB_PROF_SCAN, !reuse);
         if (!folds) add(SB_K_PREP, SB_PROF_PREP, !reuse, nparts);

@@ -21,6 +21,25 @@
 #define SB_WIND_WGS_PER_CU_F32 8    // 16 x 4 131.8, 16 x 6 126.4, 8 x 8 120.3, 14 x 7 119.1, 19 x 8 117.6, 28 x 8 118.1,
 #endif                              // 14 x 8 114.3-118.1; 2560x1920x56 fp32: 50.1 -> 39.7 us
 
+// The device-wide summed-area tables of sb_set_table_contrast (sb_table_kernels.hip) over the (nxh, nyh) frame: inclusive
+// 2-D prefix sums of t0 in fixed point with SB_TAB_FB fractional bits (A), of the same over land-side cells (L) and of
+// the land-side count (C); S*: per block of SB_TAB_RB rows and per column the block's sum of the row-prefixed values,
+// which the row pass leaves for the column pass.  Unsigned: the sums wrap, the differences a query forms do not.
+//   Format.  A window of (2R+1)^2 values below 2^11 K must fit 63 bits: (2R+1)^2 2^(11+F) < 2^63.  A value is rounded
+// once, by at most 2^-(F+1) K, so a window mean and hence thc moves by at most 2 2^-(F+1) K, which sb_con amplifies by at
+// most 11/0.75 (scale_wind <= thr_wind / 1, d scale_thc / d thc <= 1 / thr_thc); the double-precision tests allow
+// 1e-7 max(|ref|, 1e-2), so that bound must stay below 1e-9.  F = 36: reach R = 127 (255^2 = 65025 < 2^16), bound
+// 2^-36 11/0.75 = 2.1e-10, and every single-precision value of magnitude >= 2^-12 is exact.  One format for both precisions.
+#define SB_TAB_FB 36
+#define SB_TAB_REACH 127
+#define SB_TAB_RB 16                // rows per workgroup of the row pass = rows of a block of S
+static_assert((2 * SB_TAB_REACH + 1) * (2 * SB_TAB_REACH + 1) < (1 << (63 - 11 - SB_TAB_FB)), "a window at the reach must fit 63 bits");
+static_assert((2 * SB_TAB_REACH + 3) * (2 * SB_TAB_REACH + 3) >= (1 << (63 - 11 - SB_TAB_FB)), "the reach is the largest the format holds");
+struct SbTables {
+    unsigned long long *A, *L, *SA, *SL;
+    unsigned *C, *SC;
+};
+
 // Everything of the context a diag launch needs besides the job itself.
 struct SbLaunchCtx {
     hipStream_t stream;             // every kernel of the call is enqueued here
@@ -34,6 +53,7 @@ struct SbLaunchCtx {
     hipEvent_t moments_event;       // ... and this event is recorded behind k_scan, or nullptr
     int *stats_ticket;              // ... with this device word (zero between launches) as the workgroups' ticket
     int ncu;                        // compute units (k_scan and the contrast kernel run one workgroup per CU)
+    SbTables tables;                // a call whose plan builds the device-wide tables (SbDiagPlan::table)
 };
 
 template <typename T>
@@ -82,6 +102,14 @@ inline SbShapes sb_contrast_shapes(int nx, int rows) {
     sb_thc_tile_shape(32, &s.tile_w, &s.tile_rows32);
     return s;
 }
+
+// the device-wide tables (sb_table_kernels.hip): the row pass (t0 -> fixed point -> prefix along longitude, block sums for
+// the column pass), the column pass (prefix along latitude, in place), the query (one wave per listed segment -> thc)
+template <typename T>
+hipError_t sb_launch_table_rows(const DiagJob<T> &job, const SbTables &tb, hipStream_t st);
+hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st);
+template <typename T>
+hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st);
 
 // theta <- theta - (gmma*z)*sigmoid(sigma) over n cells, with the scalars the last diag call left in `stats`
 template <typename T>

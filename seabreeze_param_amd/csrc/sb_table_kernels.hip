@@ -1,0 +1,290 @@
+// sb_table_kernels.hip -- the land-sea contrast from DEVICE-WIDE summed-area tables (sb_set_table_contrast): the strip
+// kernels' idea -- exact fixed-point tables of t0, of land-side t0 and of the land-side count, four reads per table
+// per window -- lifted from LDS to device memory, so that the cost of a band cell does not depend on the radius of its
+// window.   ref: generic/sea_breeze_diag.f90:188-216
+//
+//   k_table_rows   one wave per frame row: t0 (the one sequence, sb_t0) -> fixed point, rounded once (SB_TAB_FB, sb_launch.hpp)
+//                  -> inclusive prefix along longitude of {all, land side, land-side count} by DPP scans with a carry
+//                  between the 64-cell segments of the row.  The SB_TAB_RB waves of a workgroup add their prefixed rows
+//                  up per column (LDS atomics, 1024 columns at a time): S, the block sums the column pass starts from.
+//   k_table_cols   prefix along latitude, in place, BLOCKED: a workgroup takes 256 columns x 64 rows, starts from the sum of
+//                  the blocks of S above it (independent loads, a few dozen) and walks its rows with eight rows of loads
+//                  in flight.  Lanes run along longitude: every access is a whole line.  (One chain per column over all
+//                  rows would leave nxh threads alive; a march of whole column strips a few hundred waves.)
+//   k_table_query  one wave per listed 64-cell segment (k_prep's lists, as k_wind), band lanes active: the smallest radius
+//                  whose square holds both classes by galloping and bisection on the count table alone, then the two
+//                  window sums, the means, thc.  Cells the tables cannot answer take contrast_global, here.
+// The sums are wrapping unsigned adds: a window sum is the exact sum of once-rounded values, whatever the launch geometry.
+#include "sb_thc_common.hpp"
+#include "sb_strip_common.hpp"
+
+#define TAB_ROWS_NT (SB_TAB_RB * SB_WAVE)
+#define TAB_CH 16                  // segments of a row between two hand-overs of block sums (TAB_CH * 64 == TAB_ROWS_NT columns)
+#define TAB_COLS_NT 256
+#define TAB_CB 64                  // rows of a block of the column pass
+#define TAB_QUERY_NT 256
+static_assert(TAB_CH * SB_WAVE == TAB_ROWS_NT, "one thread per column of a chunk");
+static_assert(TAB_CB % SB_TAB_RB == 0 && (TAB_CB / SB_TAB_RB) % 4 == 0, "a block of the column pass is whole blocks of S, four at a time");
+
+// t0 (K) -> fixed point: fma rounds x * 2^F + 1.5 * 2^52 to an integer held in the mantissa (|x| < 2048 K; beyond, and for
+// NaN, the windows that hold the cell are garbage, not a fault -- and only those: the sums wrap); the bias is taken out here
+__device__ __forceinline__ u64 tab_fixed(double x) {
+    return (u64)__double_as_longlong(__builtin_fma(x, (double)(1ll << SB_TAB_FB), 0x1.8p52)) - 0x4338000000000000ull;
+}
+__device__ __forceinline__ u64 tab_readlane63(u64 v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((u64)hi << 32) | lo;
+}
+
+// ---- the row pass
+template <typename T>
+__global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTables tb) {
+    const Geo g = job.g;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int Y = __builtin_amdgcn_readfirstlane((int)blockIdx.x * SB_TAB_RB + wv);
+    const bool rowok = Y < g.nyh;                        // (wave-uniform; the waves beyond the frame only keep the barriers)
+    const size_t row = (size_t)(rowok ? Y : g.nyh - 1) * g.nxh;
+    const uint64_t *cls = job.clsbits + (size_t)(rowok ? Y : g.nyh - 1) * g.nw;
+    const T sd = job.stats[0], rr = job.stats[1];
+    __shared__ u64 sA[TAB_ROWS_NT], sL[TAB_ROWS_NT];
+    __shared__ unsigned sC[TAB_ROWS_NT];
+    u64 carA = 0, carL = 0;
+    unsigned carC = 0;
+    struct In { T th, zz, sg; uint64_t word; };
+    auto issue = [&](int w) {                            // every load unconditional, from a clamped address
+        const int X = min(w * 64 + lane, g.nxh - 1);
+        In r;
+        r.th = job.t0_fly ? job.theta[row + X] : job.t0[row + X];
+        r.zz = job.z[row + X]; r.sg = job.sigma[row + X];
+        r.word = cls[min(w, g.nw - 1)];
+        return r;
+    };
+    auto segment = [&](int w, const In &r) {
+        const int X = w * 64 + lane;
+        const bool in = X < g.nxh;
+        const T t0v = job.t0_fly ? sb_t0<T>(r.th, r.zz, r.sg, sd, rr) : r.th;
+        const bool land = ((r.word >> lane) & 1ull) != 0ull;          // (no bits beyond the frame: k_scan)
+        u64 a = in ? tab_fixed((double)t0v) : 0ull, l = land ? a : 0ull;
+        int c = land ? 1 : 0;
+        sb_scan2_u64(a, l);                              // (all 64 lanes)
+        c = sb_wave_scan_add(c);
+        a += carA; l += carL;
+        const unsigned cc = (unsigned)c + carC;
+        carA = tab_readlane63(a); carL = tab_readlane63(l);
+        carC = (unsigned)__builtin_amdgcn_readlane((int)cc, 63);
+        if (in) {
+            tb.A[row + X] = a; tb.L[row + X] = l; tb.C[row + X] = cc;
+            const int k = X & (TAB_ROWS_NT - 1);
+            atomicAdd((unsigned long long *)&sA[k], (unsigned long long)a);
+            atomicAdd((unsigned long long *)&sL[k], (unsigned long long)l);
+            atomicAdd(&sC[k], cc);
+        }
+    };
+    for (int w0 = 0; w0 < g.nw; w0 += TAB_CH) {
+        sA[tid] = 0; sL[tid] = 0; sC[tid] = 0;           // (this thread read its column of the chunk before: see below)
+        __syncthreads();
+        if (rowok) {
+            const int w1 = min(w0 + TAB_CH, g.nw);
+            In cur = issue(w0);
+            for (int w = w0; w < w1; ++w) {
+                const In nxt = issue(min(w + 1, w1 - 1));        // the next segment travels under this one's logistic
+                segment(w, cur);
+                cur = nxt;
+            }
+        }
+        __syncthreads();
+        const int X = w0 * 64 + tid;
+        if (X < g.nxh) {
+            const size_t si = (size_t)blockIdx.x * g.nxh + X;
+            tb.SA[si] = sA[tid]; tb.SL[si] = sL[tid]; tb.SC[si] = sC[tid];
+        }
+    }
+}
+
+// ---- the column pass
+__global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, int nbx, SbTables tb) {
+    const int bx = (int)(blockIdx.x % (unsigned)nbx), b = (int)(blockIdx.x / (unsigned)nbx);
+    const int X = bx * TAB_COLS_NT + (int)threadIdx.x;
+    if (X >= nxh) return;
+    u64 ra = 0, rl = 0;
+    unsigned rc = 0;
+    const int nsb = b * (TAB_CB / SB_TAB_RB);            // blocks of S above this block: a multiple of four
+    for (int j = 0; j < nsb; j += 4) {
+        u64 a[4], l[4];
+        unsigned c[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t si = (size_t)(j + q) * nxh + X;
+            a[q] = tb.SA[si]; l[q] = tb.SL[si]; c[q] = tb.SC[si];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { ra += a[q]; rl += l[q]; rc += c[q]; }
+    }
+    const int Y0 = b * TAB_CB, Y1 = min(Y0 + TAB_CB, nyh);
+    for (int Ys = Y0; Ys < Y1; Ys += 8) {
+        u64 a[8], l[8];
+        unsigned c[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const size_t i = (size_t)min(Ys + q, Y1 - 1) * nxh + X;
+            a[q] = tb.A[i]; l[q] = tb.L[i]; c[q] = tb.C[i];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            if (Ys + q < Y1) {
+                const size_t i = (size_t)(Ys + q) * nxh + X;
+                ra += a[q]; rl += l[q]; rc += c[q];
+                tb.A[i] = ra; tb.L[i] = rl; tb.C[i] = rc;
+            }
+        }
+    }
+}
+
+// ---- the query
+// The square of radius nn round interior cell (x, y) as rectangles of the frame -- sb_map_cell's rule for the two boundary
+// modes the tables serve.  SB_BND_HALO (Geo::band == 0): no wrap, no clamp, the caller keeps nn within the frame reach.
+// SB_BND_GLOBAL: longitude periodic, at most two column ranges while 2 nn + 1 <= nx; latitude clamped, a row beyond a
+// pole is the edge row again, once per repetition: the rows in range plus `below` times row 0 plus `above` times row ny - 1.
+struct TabWin { int xa0, xb0, xa1, xb1, ya, yb, below, above; };      // (xa1 > xb1: one column range)
+__device__ __forceinline__ TabWin tab_window(const Geo &g, int x, int y, int nn) {
+    TabWin w;
+    w.xa1 = 1; w.xb1 = 0; w.below = w.above = 0;
+    if (g.bnd == BND_HALO) {
+        w.xa0 = x + g.h - nn; w.xb0 = x + g.h + nn; w.ya = y + g.h - nn; w.yb = y + g.h + nn;
+        return w;
+    }
+    const int lo = x - nn, hi = x + nn;
+    if (lo < 0) { w.xa0 = lo + g.nx; w.xb0 = g.nx - 1; w.xa1 = 0; w.xb1 = hi; }
+    else if (hi >= g.nx) { w.xa0 = lo; w.xb0 = g.nx - 1; w.xa1 = 0; w.xb1 = hi - g.nx; }
+    else { w.xa0 = lo; w.xb0 = hi; }
+    w.ya = max(y - nn, 0); w.yb = min(y + nn, g.ny - 1);
+    w.below = max(nn - y, 0); w.above = max(y + nn - (g.ny - 1), 0);
+    return w;
+}
+// P(Y, X), zero in front of the frame (every address clamped into it)
+template <typename V>
+__device__ __forceinline__ V tab_at(const V *t, const Geo &g, int Y, int X) {
+    const V v = t[(size_t)min(max(Y, 0), g.nyh - 1) * g.nxh + min(max(X, 0), g.nxh - 1)];
+    return (X < 0 || Y < 0) ? V(0) : v;
+}
+template <typename V>
+__device__ __forceinline__ V tab_rect(const V *t, const Geo &g, int xa, int xb, int ya, int yb) {
+    return (tab_at(t, g, yb, xb) - tab_at(t, g, ya - 1, xb)) - (tab_at(t, g, yb, xa - 1) - tab_at(t, g, ya - 1, xa - 1));
+}
+template <typename V>
+__device__ __forceinline__ V tab_cols(const V *t, const Geo &g, const TabWin &w, int xa, int xb) {
+    V s = tab_rect(t, g, xa, xb, w.ya, w.yb);
+    if (w.below) s += (V)w.below * tab_rect(t, g, xa, xb, 0, 0);
+    if (w.above) s += (V)w.above * tab_rect(t, g, xa, xb, g.ny - 1, g.ny - 1);
+    return s;
+}
+template <typename V>
+__device__ __forceinline__ V tab_sum(const V *t, const Geo &g, const TabWin &w) {
+    V s = tab_cols(t, g, w, w.xa0, w.xb0);
+    if (w.xa1 <= w.xb1) s += tab_cols(t, g, w, w.xa1, w.xb1);
+    return s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, SbTables tb) {
+    const Geo g = job.g;
+    const int lane = threadIdx.x & 63;
+    // the sub-lists' sizes -> position of an entry, as k_wind
+    const int cnt = lane < SB_SEG_PARTS ? job.seg_count[lane] : 0;
+    const int incl = sb_wave_scan_add(cnt);
+    const int total = __builtin_amdgcn_readlane(incl, SB_SEG_PARTS - 1);
+    const int nwaves = gridDim.x * (TAB_QUERY_NT / SB_WAVE);
+    const int gw = __builtin_amdgcn_readfirstlane(blockIdx.x * (TAB_QUERY_NT / SB_WAVE) + (threadIdx.x >> 6));
+    auto entry = [&](int e) {
+        const uint64_t hit = __ballot(lane < SB_SEG_PARTS && e < incl);
+        const int part = hit ? __ffsll((unsigned long long)hit) - 1 : 0;
+        const int base = __shfl(incl, part) - __shfl(cnt, part);
+        return job.seg_list[(size_t)part * job.seg_cap + (e < total ? e - base : 0)];
+    };
+    const T sd = job.stats[0], rr = job.stats[1];
+    const bool limited = g.bnd == BND_HALO;
+    for (int e = gw; e < total; e += nwaves) {               // (wave-uniform)
+        const SbSegEntry cur = entry(e);
+        const unsigned Y = cur.seg / (unsigned)g.nw, Xw = cur.seg - Y * (unsigned)g.nw;
+        const int x = (int)(Xw * 64u) + lane - g.h, y = (int)Y - g.h;
+        int nnmax = 0, flag = -1;
+        if ((cur.word >> lane) & 1ull) {                     // band bits are set for interior cells of processed rows only
+            const unsigned o = (unsigned)y * (unsigned)g.nx + (unsigned)x;
+            // the largest radius the tables answer for this cell: the reach of the format; the frame (no wrap, no clamp:
+            // strip_frame_reach) or the circle (2 nn + 1 <= nx)
+            const int cap = min(SB_TAB_REACH, limited ? strip_frame_reach(g, x, y) : (g.nx - 1) / 2);
+            auto count = [&](int rad) { return (int)tab_sum<unsigned>(tb.C, g, tab_window(g, x, y, rad)); };
+            auto mixed = [](int nl, int rad) { return nl > 0 && nl < (2 * rad + 1) * (2 * rad + 1); };
+            // "the square of radius nn holds both classes" is monotone in nn: gallop to the first radius that does, bisect
+            // between it and the last that did not
+            bool found = false;
+            int hi = 0, nl = 0, below = 0;
+            if (cap >= 1) {
+                for (int r = 1;;) {
+                    const int c = count(r);
+                    if (mixed(c, r)) { found = true; hi = r; nl = c; break; }
+                    if (r >= cap) break;
+                    below = r;
+                    r = min(2 * r, cap);
+                }
+                for (int lo = below + 1; found && lo < hi;) {
+                    const int mid = (lo + hi) >> 1, c = count(mid);
+                    if (mixed(c, mid)) { hi = mid; nl = c; } else lo = mid + 1;
+                }
+            }
+            const T mul = sb_bit(job.clsbits, g.nw, x + g.h, y + g.h) ? T(1) : T(-1);
+            if (found) {
+                const TabWin w = tab_window(g, x, y, hi);
+                const long long TL = (long long)tab_sum<u64>(tb.L, g, w), TS = (long long)(tab_sum<u64>(tb.A, g, w) - (u64)TL);
+                auto to_f64 = [](long long v) { return __builtin_fma((double)(int)(v >> 32), 0x1p32, (double)(unsigned)v); };
+                const double dnl = (double)nl, dns = (double)((2 * hi + 1) * (2 * hi + 1) - nl);
+                const double ml = to_f64(TL) * sb_inv(dnl), ms = to_f64(TS) * sb_inv(dns);
+                job.thc[o] = mul * (T)((ml - ms) * (1.0 / (double)(1ll << SB_TAB_FB)));          // ref :216; k_wind applies :235-266
+                nnmax = hi;
+            } else {
+                // beyond the reach, wider than the circle, or one class as far as the search may go: the global-memory
+                // search, with the bound and the counters of a marked cell of the strip kernels (strip_slow_cell)
+                int capg = g.nx + g.ny;
+                if (limited) capg = min(capg, strip_frame_reach(g, x, y));
+                bool one_class;
+                const T cg = contrast_global(job, x, y, capg, sd, rr, nnmax, one_class);
+                atomicAdd(&job.counters[0], 1);
+                if (one_class) atomicAdd(&job.counters[1], 1);
+                job.thc[o] = mul * cg;
+            }
+            flag = (x >> job.thc_txs) * job.tile_sx + (y / job.thc_ty) * job.tile_sy + job.tile_off;
+        }
+        // the largest radius per block / tile (diagnostic, read by sb_last_counters; the flag k_scan raised is 1): one atomic
+        // per flag the segment's cells fall under
+        for (uint64_t todo = __ballot(nnmax > 1); todo;) {
+            const int f = __builtin_amdgcn_readlane(flag, __ffsll((unsigned long long)todo) - 1);
+            const bool mine = nnmax > 1 && flag == f;
+            const int v = sb_wave_max_to_last(mine ? nnmax : 0);
+            if (lane == SB_WAVE - 1) atomicMax(&job.tile_nnmax[f], v);
+            todo &= ~__ballot(mine);
+        }
+    }
+}
+
+// ---- launchers
+template <typename T>
+hipError_t sb_launch_table_rows(const DiagJob<T> &job, const SbTables &tb, hipStream_t st) {
+    const int nblk = (job.g.nyh + SB_TAB_RB - 1) / SB_TAB_RB;
+    hipLaunchKernelGGL(k_table_rows<T>, dim3(nblk), dim3(TAB_ROWS_NT), 0, st, job, tb);
+    return hipGetLastError();
+}
+hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st) {
+    const int nbx = (g.nxh + TAB_COLS_NT - 1) / TAB_COLS_NT, nby = (g.nyh + TAB_CB - 1) / TAB_CB;
+    hipLaunchKernelGGL(k_table_cols, dim3((unsigned)nbx * (unsigned)nby), dim3(TAB_COLS_NT), 0, st, g.nxh, g.nyh, nbx, tb);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st) {
+    if (!job.wind_final) return hipErrorInvalidValue;   // (the update is k_wind's: the plan sees to it)
+    hipLaunchKernelGGL(k_table_query<T>, dim3(ncu * 4), dim3(TAB_QUERY_NT), 0, st, job, tb);
+    return hipGetLastError();
+}
+template hipError_t sb_launch_table_rows<float>(const DiagJob<float> &, const SbTables &, hipStream_t);
+template hipError_t sb_launch_table_rows<double>(const DiagJob<double> &, const SbTables &, hipStream_t);
+template hipError_t sb_launch_table_query<float>(const DiagJob<float> &, const SbTables &, int, hipStream_t);
+template hipError_t sb_launch_table_query<double>(const DiagJob<double> &, const SbTables &, int, hipStream_t);

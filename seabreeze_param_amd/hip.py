@@ -151,6 +151,11 @@ class Context:
         """Opt-in: sigma does not change between calls; its statistics are formed once (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_static_sigma(self.h, C.c_int(1 if on else 0)), "sb_set_static_sigma")
 
+    def set_table_contrast(self, on: bool):
+        """Opt-in: whole single-domain host-model calls take the contrast from device-wide summed-area tables, radii up
+        to 127 at a cost that does not depend on the radius (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_table_contrast(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast")
+
     def last_step_report(self):
         """What the last diag call / band step enqueued on this rank."""
         arr = (C.c_int * 4)()

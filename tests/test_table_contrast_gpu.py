@@ -1,0 +1,344 @@
+"""The contrast from device-wide summed-area tables (sb_set_table_contrast, sb_table_kernels.hip): radii beyond what the
+LDS kernels reach, at a cost that does not depend on the radius.  ref: generic/sea_breeze_diag.f90:188-216.
+
+Everything goes through the C ABI.  Yardstick: the CPU oracle (oracle/sb_oracle.f90) on the same inputs; in double
+precision under the rule of tests/test_parity_gpu.py::_assert_close64, restated here: |a - ref| <= 1e-7 max(|ref|, 1e-2),
+NaN only where the reference has NaN.  In single precision the shared rule of oracle/fp32_criterion.py against the oracle's
+fp64 build.
+
+The block grid: 160 x 112 cells, every cell in the coastal band, land an 80 x 80 block that lies across the longitude seam
+and touches row 0 -- the cells in its middle are 40 cells from the sea, windows cross the seam (two column ranges) and
+reach beyond the pole row (the latitude clamp, with multiplicity).  The launch sequence of a table call is six kernels,
+k_scan, k_prep, the row pass, the column pass, the query, k_wind: two table passes, not fused (tests/test_table_plan.py).
+"""
+import numpy as np
+import pytest
+
+from conftest import relerr
+from oracle import fp32_criterion as crit
+from seabreeze_param_amd import hip, synth
+
+pytestmark = pytest.mark.gpu
+
+NX, NY, NZ, W = 160, 112, 3, 80
+DT_S = 7200.0
+TABLE_LAUNCHES = 6          # SCAN PREP TABLE_ROWS TABLE_COLS CONTRAST WIND
+NAMES = ("ws", "wd", "thc", "sb_con")
+f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _close64(a, b, what):
+    """|a - b| <= 1e-7 max(|b|, 1e-2); NaN exactly where b has NaN"""
+    assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what}: NaN pattern differs"
+    e = relerr(a, b, floor=1e-2)
+    assert e < 1e-7, f"{what}: rel err {e}"
+
+
+def _block_land(nx, ny, w, dx=0, dy=0, x0=0, y0=0):
+    """the block on columns x0 .. x0 + nx - 1 and rows y0 .. y0 + ny - 1 of the plane (period NX along longitude; rows below
+    0 continue the block), moved by dx columns and dy rows (the rows it leaves are sea)"""
+    x = np.arange(x0, x0 + nx)[None, :] - dx
+    y = np.arange(y0, y0 + ny)[:, None] - dy
+    land = (((x - (NX - 40)) % NX) < w) & (y < w)
+    return land & (y >= 0) if dy else land
+
+
+def _mask(land, dt):
+    return np.where(land, 100.0, -100.0).astype(dt)
+
+
+def _zeros(n, dt, ny=NY, nx=NX):
+    return [np.zeros((ny, nx), dt) for _ in range(n)]
+
+
+@pytest.fixture
+def table(hipctx):
+    hipctx.set_table_contrast(True)
+    yield hipctx
+    hipctx.set_table_contrast(False)
+    hipctx.set_search_radius_hint(16)
+
+
+@pytest.fixture(scope="module")
+def block_inputs():
+    st = synth.static_fields(NX, NY, np.float64)
+    p = synth.pressure_3d(st, NZ, np.float64)
+    steps = {tn: (synth.theta_step(st, tn, np.float64),) + synth.wind_step(st, NZ, tn, np.float64) for tn in (1, 2)}
+    return st, p, steps, _mask(_block_land(NX, NY, W), np.float64)
+
+
+@pytest.fixture(scope="module")
+def block_ref(oracles, block_inputs):
+    """the fp64 oracle on the block grid, tn = 1, 2: the state after each step and the largest radius; never modified"""
+    st, p, steps, mask = block_inputs
+    so = _zeros(4, np.float64)
+    out = {}
+    for tn in (1, 2):
+        th, u, v = steps[tn]
+        oracles[8].seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *so, halo=0, bnd=1)
+        out[tn] = ([a.copy() for a in so], oracles[8].last_nn_max)
+        for a in out[tn][0]:
+            a.setflags(write=False)
+    assert out[1][1] == 40 and not np.isnan(out[1][0][2]).any() and np.count_nonzero(out[1][0][3]) > 0
+    return out
+
+
+def _run_block(ctx, block_inputs, mask=None):
+    """tn = 1, 2 on the block grid from zero state -> per step (state, counters, launches)"""
+    st, p, steps, mask0 = block_inputs
+    mask = mask0 if mask is None else mask
+    sh = _zeros(4, np.float64)
+    out = {}
+    for tn in (1, 2):
+        th, u, v = steps[tn]
+        ctx.seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *sh, halo=0, bnd=hip.SB_BND_GLOBAL)
+        out[tn] = ([a.copy() for a in sh], ctx.last_counters(), ctx.last_step_report()["kernel_launches"])
+    return out
+
+
+def test_global_fp64_block_grid(table, block_inputs, block_ref):
+    """Seam split, pole clamp with multiplicity, radii up to 40 from the tables alone, the state update behind them."""
+    got = _run_block(table, block_inputs)
+    for tn in (1, 2):
+        state, c, launches = got[tn]
+        ref, nn_max = block_ref[tn]
+        for a, b, nm in zip(state, ref, NAMES):
+            _close64(a, b, f"tn={tn} {nm}")
+        assert c["global_path_cells"] == 0 and c["one_class_cells"] == 0, c
+        assert c["max_radius"] == nn_max == 40, (c, nn_max)
+        assert c["band_cells"] == NX * NY
+        assert launches == TABLE_LAUNCHES, launches
+
+
+def test_switch_off_and_on_again_on_one_context(table, block_inputs, block_ref):
+    """Today's path on the same context and inputs (radius hint 16: the strip kernel marks the cells beyond it and stores
+    its plan), then the tables again: the stored plan and the table workspace live side by side."""
+    on = _run_block(table, block_inputs)
+    table.set_table_contrast(False)
+    off = _run_block(table, block_inputs)
+    table.set_table_contrast(True)
+    again = _run_block(table, block_inputs)
+    for tn in (1, 2):
+        assert off[tn][1]["global_path_cells"] > 0 and off[tn][2] < TABLE_LAUNCHES, off[tn][1:]
+        assert off[tn][1]["max_radius"] == 40
+        for a, b, r, nm in zip(off[tn][0], on[tn][0], block_ref[tn][0], NAMES):
+            _close64(a, b, f"off against on, tn={tn} {nm}")
+            _close64(a, r, f"off against the oracle, tn={tn} {nm}")
+        for a, b, nm in zip(again[tn][0], on[tn][0], NAMES):
+            assert np.array_equal(a, b), (tn, nm)          # exact sums: the same bits
+        assert again[tn][1] == on[tn][1] and again[tn][2] == TABLE_LAUNCHES
+
+
+def test_coast_that_moves(table, oracles, block_inputs, block_ref):
+    """The tables are rebuilt every call: the block 7 columns east and 3 rows north in the second call."""
+    st, p, steps, mask1 = block_inputs
+    mask2 = _mask(_block_land(NX, NY, W, dx=7, dy=3), np.float64)
+    assert not np.array_equal(mask1, mask2) and mask2[0].max() < 0 and mask2[3].max() > 0
+    sh = _zeros(4, np.float64)
+    so = [a.copy() for a in block_ref[1][0]]                 # the oracle's state after tn = 1 on the first mask
+    for tn, mask in ((1, mask1), (2, mask2)):
+        th, u, v = steps[tn]
+        table.seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *sh, halo=0, bnd=hip.SB_BND_GLOBAL)
+    th, u, v = steps[2]
+    oracles[8].seabreeze_diag(DT_S, 2, p, u, v, th, mask2, st.z, st.sigma, *so, halo=0, bnd=1)
+    for a, b, nm in zip(sh, so, NAMES):
+        _close64(a, b, f"moved coast {nm}")
+    c = table.last_counters()
+    assert c["global_path_cells"] == 0 and c["max_radius"] == oracles[8].last_nn_max, (c, oracles[8].last_nn_max)
+
+
+def test_fp32_block_grid_against_the_fp64_oracle(table, oracles):
+    dt = np.float32
+    st = synth.static_fields(NX, NY, dt)
+    p = synth.pressure_3d(st, NZ, dt)
+    mask = _mask(_block_land(NX, NY, W), dt)
+    sh, so = _zeros(4, dt), _zeros(4, np.float64)
+    band = np.ones((NY, NX), bool)                           # no cell is masked
+    per = []
+    for tn in (1, 2):
+        th = synth.theta_step(st, tn, dt)
+        u, v = synth.wind_step(st, NZ, tn, dt)
+        gp, op = [a.copy() for a in sh], [a.copy() for a in so]
+        oracles[8].seabreeze_diag(DT_S, tn, f8(p), f8(u), f8(v), f8(th), f8(mask), f8(st.z), f8(st.sigma), *so, halo=0, bnd=1)
+        table.seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *sh, halo=0, bnd=hip.SB_BND_GLOBAL)
+        per.append(crit.check_step(tn, gp, sh, op, so, band, timestep=DT_S))
+    res = crit.merge(per)
+    assert res["ok"], res
+    c = table.last_counters()
+    assert c["global_path_cells"] == 0 and c["max_radius"] == oracles[8].last_nn_max == 40, c
+    assert table.last_step_report()["kernel_launches"] == TABLE_LAUNCHES
+
+
+HBIG = 48                   # ghost width of the frame the oracle runs on: no window of the block grid (radii up to 40) leaves it
+
+
+@pytest.fixture(scope="module")
+def framed():
+    """The block grid as the interior of a frame whose ghost cells continue the fields.  The oracle reads raw indices under
+    bnd = 2 and would leave a frame of 8 (or 4) ghost cells on this grid, so it runs on the same fields with HBIG ghost
+    cells; the library gets the inner part with the ghost width under test."""
+    st = synth.static_fields(NX + 2 * HBIG, NY + 2 * HBIG, np.float64)
+    core = (slice(HBIG, HBIG + NY), slice(HBIG, HBIG + NX))
+    p = synth.pressure_3d(st, NZ, np.float64)[:, core[0], core[1]].copy()
+    mask = _mask(_block_land(NX + 2 * HBIG, NY + 2 * HBIG, W, x0=-HBIG, y0=-HBIG), np.float64)
+    steps = {}
+    for tn in (1, 2):
+        u, v = (a[:, core[0], core[1]].copy() for a in synth.wind_step(st, NZ, tn, np.float64))
+        steps[tn] = (synth.theta_step(st, tn, np.float64), u, v)
+    return st, p, mask, steps
+
+
+def _cut(a, h):
+    return np.ascontiguousarray(a[HBIG - h:a.shape[0] - (HBIG - h), HBIG - h:a.shape[1] - (HBIG - h)])
+
+
+def _frame_radii(mask_h, h):
+    """per interior cell of a frame of h ghost cells: the smallest radius >= 1 whose square holds both classes and lies
+    inside the frame (0: none does), and how far a square round the cell may reach -- by a summed-area table of its own"""
+    land = np.pad(np.cumsum(np.cumsum((mask_h >= 0).astype(np.int64), axis=0), axis=1), ((1, 0), (1, 0)))
+    y, x = np.mgrid[0:NY, 0:NX]
+    reach = np.minimum(np.minimum(x, NX - 1 - x), np.minimum(y, NY - 1 - y)) + h
+    nn = np.zeros((NY, NX), np.int64)
+    for r in range(1, int(reach.max()) + 1):
+        todo = (nn == 0) & (reach >= r)
+        ys, xs = y[todo] + h, x[todo] + h
+        cnt = land[ys + r + 1, xs + r + 1] - land[ys - r, xs + r + 1] - land[ys + r + 1, xs - r] + land[ys - r, xs - r]
+        hit = (cnt > 0) & (cnt < (2 * r + 1) ** 2)
+        nn[y[todo][hit], x[todo][hit]] = r
+    return nn, reach
+
+
+def _check_framed(ctx, sh, so, nn, reach, what):
+    """ws, wd everywhere; thc and sb_con against the oracle where the cell's square lies inside the frame, NaN and no
+    trigger where none does (include/seabreeze_hip.h); the counters"""
+    found = nn > 0
+    for a, b, nm in zip(sh[:2], so[:2], NAMES[:2]):
+        _close64(a, b, f"{what} {nm}")
+    assert np.array_equal(np.isnan(sh[2]), ~found), f"{what}: NaN pattern of thc"
+    assert np.all(sh[3][~found] == 0.0)
+    for a, b, nm in zip(sh[2:], so[2:], NAMES[2:]):
+        _close64(np.where(found, a, 0.0), np.where(found, b, 0.0), f"{what} {nm}")
+    c = ctx.last_counters()
+    n_nan = int((~found).sum())
+    assert 0 < n_nan < NX * NY and c["one_class_cells"] == n_nan and c["global_path_cells"] == n_nan, (c, n_nan)
+    assert c["max_radius"] == max(int(nn.max()), int(reach[~found].max())), c     # (a search that fails ends at its bound)
+    assert ctx.last_step_report()["kernel_launches"] == TABLE_LAUNCHES
+
+
+@pytest.fixture(scope="module")
+def framed_ref(oracles, framed):
+    """the oracle on the wide frame, per level rule: the state after tn = 1, 2"""
+    st, p, mask, steps = framed
+    out = {}
+    for rule in (0, 1):
+        so = _zeros(4, np.float64)
+        for tn in (1, 2):
+            th, u, v = steps[tn]
+            oracles[8].seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *so, halo=HBIG, bnd=2, level_rule=rule)
+            out[rule, tn] = [a.copy() for a in so]
+        assert oracles[8].last_nn_max == 40 and not np.isnan(so[2]).any()
+    return out
+
+
+def test_halo_frame(table, framed, framed_ref):
+    """SB_BND_HALO, 8 ghost cells: no wrap, no clamp, windows stop at the frame -- a cell whose square would leave it finds
+    one class only: NaN, counted; every other cell has the oracle's value."""
+    h = 8
+    st, p, mask, steps = framed
+    nn, reach = _frame_radii(_cut(mask, h), h)
+    sh = _zeros(4, np.float64)
+    for tn in (1, 2):
+        th, u, v = steps[tn]
+        table.seabreeze_diag(DT_S, tn, p, u, v, _cut(th, h), _cut(mask, h), _cut(st.z, h), _cut(st.sigma, h), *sh, halo=h,
+                             bnd=hip.SB_BND_HALO)
+        _check_framed(table, sh, framed_ref[0, tn], nn, reach, f"halo tn={tn}")
+
+
+def test_um_entry_point(table, framed, framed_ref, oracles):
+    """sb_seabreeze_diag_um_f64: theta, z, sigma with 4 ghost cells, mask with 8, both flags; theta comes back as t0, ghost
+    cells included, as with the switch off."""
+    hs, hl = 4, 8
+    flags = hip.SB_UM_THETA_TO_T0 | hip.SB_UM_LEVEL_WALK
+    st, p, mask, steps = framed
+    nn, reach = _frame_radii(_cut(mask, hs), hs)
+    z_s, sg_s, mask_l = _cut(st.z, hs), _cut(st.sigma, hs), _cut(mask, hl)
+    sh, sx = _zeros(4, np.float64), _zeros(4, np.float64)
+    for tn in (1, 2):
+        th, u, v = steps[tn]
+        th_s = _cut(th, hs)
+        theta_on = th_s.copy()
+        assert table.seabreeze_diag_um(DT_S, tn, p, u, v, theta_on, z_s, sg_s, mask_l, *sh, halo_s=hs, halo_l=hl, flags=flags) == 0
+        _check_framed(table, sh, framed_ref[1, tn], nn, reach, f"UM tn={tn}")
+        table.set_table_contrast(False)
+        theta_off = th_s.copy()
+        assert table.seabreeze_diag_um(DT_S, tn, p, u, v, theta_off, z_s, sg_s, mask_l, *sx, halo_s=hs, halo_l=hl, flags=flags) == 0
+        table.set_table_contrast(True)
+        assert np.array_equal(theta_on, theta_off) and not np.array_equal(theta_on, th_s)
+        for a, b in zip(sh, sx):
+            assert np.array_equal(np.isnan(a), np.isnan(b))
+        sd, r = oracles[8].sigmoid_scalars(_cut(st.sigma, 0))
+        t0 = th_s - (-0.0060956 * z_s) * (1 / (1 + np.exp(-sd * (sg_s - r))))
+        assert relerr(theta_on, t0) < 1e-12
+
+
+def test_fallback_window_wider_than_the_circle(table, oracles):
+    """64 x 40, sea in the last column only: the cells of column 31 are 32 cells from it either way round, and a window of
+    65 columns is wider than the circle -- they take the global-memory search, and only they."""
+    nx, ny = 64, 40
+    st = synth.static_fields(nx, ny, np.float64)
+    p = synth.pressure_3d(st, NZ, np.float64)
+    mask = _mask(np.broadcast_to(np.arange(nx)[None, :] < 63, (ny, nx)), np.float64)
+    sh, so = _zeros(4, np.float64, ny, nx), _zeros(4, np.float64, ny, nx)
+    for tn in (1, 2):
+        th = synth.theta_step(st, tn, np.float64)
+        u, v = synth.wind_step(st, NZ, tn, np.float64)
+        oracles[8].seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *so, halo=0, bnd=1)
+        table.seabreeze_diag(DT_S, tn, p, u, v, th, mask, st.z, st.sigma, *sh, halo=0, bnd=hip.SB_BND_GLOBAL)
+        for a, b, nm in zip(sh, so, NAMES):
+            _close64(a, b, f"circle tn={tn} {nm}")
+        c = table.last_counters()
+        assert oracles[8].last_nn_max == 32
+        assert c["global_path_cells"] == ny and c["one_class_cells"] == 0 and c["max_radius"] == 32, c
+
+
+def test_fallback_one_class_grid(table):
+    """All land: every band cell is NaN and counted, with the switch on as with it off."""
+    nx, ny = 64, 40
+    st = synth.static_fields(nx, ny, np.float64)
+    p = synth.pressure_3d(st, NZ, np.float64)
+    mask = np.full((ny, nx), 100.0)
+    th = synth.theta_step(st, 1, np.float64)
+    u, v = synth.wind_step(st, NZ, 1, np.float64)
+    res = {}
+    for on in (True, False):
+        table.set_table_contrast(on)
+        sh = _zeros(4, np.float64, ny, nx)
+        table.seabreeze_diag(DT_S, 1, p, u, v, th, mask, st.z, st.sigma, *sh, halo=0, bnd=hip.SB_BND_GLOBAL)
+        res[on] = (sh, table.last_counters())
+        assert np.isnan(sh[2]).all()
+        assert res[on][1]["global_path_cells"] == res[on][1]["one_class_cells"] == nx * ny, res[on][1]
+    table.set_table_contrast(True)
+    for a, b in zip(res[True][0], res[False][0]):
+        assert np.array_equal(a, b, equal_nan=True)
+    assert res[True][1] == res[False][1]
+
+
+def test_ignored_by_the_f2py_flavour(table):
+    """A wrapper-flavour diag call does not know the switch: the same bits, the same launches."""
+    nx, ny, nz = 96, 72, 3
+    dt = np.float64
+    st = synth.static_fields(nx, ny, dt)
+    cd = _mask(np.broadcast_to((np.arange(nx)[None, :] // 12) % 2 == 0, (ny, nx)), dt)      # stripes: radii up to 6
+    p = synth.pressure_1d(nz, dt)
+    th = synth.theta_step(st, 1, dt)
+    u, v = synth.wind_step(st, nz, 1, dt)
+    res = {}
+    for on in (True, False):
+        table.set_table_contrast(on)
+        w = _zeros(3, dt, ny, nx)
+        out = table.diag(1, p, st.z, st.sigma, th, v, u, cd, *w)
+        res[on] = (w + [out], table.last_step_report()["kernel_launches"])
+    table.set_table_contrast(True)
+    for a, b in zip(res[True][0], res[False][0]):
+        assert np.array_equal(a, b, equal_nan=True)
+    assert res[True][1] == res[False][1] < TABLE_LAUNCHES
