@@ -361,7 +361,17 @@ int sb_get_edges_f32_dev(sb_ctx *ctx, int nlons, int nlats, const float *lsm, co
 /* kwin >= 0: fixed +-kwin cells (the generic/UM halo width, generic :422,425).      */
 /* lon, lat: HOST pointers in every variant (tiny vectors; the window size is        */
 /* derived from them on the host).                                                   */
+/* Reach: kwin, or the half-width derived for kwin < 0, may be 0 ..                  */
+/* SB_DIST_MAX_WINDOW cells (113 at 0.0135 degrees and maxdist = 180 km, the grids   */
+/* sb_set_table_contrast is for); a wider window is refused with SB_ERR_ARG.  Any    */
+/* nlons >= 1, also grids narrower than the window.                                  */
+/* Single precision on km-scale grids: the coordinates are rounded to 24 bits before */
+/* they are subtracted, as in the reference's own single-precision build.  At 0.0135 */
+/* degrees spacing near 70 N that field differs from the double-precision one by     */
+/* 5.6e-4 relative.  It is reproduced as it is, not more accurately: use the _f64    */
+/* entry points for such grids.                                                      */
 /* -------------------------------------------------------------------------------- */
+#define SB_DIST_MAX_WINDOW 255
 int sb_get_dist_f64(sb_ctx *ctx, int nlons, int nlats, const double *coast, const double *mask,
                     const double *lon, const double *lat, double maxdist, int kwin, double *cdist);
 int sb_get_dist_f32(sb_ctx *ctx, int nlons, int nlats, const float *coast, const float *mask,

@@ -162,8 +162,12 @@ struct sb_ctx {
     // get_dist's coordinate tables (device: `vecs`): the coordinates they were made from, the host copy the upload reads,
     // and what the host found out about the coordinates' order
     std::vector<unsigned char> dist_key, dist_hv;
-    bool dist_ordered = false;
-    double dist_maxstep = 0.0;
+    // what the host derives from them, each true only with every latitude within +-90 degrees (cos >= 0): longitudes in
+    // order round the whole circle, and the largest step | the steps j -> j+1, j < nx-1 (without the closing one) all
+    // one way, and the largest of them | latitudes stepping one way.  k_dist_bits' `nearest` needs the first and the
+    // third; k_dist_wide takes its cuts one by one.
+    bool dist_circle = false, dist_inner = false, dist_latmono = false;
+    double dist_maxstep = 0.0, dist_maxstep_inner = 0.0;
     hipStream_t dist_upload_stream = nullptr;   // the stream the tables were uploaded on, until another stream has waited for it
     // staging buffers for the host-pointer entry points
     std::vector<DevBuf> stage;
@@ -982,8 +986,9 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
         int rc = dist_window<T>(nx, ny, lon, lat, maxdist, &k);
         if (rc) { c->err = g_err; return rc; }
     }
-    if ((size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k) > 64 * 1024)
-        return fail(c, SB_ERR_ARG, "get_dist: window too large for the LDS tile");
+    if (k > SB_DIST_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "get_dist: window half-width " + std::to_string(k) + " exceeds SB_DIST_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
     // The coordinate tables on the device -- phi = d2r*lat, the folded longitudes in radians (ref: sobel.f90:130,165-174),
     // sin and cos of half of them (k_dist_bits, fp64) -- and what the host derives from the coordinates (may the kernel keep
     // only the nearest hit per side of a row?) stand for as long as the coordinates do: they are keyed on the CONTENT of
@@ -1024,12 +1029,28 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
             turn += d;
             maxstep = d > maxstep ? d : maxstep;
         }
-        bool latmono = true;                      // sp^2 grows with the row distance: latitudes step one way
+        bool latin = true;                        // cos(phi) >= 0: the haversine term grows with sin^2 of either difference
+        for (int i = 0; i < ny && latin; ++i) latin = std::fabs((double)lat[i]) <= 90.0;
+        bool latmono = latin;                     // sp^2 grows with the row distance: latitudes step one way
         for (int i = 0; i + 2 < ny && latmono; ++i)
             latmono = ((double)lat[i + 1] - (double)lat[i]) * ((double)lat[i + 2] - (double)lat[i + 1]) > 0.0;
-        for (int i = 0; i < ny && latmono; ++i) latmono = std::fabs((double)lat[i]) <= 90.0;
-        c->dist_ordered = mono && latmono && turn < 360.0 + 1.0e-3;
+        c->dist_circle = latin && mono && turn < 360.0 + 1.0e-3;
+        c->dist_latmono = latmono;
         c->dist_maxstep = maxstep;
+        // k_dist_wide decides the column cut per target: a window that stays inside the frame never meets the closing
+        // step, so for it the steps inside the frame decide (eastwards or westwards, folded to +-180 degrees)
+        bool east = nx > 1, west = nx > 1;
+        double maxin = 0.0;
+        for (int j = 0; j + 1 < nx && (east || west); ++j) {
+            double d = std::fmod((double)lon[j + 1] - (double)lon[j], 360.0);
+            if (d > 180.0) d -= 360.0;
+            if (d <= -180.0) d += 360.0;
+            east = east && d > 1.0e-6;
+            west = west && d < -1.0e-6;
+            maxin = std::fabs(d) > maxin ? std::fabs(d) : maxin;
+        }
+        c->dist_inner = latin && (east || west);
+        c->dist_maxstep_inner = maxin;
         c->dist_key.resize(kb + sizeof(dims));
         std::memcpy(c->dist_key.data(), dims, sizeof(dims));
         std::memcpy(c->dist_key.data() + sizeof(dims), lon, (size_t)nx * sizeof(T));
@@ -1042,9 +1063,16 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
     }
     const T *dphi = (const T *)c->vecs.p, *dlam = dphi + ny;
     if ((rc = ensure(c, c->coastbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
-    const int nearest = (c->dist_ordered && (double)k * c->dist_maxstep < 170.0) ? 1 : 0;
+    // bit 0: k_dist_bits' `nearest` (k <= 31); bits 1-3: k_dist_wide's cuts (sb_coast_kernels.hip), each with its own condition
+    const bool circle = c->dist_circle && (double)k * c->dist_maxstep < 170.0;
+    int cuts = (circle && c->dist_latmono) ? 1 : 0;
+    if (circle) cuts |= 2;
+#ifndef SB_DIST_NO_INNER_CUT                                     // (A/B builds: what the per-target rule buys, tools/dist_wide_cost.py)
+    if (c->dist_inner && (double)k * c->dist_maxstep_inner < 170.0) cuts |= 4;
+#endif
+    if (c->dist_latmono) cuts |= 8;
     HIPCHK(c, sb_launch_dist<T>(coast, mask, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist, nx, ny, k, maxdist,
-                                (uint64_t *)c->coastbits.p, nearest, st));
+                                (uint64_t *)c->coastbits.p, cuts, st));
     // a distance field made here bounds the search radius of the following diag calls
     c->radius_hint = k + 1;
     return SB_OK;

@@ -7,6 +7,11 @@
 //            racy scatter over coast cells (ref: sobel.f90:152-191);
 //            the gather keeps its results, including the sweep-order reset of :188,
 //            by tracking the minimum over sources swept before and after the target.
+//            k_dist itself (byte probes in LDS) is left with k <= 31 on grids narrower than the
+//            window; every other call takes the bit-plane kernels: k_dist_bits[_small] for
+//            k <= 31, k_dist_wide for 32 <= k <= SB_DIST_MAX_WINDOW (71 and 115 times faster than
+//            k_dist at k = 40 and 100 on 2560 x 1920).
+#include "../../include/seabreeze_hip.h"
 #include "sb_device.hpp"
 #include "sb_launch.hpp"
 
@@ -538,6 +543,265 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
 }
 
+// ------------------------------------------------------------------------------------
+// k_dist_wide: k_dist_bits for windows of 32 .. SB_DIST_MAX_WINDOW cells each way (km-scale regional grids: 113 cells
+// at 0.0135 degrees).  A target's window of 2k+1 <= 511 columns no longer fits one word, and the 2k+1 source rows no
+// longer fit LDS at once, so
+//   * a source row's coast bits over the columns x0-k .. x0+255+k in reach of the workgroup are a bit string of up to
+//     WIDE_WORDS words (bit b is column (x0 - k + b) mod nx: the seam, and a grid narrower than the reach, are dealt with
+//     in the staging); the window of target t is bits t .. t+2k of it, its own column bit t+k;
+//   * the source rows are staged in passes, nearest to the target rows first: pass j holds the WIDE_A rows from
+//     WIDE_A*j + 1 above the workgroup's first target row, as many below its last, and (pass 0) the target rows:
+//     64 slots, one lane of a wave each, so a wave's row mask is one ballot per pass;
+//   * the nearest hit at or left of the own column, and right of it, is found by scanning words outwards from bit t+k.
+// Everything else is k_dist_bits': rows without a coast bit in reach of the wave are skipped by the wave, a workgroup
+// with nothing in reach leaves before any trigonometry, min(a) per sweep class and one distance per cell, dist_small,
+// the exact zero of the own column's difference of products.
+//
+// `cuts` (host, sb_capi.hip) says what may be left out; each is exact:
+//   WIDE_CUT_CIRCLE  nearest hit per side in every row (k_dist_bits' rule: longitudes step one way round the whole
+//                    circle and the window spans less than half of it);
+//   WIDE_CUT_INNER   the same for a target whose window xx-k .. xx+k lies inside 0 .. nx-1: the steps j -> j+1, j < nx-1
+//                    (not the closing one) go one way and k of the largest stay below 170 degrees, so inside such a window
+//                    the angular separation grows with the column distance and stays below 180 degrees, where
+//                    sin^2(dlam/2) grows with it (the fold of longitudes beyond 180 shifts dlam by 2 pi: sin^2 does not
+//                    see it).  A regional grid's closing step of 300-odd degrees forbids WIDE_CUT_CIRCLE for every target
+//                    although only the windows within k of the frame's edge cross it;
+//   WIDE_CUT_ROWS    a >= sp^2, which grows with the row distance when latitudes step one way: a sweep class stops at
+//                    the first row that cannot lower its minimum.
+// Windows that may not be cut visit every hit; so does the own row of a window across the seam (xs <= xx is decided
+// on wrapped indices there, ref: sobel.f90:188).  With 2k+1 >= nx the window is the nx columns from xx-k on: every
+// column once (the reference's loop meets some twice, which changes no minimum).
+// ------------------------------------------------------------------------------------
+#define WIDE_ROWS 2                                              // target rows per workgroup (256 x 2 threads)
+#define WIDE_A 31                                                // source rows above, and below, per pass
+#define WIDE_SLOTS (2 * WIDE_A + WIDE_ROWS)                      // rows resident in LDS: one per lane of a wave
+#define WIDE_SPAN (256 + 2 * SB_DIST_MAX_WINDOW)                 // columns a workgroup's 256 targets can reach
+#define WIDE_WORDS ((WIDE_SPAN + 63) / 64)
+#define WIDE_CUT_CIRCLE 2
+#define WIDE_CUT_INNER 4
+#define WIDE_CUT_ROWS 8
+static_assert(WIDE_SLOTS == 64 && WIDE_ROWS == 2, "k_dist_wide: a slot per lane, and the walk names both target rows");
+
+// 64 bits of a row of the plane from circular column p on (0 <= p < nx), round the seam as often as it takes
+__device__ __forceinline__ uint64_t circ_bits64(const uint64_t *__restrict__ rw, int p, int nx) {
+    uint64_t v = 0;
+    for (int f = 0; f < 64;) {
+        const int l = nx - p < 64 - f ? nx - p : 64 - f;
+        if (l == 64) {
+            const int w = p >> 6, o = p & 63;
+            v = rw[w] >> o;
+            if (o) v |= rw[w + 1] << (64 - o);
+            return v;
+        }
+        v |= row_bits(rw, p, l) << f;
+        f += l;
+        p = 0;
+    }
+    return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *__restrict__ bits, const T *__restrict__ mask,
+                                                   const T *__restrict__ phi, const T *__restrict__ lamf,
+                                                   const T *__restrict__ shl, const T *__restrict__ chl,
+                                                   T *__restrict__ cdist, int nx, int ny, int nw, int k,
+                                                   T maxdist, int cuts) {
+    __shared__ uint64_t s_bw[WIDE_SLOTS][WIDE_WORDS];
+    __shared__ T s_ta[WIDE_SPAN], s_tb[sizeof(T) == 8 ? WIDE_SPAN : 1];   // fp64: sin, cos of half the folded longitude; fp32: the folded longitude
+    __shared__ T s_sp2[WIDE_ROWS][WIDE_SLOTS], s_cosp[WIDE_SLOTS], s_cost[WIDE_ROWS];
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 256 + tx;
+    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * WIDE_ROWS;
+    const int xx = x0 + tx, yy = y0 + ty;
+    const bool active = xx < nx && yy < ny;                      // (every thread stays for the barriers)
+    const T big = T(12000.);
+    const int span = 256 + 2 * k, nws = (span + 63) >> 6;
+    int c0 = (x0 - k) % nx;                                      // first column in reach, circular
+    if (c0 < 0) c0 += nx;
+    const int t = tx, P = t + k;                                 // this target's window starts at bit t; its own column
+    const int hi = t + (2 * k + 1 < nx ? 2 * k + 1 : nx) - 1;    // ... and ends at bit hi
+    const bool inside = xx - k >= 0 && xx + k <= nx - 1;
+    const bool colcut = (cuts & WIDE_CUT_CIRCLE) || ((cuts & WIDE_CUT_INNER) && inside);
+    const bool rowcut = (cuts & WIDE_CUT_ROWS) != 0;
+    // slot s of pass j: the row of the plane it holds (may lie outside 0 .. ny-1), and its distance from the nearer
+    // target row
+    auto slot_row = [&](int s, int j) {
+        if (s < WIDE_A) return y0 - 1 - WIDE_A * j - s;
+        if (s < 2 * WIDE_A) return y0 + WIDE_ROWS + WIDE_A * j + (s - WIDE_A);
+        return j == 0 ? y0 + (s - 2 * WIDE_A) : -1;
+    };
+    auto slot_dist = [&](int s, int j) { return s < 2 * WIDE_A ? 1 + WIDE_A * j + (s < WIDE_A ? s : s - WIDE_A) : 0; };
+
+    const T none = T(4);                                         // a <= 1: "no source in this class"
+    T a_early = none, a_late = none;
+    T ta_t = T(0), tb_t = T(0), cost = T(0);
+    bool stop_up = !active, stop_dn = !active;                   // this target's sweep class cannot improve any more
+    bool tables = false;                                         // (workgroup-uniform)
+    const int npass = (k - 1) / WIDE_A + 1;
+    for (int j = 0; j < npass; ++j) {
+        // (the barrier between the walk of the pass before and this pass's staging; with the row cut most workgroups
+        // near a coast are done after pass 0)
+        if (j > 0 && __syncthreads_and(stop_up && stop_dn ? 1 : 0)) break;
+        int anyv = 0;
+        for (int i = tid; i < WIDE_SLOTS * WIDE_WORDS; i += 256 * WIDE_ROWS) {
+            const int s = i / WIDE_WORDS, w = i - s * WIDE_WORDS;
+            const int ys = slot_row(s, j);
+            uint64_t v = 0;
+            if (w < nws && ys >= 0 && ys < ny && slot_dist(s, j) <= k)       // clamped rows add no new sources
+                v = circ_bits64(bits + (size_t)ys * nw, (c0 + 64 * w) % nx, nx);
+            s_bw[s][w] = v;
+            anyv |= v != 0 ? 1 : 0;
+        }
+        if (!__syncthreads_or(anyv)) continue;                   // no coast cell in this pass's rows within reach of the workgroup
+        // the latitude factors of this pass's rows, per target row; with the first pass that holds a coast cell also
+        // the longitude tables over the reach -- a workgroup with nothing in reach never gets here
+        if (tid < WIDE_ROWS * WIDE_SLOTS) {
+            const int r = tid / WIDE_SLOTS, s = tid - r * WIDE_SLOTS;
+            int ys = slot_row(s, j);
+            ys = ys < 0 ? 0 : (ys >= ny ? ny - 1 : ys);
+            const T phit = phi[y0 + r < ny ? y0 + r : ny - 1], phis = phi[ys];
+            const T dphi = phis - phit;                          // phi1(i) - phi1(yy)
+            const T sp = sin(dphi / T(2));
+            s_sp2[r][s] = sp * sp;
+            if (r == 0) s_cosp[s] = cos(phis);
+        }
+        if (!tables) {
+            if (tid >= 256 && tid < 256 + WIDE_ROWS) s_cost[tid - 256] = cos(phi[y0 + tid - 256 < ny ? y0 + tid - 256 : ny - 1]);
+            for (int i = tid; i < span; i += 256 * WIDE_ROWS) {
+                const int xs = (c0 + i) % nx;
+                if constexpr (sizeof(T) == 8) { s_ta[i] = shl[xs]; s_tb[i] = chl[xs]; }
+                else s_ta[i] = lamf[xs];
+            }
+        }
+        __syncthreads();
+        if (!tables) {
+            tables = true;
+            ta_t = s_ta[P];
+            if constexpr (sizeof(T) == 8) tb_t = s_tb[P];
+            cost = s_cost[ty];
+        }
+        // Which of the 64 resident rows hold any coast cell within reach of this wave's 64 targets (bits 64 wv ..
+        // 64 wv + 63 + 2k of the strings; whole words: never an under-estimate)?  Lane i answers for slot i.
+        uint64_t rowmask;
+        {
+            const int lane = tx & 63, wv = tx >> 6;
+            uint64_t any = 0;
+            for (int w = wv; w <= (64 * wv + 63 + 2 * k) >> 6; ++w) any |= s_bw[lane][w];
+            rowmask = __ballot(any != 0);
+        }
+        if (!active || rowmask == 0) continue;                   // (the next barrier is the loop's first statement)
+
+        auto row = [&](int s, int ii) {                          // slot s holds row yy + ii
+            const uint64_t *w = s_bw[s];
+            const T sp2 = s_sp2[ty][s], cosp = s_cosp[s];
+            auto visit = [&](int q, bool early) {                // the hit at bit q of the string
+                T sl;
+                // fp64: sin((l1 - l2) / 2) = sin(l1/2) cos(l2/2) - cos(l1/2) sin(l2/2) from the per-column tables, as in
+                // k_dist_bits (two rounded products, no fma: for the own column, and for a copy of it a whole turn
+                // away, they are the same product and the difference is exactly zero).  The difference carries an
+                // absolute error of about 1e-16 whatever the spacing, so the distance one of 2R cos(phi) 1e-16 <= 1.3e-12
+                // km: within 1e-12 of max(|distance|, 1 km), the tests' rule, although not of a distance well below
+                // 1 km were there one (the smallest is 0.5).  Measured at 0.0135 degrees, 68-71 N: 1.3e-13.
+                if constexpr (sizeof(T) == 8) sl = s_ta[q] * tb_t - s_tb[q] * ta_t;
+                else {
+                    const T dlam = s_ta[q] - ta_t;               // l1 - l2
+                    sl = sin(dlam / T(2));
+                }
+                const T a = sp2 + (cosp * (cost * (sl * sl)));   // ref: sobel.f90:176
+                if (early) a_early = a < a_early ? a : a_early;
+                else a_late = a < a_late ? a : a_late;
+            };
+            if (colcut && (ii != 0 || inside)) {
+                // at or left of the own column: downwards from its word to the window's first
+                int wi = P >> 6;
+                uint64_t v = w[wi] & (~0ull >> (63 - (P & 63)));
+                while (!v && wi > (t >> 6)) v = w[--wi];
+                if (v) {
+                    const int q = 64 * wi + 63 - __builtin_clzll(v);
+                    if (q >= t) visit(q, ii <= 0);
+                }
+                // right of it: upwards to the window's last word
+                wi = (P + 1) >> 6;
+                v = w[wi] & (~0ull << ((P + 1) & 63));
+                while (!v && wi < (hi >> 6)) v = w[++wi];
+                if (v) {
+                    const int q = 64 * wi + __builtin_ctzll(v);
+                    if (q <= hi) visit(q, ii < 0);
+                }
+            } else {
+                for (int wi = t >> 6; wi <= hi >> 6; ++wi) {
+                    uint64_t v = w[wi];
+                    if (wi == t >> 6) v &= ~0ull << (t & 63);
+                    if (wi == hi >> 6) v &= ~0ull >> (63 - (hi & 63));
+                    while (v) {
+                        const int q = 64 * wi + __builtin_ctzll(v);
+                        v &= v - 1;
+                        bool early = ii < 0;
+                        if (ii == 0) early = (c0 + q) % nx <= xx;            // xs <= xx on wrapped indices
+                        visit(q, early);
+                    }
+                }
+            }
+        };
+        // Rows above the target are swept before it, rows below after it; within a class nearest first, over the passes
+        // too, so the row cut may end a class for good.  Only rows whose bit is set in the wave's row mask are visited
+        // (scalar bit scans: the mask is wave-uniform).
+        if (j == 0) {
+            if ((rowmask >> (2 * WIDE_A + ty)) & 1) row(2 * WIDE_A + ty, 0);
+            if (ty == 1 && ((rowmask >> (2 * WIDE_A)) & 1)) {                 // the other target row: one above ...
+                if (rowcut && !(s_sp2[ty][2 * WIDE_A] < a_early)) stop_up = true;
+                else row(2 * WIDE_A, -1);
+            }
+            if (ty == 0 && ((rowmask >> (2 * WIDE_A + 1)) & 1)) {             // ... or one below
+                if (rowcut && !(s_sp2[ty][2 * WIDE_A + 1] < a_late)) stop_dn = true;
+                else row(2 * WIDE_A + 1, 1);
+            }
+        }
+        if (!stop_up)
+            for (uint32_t m = (uint32_t)rowmask & ((1u << WIDE_A) - 1u); m; m &= m - 1) {
+                const int s = __builtin_ctz(m), d = ty + 1 + WIDE_A * j + s;
+                if (d > k) break;                                // wave-uniform
+                if (rowcut && !(s_sp2[ty][s] < a_early)) { stop_up = true; break; }
+                row(s, -d);
+            }
+        if (!stop_dn)
+            for (uint32_t m = (uint32_t)(rowmask >> WIDE_A) & ((1u << WIDE_A) - 1u); m; m &= m - 1) {
+                const int s = WIDE_A + __builtin_ctz(m), d = (WIDE_ROWS - 1 - ty) + 1 + WIDE_A * j + (s - WIDE_A);
+                if (d > k) break;
+                if (rowcut && !(s_sp2[ty][s] < a_late)) { stop_dn = true; break; }
+                row(s, d);
+            }
+    }
+    // One distance per cell, as in k_dist_bits: at the smaller a, unless that is the early class's and the sweep-time
+    // reset (ref: sobel.f90:188) throws it away; the series for a < 2^-10 (see there).
+    const T R = T(6370.9989);                                   // ref: sobel.f90:115
+    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref :177
+    auto dist_small = [&](T a) {
+        const double ad = (double)a;
+        double pl = __builtin_fma(ad, 945.0 / 42240.0, 105.0 / 3456.0);
+        pl = __builtin_fma(pl, ad, 15.0 / 336.0);
+        pl = __builtin_fma(pl, ad, 3.0 / 40.0);
+        pl = __builtin_fma(pl, ad, 1.0 / 6.0);
+        pl = __builtin_fma(pl, ad, 1.0);
+        return (R * T(2)) * (T)(sqrt(ad) * pl) + T(0.5);
+    };
+    const bool late_wins = a_late < a_early;
+    const T a_sel = late_wins ? a_late : a_early;
+    T m = big;
+    if (sizeof(T) == 8 && __ballot(a_sel < none && a_sel >= T(0x1p-10)) == 0) {      // wave-uniform
+        if (a_sel < none) m = dist_small(a_sel);
+    } else if (a_sel < none) m = dist_of(a_sel);
+    const bool again = !late_wins && m > T(2) * maxdist;         // ref: sobel.f90:188 at sweep time
+    if (__ballot(again) != 0) {                                  // wave-uniform
+        const T m2 = a_late < none ? dist_of(a_late) : big;
+        if (again) m = m2;
+    }
+    if (!active) return;
+    const size_t o = (size_t)yy * nx + xx;
+    if (m >= big) cdist[o] = big;
+    else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
+}
+
 template <typename T>
 hipError_t sb_launch_edges(const T *lsm, const T *ci, T *coast, int nx, int ny, int rule, int bnd, hipStream_t st) {
     Geo g;
@@ -548,7 +812,16 @@ hipError_t sb_launch_edges(const T *lsm, const T *ci, T *coast, int nx, int ny, 
 
 template <typename T>
 hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
-                          int nx, int ny, int k, T maxdist, uint64_t *bits, int nearest, hipStream_t st) {
+                          int nx, int ny, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st) {
+    const int nearest = cuts & 1;
+    if (bits && k >= 32) {                                       // any nx >= 1; the C ABI holds k <= SB_DIST_MAX_WINDOW
+        if (k > SB_DIST_MAX_WINDOW) return hipErrorInvalidValue;
+        const int nw = (nx + 63) / 64;
+        hipLaunchKernelGGL(k_coastbits<T>, dim3((nx + 255) / 256, (ny + COASTBITS_ROWS - 1) / COASTBITS_ROWS), dim3(256), 0, st, coast, bits, nx, ny, nw);
+        hipLaunchKernelGGL(k_dist_wide<T>, dim3((nx + 255) / 256, (ny + WIDE_ROWS - 1) / WIDE_ROWS), dim3(256, WIDE_ROWS), 0, st, bits, mask,
+                           phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, cuts);
+        return hipGetLastError();
+    }
     if (bits && k <= 31 && 2 * k + 1 <= nx) {
         const int nw = (nx + 63) / 64;
         hipLaunchKernelGGL(k_coastbits<T>, dim3((nx + 255) / 256, (ny + COASTBITS_ROWS - 1) / COASTBITS_ROWS), dim3(256), 0, st, coast, bits, nx, ny, nw);
@@ -563,7 +836,7 @@ hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *
                                nx, ny, nw, k, maxdist, nearest);
         return hipGetLastError();
     }
-    const size_t lds = (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k);
+    const size_t lds = (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k);   // (k <= 31 with 2k + 1 > nx, or no workspace)
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dist<T>, dim3((nx + 63) / 64, (ny + SB_DIST_TY - 1) / SB_DIST_TY), dim3(256), lds, st, coast, mask,
                        phi, lamf, cdist, nx, ny, k, maxdist);

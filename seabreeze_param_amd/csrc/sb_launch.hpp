@@ -123,7 +123,8 @@ hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *
                           const T *shl, const T *chl,         // sin, cos of half the folded longitudes (k_dist_bits, fp64)
                           T *cdist, int nx, int ny,
                           int k, T maxdist, uint64_t *bits,   // bits: ny*ceil(nx/64) words of workspace, or nullptr
-                          int nearest,                        // 1: nearest hit per side of a source row only (see k_dist_bits)
+                          int cuts,                           // bit 0: nearest hit per side of a source row only (see k_dist_bits);
+                                                              // bits 1-3: k_dist_wide's WIDE_CUT_CIRCLE, _INNER, _ROWS (k >= 32)
                           hipStream_t st);
 
 // the UM vn10.7 copy's coast setup on the tdims_l layout (sb_um_coast_kernels.hip): lf, ci, coast are

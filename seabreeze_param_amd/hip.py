@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("SEABREEZE_HIP_LIB", os.path.join(_HERE, "libseabreeze
 
 SB_BND_WRAPPER, SB_BND_GLOBAL, SB_BND_HALO = 0, 1, 2
 SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK = 1, 2
+SB_DIST_MAX_WINDOW = 255            # include/seabreeze_hip.h: the widest get_dist window (kwin, or the derived half-width)
 
 _SFX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 _CT = {np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double}
@@ -263,6 +264,8 @@ class Context:
         return coast
 
     def get_dist(self, coast, mask, lon, lat, maxdist=180.0, kwin=-1):
+        """Signed coast distance (km); kwin < 0 derives the window from the grid spacing (dist_window).  The window may
+        reach SB_DIST_MAX_WINDOW cells each way; on km-scale grids use float64 (see include/seabreeze_hip.h)."""
         coast = np.ascontiguousarray(coast)
         dt = np.dtype(coast.dtype)
         mask = _host(mask, dt); lon = _host(lon, dt); lat = _host(lat, dt)
