@@ -41,7 +41,7 @@ module sea_breeze_diag_mod
   public :: seabreeze_diag, seabreeze_diag_status, get_edges, get_dist, sigmoid, sb_shutdown
   public :: band_seabreeze_diag, seabreeze_diag_dev, band_seabreeze_diag_dev
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
-  public :: get_edges_um, get_dist_um
+  public :: get_edges_um, get_dist_um, get_dist_um_win
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
 #ifdef SB_REAL8
@@ -56,6 +56,7 @@ module sea_breeze_diag_mod
 #define SB_DIAG_UM        "sb_seabreeze_diag_um_f64"
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f64"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f64"
+#define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f64"
 #else
   integer, parameter :: rk = c_float
 #define SB_SEABREEZE_DIAG "sb_seabreeze_diag_f32"
@@ -68,6 +69,7 @@ module sea_breeze_diag_mod
 #define SB_DIAG_UM        "sb_seabreeze_diag_um_f32"
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f32"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f32"
+#define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f32"
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
@@ -155,6 +157,15 @@ module sea_breeze_diag_mod
       import :: c_ptr, c_int, rk
       type(c_ptr), value :: ctx
       integer(c_int), value :: nx, ny, hi, hj
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
+      real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_get_dist_um_win(ctx, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, maxdist, cdist) &
+        bind(C, name=SB_GET_DIST_UM_WIN)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj, wi, wj
       real(rk), value :: maxdist
       real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
       real(rk), intent(inout) :: cdist(*)
@@ -443,6 +454,36 @@ contains
     if (rc /= 0) call fail('get_dist_um', rc)
     deallocate(c2)
   end subroutine get_dist_um
+
+  !---------------------------------------------------------------------------
+  ! get_dist_um with the window stated apart from the layout: +-win_i columns x +-win_j rows, each 0 .. 255
+  ! (SB_DIST_UM_MAX_WINDOW; 113 cells at 0.0135 degrees and 180 km), wider or narrower than the ghost width of coast,
+  ! which is read off the shapes and only says where the interior lies.  Everything else is get_dist_um's.
+  !---------------------------------------------------------------------------
+  subroutine get_dist_um_win(landfrac, coast, true_latitude, true_longitude, win_i, win_j, maxdist)
+    real, intent(in), contiguous :: landfrac(:,:), true_latitude(:,:), true_longitude(:,:)
+    real, intent(inout), contiguous :: coast(:,:)
+    integer, intent(in) :: win_i, win_j
+    real, intent(in), optional :: maxdist
+    real, allocatable :: c2(:,:)
+    real :: md
+    integer(c_int) :: nx, ny, hi, hj, rc
+    nx = size(landfrac, 1); ny = size(landfrac, 2)
+    hi = (size(coast, 1) - nx) / 2; hj = (size(coast, 2) - ny) / 2
+    if (any(shape(true_latitude) /= [nx, ny]) .or. any(shape(true_longitude) /= [nx, ny]) .or. hi < 0 .or. hj < 0 &
+        .or. any(shape(coast) /= [nx + 2*hi, ny + 2*hj])) &
+      call fail('get_dist_um_win: need landfrac, true_latitude, true_longitude (nx, ny), coast (nx+2*halo_i, ny+2*halo_j)', &
+                1_c_int)
+    md = 180.
+    if (present(maxdist)) md = maxdist
+    allocate(c2(size(coast, 1), size(coast, 2)))
+    c2 = coast                                   ! (the coast mask the distance field replaces)
+    call ensure_ctx()
+    rc = c_get_dist_um_win(ctx, nx, ny, hi, hj, int(win_i, c_int), int(win_j, c_int), c2, landfrac, true_latitude, &
+                           true_longitude, real(md, rk), coast)
+    if (rc /= 0) call fail('get_dist_um_win', rc)
+    deallocate(c2)
+  end subroutine get_dist_um_win
 
   !---------------------------------------------------------------------------
   ! ref: generic/sea_breeze_diag.f90:457-481

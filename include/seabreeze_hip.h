@@ -450,6 +450,44 @@ int sb_get_dist_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
                        float maxdist, float *cdist, void *stream);
 
 /* -------------------------------------------------------------------------------- */
+/* get_dist -- UM vn10.7 layout, the window stated apart from the ghost width         */
+/* The field of sb_get_dist_um_* for a window of +-win_i columns x +-win_j rows,      */
+/* 0 <= win_i, win_j <= SB_DIST_UM_MAX_WINDOW (113 cells at 0.0135 degrees and        */
+/* maxdist = 180 km: the signed distance sb_set_table_contrast consumes on km-scale   */
+/* rotated grids); a negative or wider window is refused with SB_ERR_ARG.  halo_i,    */
+/* halo_j >= 0 describe the layout only: coast and cdist are                          */
+/* (nx+2*halo_i, ny+2*halo_j) with the interior at (halo_i, halo_j), and the window   */
+/* may be wider or narrower than the ghost width.  Everything else is                 */
+/* sb_get_dist_um_*'s rule: interior sources and targets only (no wrap, no clamp),    */
+/* the UM's constants and both longitude corrections, the sweep-order reset on the    */
+/* minimum over sources swept at or before the target, 12000 where the window holds   */
+/* no coast, only the interior of cdist written, cdist == coast allowed; the _dev     */
+/* forms enqueue without synchronising and derive nothing on the host.                */
+/* With win_i == halo_i <= 31 and win_j == halo_j <= 31 the call is                   */
+/* sb_get_dist_um_*'s, bit for bit.  Any other window goes to a kernel that, in       */
+/* double precision, takes sin((phi_s - phi_t)/2) on the difference as the UM writes  */
+/* it: at km-scale spacing the fields of the two kernels differ by up to 1e-12        */
+/* relative, the wide one being the closer to the UM's own arithmetic.                */
+/* -------------------------------------------------------------------------------- */
+#define SB_DIST_UM_MAX_WINDOW 255
+int sb_get_dist_um_win_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                       const double *coast, const double *landfrac,
+                       const double *true_lat, const double *true_lon,
+                       double maxdist, double *cdist);
+int sb_get_dist_um_win_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                       const float *coast, const float *landfrac,
+                       const float *true_lat, const float *true_lon,
+                       float maxdist, float *cdist);
+int sb_get_dist_um_win_f64_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                       const double *coast, const double *landfrac,
+                       const double *true_lat, const double *true_lon,
+                       double maxdist, double *cdist, void *stream);
+int sb_get_dist_um_win_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                       const float *coast, const float *landfrac,
+                       const float *true_lat, const float *true_lon,
+                       float maxdist, float *cdist, void *stream);
+
+/* -------------------------------------------------------------------------------- */
 /* swap_bounds -- ghost-cell fill of one latitude band of a multi-GPU run            */
 /* replaces: subroutine swap_bounds(field, halo_size)                                */
 /*           ref: generic/halo_exchange_mod.f90:12-17 (an empty stub; the UM copy    */

@@ -1159,6 +1159,47 @@ int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, 
     return s.finish();
 }
 
+// sb_get_dist_um_win_*: the window stated apart from the layout (halo_i, halo_j >= 0 say where the interior lies)
+template <typename T>
+int check_dist_um_win(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast, const T *lf, const T *tlat,
+                      const T *tlon, T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || hi < 0 || hj < 0 || !coast || !lf || !tlat || !tlon || !cdist)
+        return fail(c, SB_ERR_ARG, "bad get_dist_um_win arguments");
+    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "get_dist_um_win: the window +-" + std::to_string(wi) + " x +-" + std::to_string(wj) +
+                                       " needs 0 <= win_i, win_j <= SB_DIST_UM_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_UM_MAX_WINDOW) + " cells");
+    return SB_OK;
+}
+
+template <typename T>
+int get_dist_um_win_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast, const T *lf,
+                        const T *tlat, const T *tlon, T maxdist, T *cdist, void *stream) {
+    int rc = check_dist_um_win<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    if ((rc = ensure(c, c->umbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, sb_launch_dist_um_win<T>(coast, lf, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, maxdist, (uint64_t *)c->umbits.p, st));
+    return SB_OK;
+}
+
+template <typename T>
+int get_dist_um_win_host(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast, const T *lf,
+                         const T *tlat, const T *tlon, T maxdist, T *cdist) {
+    int rc = check_dist_um_win<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    const size_t n = (size_t)nx * ny, nl = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    Stager s(c);
+    // (as get_dist_um_host: cdist goes in as well, its ghost cells stay)
+    T *dco = s.in(coast, nl), *dl = s.in(lf, n), *dla = s.in(tlat, n), *dlo = s.in(tlon, n), *dcd = s.in((const T *)cdist, nl);
+    if (s.rc) return s.rc;
+    rc = get_dist_um_win_dev<T>(c, nx, ny, hi, hj, wi, wj, dco, dl, dla, dlo, maxdist, dcd, nullptr);
+    if (rc) return rc;
+    s.back(cdist, dcd, nl);
+    return s.finish();
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1430,6 +1471,15 @@ int sb_last_counters(sb_ctx *c, long long counters[4]) {
     int sb_get_dist_um_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf,          \
                                    const T *tlat, const T *tlon, T maxdist, T *cdist, void *stream) {               \
         return get_dist_um_dev<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, maxdist, cdist, stream);                \
+    }                                                                                                              \
+    int sb_get_dist_um_win_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast,         \
+                                 const T *lf, const T *tlat, const T *tlon, T maxdist, T *cdist) {                  \
+        return get_dist_um_win_host<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, maxdist, cdist);           \
+    }                                                                                                              \
+    int sb_get_dist_um_win_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast,   \
+                                       const T *lf, const T *tlat, const T *tlon, T maxdist, T *cdist,              \
+                                       void *stream) {                                                              \
+        return get_dist_um_win_dev<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, maxdist, cdist, stream);    \
     }                                                                                                              \
     int sb_dist_window_##SFX(int nx, int ny, const T *lon, const T *lat, T maxdist, int *k) {                       \
         return dist_window<T>(nx, ny, lon, lat, maxdist, k);                                                        \

@@ -136,6 +136,11 @@ hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny
 template <typename T>
 hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                              int hi, int hj, T maxdist, uint64_t *bits, hipStream_t st);
+// the same with the window +-wi x +-wj (0 .. SB_DIST_UM_MAX_WINDOW) apart from the layout's ghost width hi, hj >= 0:
+// k_dist_um where wi == hi <= 31 and wj == hj <= 31, k_dist_um_wide otherwise
+template <typename T>
+hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
+                                 int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st);
 
 // local part of swap_bounds: E-W periodic ghost columns, pole-side ghost rows replicate the edge row
 template <typename T>

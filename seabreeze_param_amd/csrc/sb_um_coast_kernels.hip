@@ -6,12 +6,14 @@
 //   k_coastbits_um coast > 0 of the interior, one 64-bit word per 64 columns (a wave ballot)
 //   k_dist_um      signed haversine distance to the nearest interior coast cell within +-halo_i columns x +-halo_j
 //                  rows, from per-cell coordinates     ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)
+//   k_dist_um_wide the same rule for a window of up to +-255 cells stated apart from the ghost width (sb_get_dist_um_win_*)
 //
 // The UM's get_dist is a scatter from interior coast cells into a window that reaches into the halo; swap_bounds then
 // throws the halo writes away (:584-598).  So sources and targets are interior cells only -- no wrap, no clamp -- and
 // the gather below keeps the scatter's result, the sweep-order reset |cdist| > 2*maxdist -> 12000 (:578) included, by
 // keeping the minimum over sources swept at or before the target (rows outer, columns inner) apart from the minimum
 // over sources swept after it, as k_dist does (sb_coast_kernels.hip).
+#include "../../include/seabreeze_hip.h"
 #include "sb_launch.hpp"
 
 template <typename T>
@@ -226,6 +228,201 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
     else cdist[o] = (lf > T(0)) ? m : -m;                          // ref: UM :568-574
 }
 
+// ------------------------------------------------------------------------------------
+// k_dist_um_wide: the gather for a window of +-wi columns x +-wj rows stated apart from the layout's ghost width
+// (hi, hj), 0 <= wi, wj <= SB_DIST_UM_MAX_WINDOW (113 cells at 0.0135 degrees and 180 km).  Rule and classes are
+// k_dist_um's; what changes is what is resident.  A workgroup is UMW_TY target rows of 64 columns (a wave per row); its
+// reach is up to 64 + 2*255 = 574 columns and UMW_TY + 2*255 rows, so
+//   * a reach row is a bit string of UMW_WORDS words from column x0 - wi on; the source rows are staged in passes that go
+//     outwards from the target rows (pass 0: the target rows and UMW_A rows either side, nearest first and sides
+//     alternating; pass j: the next UMW_A either side), so each sweep class meets its rows nearest first;
+//   * the per-source terms (phi, cos(phi), l1) are staged for coast cells only, in a compact list of UMW_CAP entries:
+//     the rows of a pass are taken in chunks of as many consecutive slots as the list holds (a row has at most
+//     574 <= UMW_CAP coast cells), s_off[slot][word] is the list index of the word's first coast cell, and a target
+//     finds the entry of bit b as s_off + popcount(bits below b).  LDS does not grow with the window;
+//   * a workgroup with no coast bit in its reach reads bit words only, writes 12000 and leaves; a pass without a bit
+//     costs its bit words, a row without one nothing more.
+// fp64 takes both sines on the difference as written, sin((phi_s - phi_t)/2) and sin((l1 - l2)/2): the half-angle
+// identity of k_dist_um carries an absolute error of ~2e-16 that a half-difference of 1e-4 rad (km-scale spacing) no
+// longer hides (up to 1.07e-12 relative, measured).  An argument of magnitude <= UMW_SIN_POLY_MAX = 0.5 rad goes
+// through the odd Taylor polynomial up to x^15 (truncation x^16/17! <= 4.3e-20 relative there); anything larger (the
+// longitude term of pairs either side of 180 degrees, or near a pole) through the library sine.  fp32 takes both
+// library sines as written, as k_dist_um does.
+// The per-pair cut: a = sp^2 + cos(phi_s) (cos(phi_t) sl^2) >= sp^2 when both cosines are >= 0 (every product of
+// non-negative terms is >= 0, and adding a non-negative term never rounds below sp^2), so a hit with sp^2 >= its
+// class's minimum cannot lower it and skips the longitude sine.  Both cosines are checked per pair.
+// -DSB_UM_WIN_NO_LAT_CUT builds the kernel without the cut (A/B: the field is the same to the last bit).
+// ------------------------------------------------------------------------------------
+#define UMW_TY 4                                                 // target rows per workgroup
+#define UMW_A 30                                                 // source rows above, and below, per pass
+#define UMW_SLOTS (2 * UMW_A + UMW_TY)                           // rows of bit strings resident in LDS
+#define UMW_SPAN (64 + 2 * SB_DIST_UM_MAX_WINDOW)                // columns a workgroup's 64 targets can reach
+#define UMW_WORDS ((UMW_SPAN + 63) / 64)
+#define UMW_CAP 1024                                             // entries of the compact source list
+#define UMW_SIN_POLY_MAX 0.5
+static_assert(UMW_CAP >= UMW_SPAN, "k_dist_um_wide: a chunk holds at least one row");
+static_assert(UMW_CAP <= 65535 && UMW_SLOTS <= 64 * UMW_TY, "k_dist_um_wide: 16-bit list offsets, a thread per slot");
+
+// sin(x) for |x| <= UMW_SIN_POLY_MAX: x + x^3 P(x^2), the Taylor terms up to x^15
+__device__ __forceinline__ double um_sin_poly(double x) {
+    const double z = x * x;
+    double p = -1.0 / 1307674368000.0;
+    p = __builtin_fma(p, z, 1.0 / 6227020800.0);
+    p = __builtin_fma(p, z, -1.0 / 39916800.0);
+    p = __builtin_fma(p, z, 1.0 / 362880.0);
+    p = __builtin_fma(p, z, -1.0 / 5040.0);
+    p = __builtin_fma(p, z, 1.0 / 120.0);
+    p = __builtin_fma(p, z, -1.0 / 6.0);
+    return __builtin_fma(x * z, p, x);
+}
+template <typename T>
+__device__ __forceinline__ T um_sin_as_written(T x) {
+    if constexpr (sizeof(T) == 8) return fabs(x) <= UMW_SIN_POLY_MAX ? um_sin_poly(x) : sin(x);
+    else return sin(x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                              const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                              T *__restrict__ cdist, int nx, int ny, int hi, int hj, int wi,
+                                                              int wj, int nw, T maxdist) {
+    __shared__ uint64_t s_bw[UMW_SLOTS][UMW_WORDS];
+    __shared__ unsigned short s_off[UMW_SLOTS][UMW_WORDS], s_cnt[UMW_SLOTS];
+    __shared__ T s_phi[UMW_CAP], s_cp[UMW_CAP], s_l1[UMW_CAP];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, tid = threadIdx.x;
+    const int x0 = blockIdx.x * 64, y0 = blockIdx.y * UMW_TY;
+    const int xx = x0 + tx, yy = y0 + ty;
+    const bool valid = xx < nx && yy < ny;                       // (every thread stays for the barriers)
+    const int NX = nx + 2 * hi;
+    const int W = 64 + 2 * wi, nws = (W + 63) >> 6;              // the reach: W columns from x0 - wi on, nws <= UMW_WORDS words
+    const uint64_t lastmask = (W & 63) ? (1ull << (W & 63)) - 1ull : ~0ull;
+    const int qlo = tx, qhi = tx + 2 * wi, qown = tx + wi;       // this target's window in the strings, its own column
+    const T big = T(12000.);
+    const T pi = T(3.1415926), r2d = T(180.0) / pi, d2r = pi / T(180.0);      // ref: UM :509-512
+    const T R = T(6370.9989);
+    // slot s of pass j: the distance of its row from the block of target rows (0: a target row) and the row itself
+    // (which may lie outside 0 .. ny-1)
+    auto slot_k = [&](int s, int j) { return j == 0 ? (s < UMW_TY ? 0 : 1 + ((s - UMW_TY) >> 1)) : 1 + UMW_A * j + (s >> 1); };
+    auto slot_row = [&](int s, int j) {
+        if (j == 0 && s < UMW_TY) return y0 + s;
+        const int k = slot_k(s, j), below = (j == 0 ? s - UMW_TY : s) & 1;
+        return below ? y0 + UMW_TY - 1 + k : y0 - k;
+    };
+    const T none = T(4);                                         // a <= 1: "no source in this class"
+    T a_early = none, a_late = none;
+    T phit = T(0), cost = T(0), l2 = T(0);
+    bool have = false;                                           // this target's own terms are loaded (workgroup-uniform)
+    const int npass = wj == 0 ? 1 : (wj + UMW_A - 1) / UMW_A;
+    for (int j = 0; j < npass; ++j) {
+        __syncthreads();                                         // (the pass before is read by every wave)
+        const int ns = j == 0 ? UMW_SLOTS : 2 * UMW_A;
+        int anyv = 0;
+        for (int i = tid; i < ns * UMW_WORDS; i += 64 * UMW_TY) {
+            const int s = i / UMW_WORDS, w = i - s * UMW_WORDS, ys = slot_row(s, j);
+            uint64_t v = 0;
+            if (w < nws && slot_k(s, j) <= wj && ys >= 0 && ys < ny) {
+                v = um_row_bits64(bits + (size_t)ys * nw, x0 - wi + 64 * w, nw);
+                if (w == nws - 1) v &= lastmask;
+            }
+            s_bw[s][w] = v;
+            anyv |= v != 0 ? 1 : 0;
+        }
+        if (!__syncthreads_or(anyv)) continue;                   // no coast cell in this pass's rows within reach
+        if (tid < ns) {
+            int c = 0;
+            for (int w = 0; w < nws; ++w) c += __builtin_popcountll(s_bw[tid][w]);
+            s_cnt[tid] = (unsigned short)c;
+        }
+        if (!have) {                                             // the first coordinates this workgroup reads
+            have = true;
+            if (valid) {
+                const size_t o = (size_t)yy * nx + xx;
+                phit = tlat[o] * d2r;                            // phi1 (ref: UM :524)
+                const T lam1 = tlon[o] * d2r;                    // lam1 (:523)
+                l2 = ((r2d * lam1) > T(180.)) ? d2r * ((r2d * lam1) - T(360.)) : lam1;   // ref: UM :560-564
+                cost = cos(phit);
+            }
+        }
+        __syncthreads();
+        for (int cs = 0; cs < ns;) {
+            // the chunk: slots cs .. ce-1, as many as the list holds (workgroup-uniform: the counts are in LDS)
+            int ce = cs, tot = 0;
+            while (ce < ns && tot + s_cnt[ce] <= UMW_CAP) tot += s_cnt[ce++];
+            if (tot == 0) { cs = ce; continue; }
+            __syncthreads();                                     // (the chunk before is read by every wave)
+            if (tid >= cs && tid < ce) {
+                int e = 0;
+                for (int s = cs; s < tid; ++s) e += s_cnt[s];
+                for (int w = 0; w < nws; ++w) {
+                    s_off[tid][w] = (unsigned short)e;
+                    e += __builtin_popcountll(s_bw[tid][w]);
+                }
+            }
+            __syncthreads();
+            // the coast cells' terms, a thread per (slot, word): cells without a coast bit read no coordinates
+            for (int i = tid; i < (ce - cs) * nws; i += 64 * UMW_TY) {
+                const int s = cs + i / nws, w = i - (s - cs) * nws;
+                uint64_t v = s_bw[s][w];
+                if (!v) continue;
+                int e = s_off[s][w];
+                const size_t orow = (size_t)slot_row(s, j) * nx;
+                while (v) {
+                    const int b = __builtin_ctzll(v);
+                    v &= v - 1ull;
+                    const size_t o = orow + (x0 - wi + 64 * w + b);      // (a set bit is an interior cell)
+                    const T lat = tlat[o], lon = tlon[o];
+                    const T phis = lat * d2r;
+                    s_phi[e] = phis;
+                    s_cp[e] = cos(phis);
+                    s_l1[e] = (lon > T(180)) ? d2r * (lon - T(360.)) : d2r * lon;     // ref: UM :552-556
+                    ++e;
+                }
+            }
+            __syncthreads();
+            if (valid)
+                for (int s = cs; s < ce; ++s) {
+                    if (!s_cnt[s]) continue;                     // workgroup-uniform
+                    const int ii = slot_row(s, j) - yy;          // source row yy + ii
+                    if (ii < -wj || ii > wj) continue;           // wave-uniform
+                    for (int wd = qlo >> 6; wd <= qhi >> 6; ++wd) {
+                        const uint64_t full = s_bw[s][wd];
+                        uint64_t v = full;
+                        if (wd == qlo >> 6) v &= ~0ull << (qlo & 63);
+                        if (wd == qhi >> 6) v &= ~0ull >> (63 - (qhi & 63));
+                        if (!v) continue;
+                        const int base = s_off[s][wd];
+                        while (v) {
+                            const int b = __builtin_ctzll(v);
+                            v &= v - 1ull;
+                            const int e = base + __builtin_popcountll(full & ((1ull << b) - 1ull));
+                            const bool early = ii < 0 || (ii == 0 && 64 * wd + b <= qown);
+                            const T sp = um_sin_as_written<T>((s_phi[e] - phit) / T(2));      // dphi (ref: UM :565)
+                            const T sp2 = sp * sp, cps = s_cp[e];
+#ifndef SB_UM_WIN_NO_LAT_CUT
+                            if (cost >= T(0) && cps >= T(0) && sp2 >= (early ? a_early : a_late)) continue;
+#endif
+                            const T dlam = s_l1[e] - l2;         // l1 - l2 (ref: UM :565)
+                            const T sl = um_sin_as_written<T>(dlam / T(2));
+                            const T a = sp2 + (cps * (cost * (sl * sl)));     // ref: UM :566
+                            if (early) a_early = a < a_early ? a : a_early;
+                            else a_late = a < a_late ? a : a_late;
+                        }
+                    }
+                }
+            cs = ce;
+        }
+    }
+    if (!valid) return;
+    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref: UM :567
+    T m_early = a_early < none ? dist_of(a_early) : big;
+    const T m_late = a_late < none ? dist_of(a_late) : big;
+    if (m_early > T(2) * maxdist) m_early = big;                 // ref: UM :578 at the target's sweep position
+    const T m = m_early < m_late ? m_early : m_late;
+    const size_t o = (size_t)(yy + hj) * NX + xx + hi;
+    if (m >= big) cdist[o] = big;
+    else cdist[o] = (landfrac[(size_t)yy * nx + xx] > T(0)) ? m : -m;       // ref: UM :568-574
+}
+
 template <typename T>
 hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st) {
     hipLaunchKernelGGL(k_edges_um<T>, dim3((nx + 255) / 256, (ny + UM_EDGE_ROWS - 1) / UM_EDGE_ROWS), dim3(256), 0, st,
@@ -246,9 +443,28 @@ hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, c
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
+                                 int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st) {
+    if (hi < 0 || hj < 0 || wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
+    // window = ghost width <= 31: sb_get_dist_um_*'s call, its kernel and its field, bit for bit
+    if (wi == hi && wj == hj && wi <= 31 && wj <= 31)
+        return sb_launch_dist_um<T>(coast, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, maxdist, bits, st);
+    const int nw = (nx + 63) / 64;
+    hipLaunchKernelGGL(k_coastbits_um<T>, dim3((nx + 255) / 256, (ny + UM_BITS_ROWS - 1) / UM_BITS_ROWS), dim3(256), 0, st,
+                       coast, bits, nx, ny, hi, hj, nw);
+    hipLaunchKernelGGL(k_dist_um_wide<T>, dim3((nx + 63) / 64, (ny + UMW_TY - 1) / UMW_TY), dim3(64 * UMW_TY), 0, st,
+                       bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist);
+    return hipGetLastError();
+}
+
 template hipError_t sb_launch_edges_um<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges_um<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_dist_um<float>(const float *, const float *, const float *, const float *, float *, int, int,
                                              int, int, float, uint64_t *, hipStream_t);
 template hipError_t sb_launch_dist_um<double>(const double *, const double *, const double *, const double *, double *, int,
                                               int, int, int, double, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um_win<float>(const float *, const float *, const float *, const float *, float *, int,
+                                                 int, int, int, int, int, float, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um_win<double>(const double *, const double *, const double *, const double *, double *,
+                                                  int, int, int, int, int, int, double, uint64_t *, hipStream_t);

@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("SEABREEZE_HIP_LIB", os.path.join(_HERE, "libseabreeze
 SB_BND_WRAPPER, SB_BND_GLOBAL, SB_BND_HALO = 0, 1, 2
 SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK = 1, 2
 SB_DIST_MAX_WINDOW = 255            # include/seabreeze_hip.h: the widest get_dist window (kwin, or the derived half-width)
+SB_DIST_UM_MAX_WINDOW = 255         # include/seabreeze_hip.h: the widest window of get_dist_um_win, each way
 
 _SFX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 _CT = {np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double}
@@ -316,6 +317,29 @@ class Context:
         self._chk(rc, "sb_get_dist_um")
         return cdist
 
+    def get_dist_um_win(self, coast_l, landfrac, true_lat, true_lon, halo_i, halo_j, win_i, win_j, maxdist=180.0,
+                        out=None):
+        """get_dist_um with the window stated apart from the layout: +-win_i columns x +-win_j rows, each 0 ..
+        SB_DIST_UM_MAX_WINDOW, wider or narrower than the ghost width; halo_i, halo_j >= 0 only say where the interior of
+        coast_l (ny + 2*halo_j, nx + 2*halo_i) lies.  Shapes, `out` and the result are get_dist_um's."""
+        coast_l = np.ascontiguousarray(coast_l)
+        dt = np.dtype(coast_l.dtype)
+        landfrac = _host(landfrac, dt); true_lat = _host(true_lat, dt); true_lon = _host(true_lon, dt)
+        ny, nx = landfrac.shape
+        if halo_i < 0 or halo_j < 0 or coast_l.shape != (ny + 2 * halo_j, nx + 2 * halo_i):
+            raise ValueError(f"coast_l shape {coast_l.shape} != {(ny + 2 * halo_j, nx + 2 * halo_i)}")
+        if true_lat.shape != (ny, nx) or true_lon.shape != (ny, nx):
+            raise ValueError("true_lat, true_lon must be (ny, nx) like landfrac")
+        cdist = np.zeros_like(coast_l) if out is None else out
+        if cdist.shape != coast_l.shape or cdist.dtype != dt or not cdist.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of coast_l's shape and dtype")
+        rc = getattr(self.lib, f"sb_get_dist_um_win_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i),
+                                                                C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j),
+                                                                _p(coast_l), _p(landfrac), _p(true_lat), _p(true_lon),
+                                                                _CT[dt](maxdist), _p(cdist))
+        self._chk(rc, "sb_get_dist_um_win")
+        return cdist
+
     # ------------------------------------------------------------------ device-pointer API
     def sigmoid_dev(self, dtype, nx, ny, ary, sm, stream=None):
         """sm = 1/(1+exp(-std*(ary-r))) on device arrays (raw addresses); enqueues without synchronising."""
@@ -362,6 +386,15 @@ class Context:
         self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), _p(coast_l), _p(landfrac),
                      _p(true_lat), _p(true_lon), _CT[dt](maxdist), _p(cdist), C.c_void_p(stream) if stream else None),
                   "sb_get_dist_um_dev")
+
+    def get_dist_um_win_dev(self, dtype, nx, ny, halo_i, halo_j, win_i, win_j, coast_l, landfrac, true_lat, true_lon,
+                            cdist, maxdist=180.0, stream=None):
+        """get_dist_um_win on device arrays (raw addresses, coordinates included); enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        fn = getattr(self.lib, f"sb_get_dist_um_win_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j),
+                     _p(coast_l), _p(landfrac), _p(true_lat), _p(true_lon), _CT[dt](maxdist), _p(cdist),
+                     C.c_void_p(stream) if stream else None), "sb_get_dist_um_win_dev")
 
     def sigma_moments_dev(self, dtype, nx, ny, halo, sigma, moments5, stream=None):
         """Band-local sigma moments -> 5 doubles at device address moments5."""
