@@ -162,12 +162,7 @@ struct sb_ctx {
     // get_dist's coordinate tables (device: `vecs`): the coordinates they were made from, the host copy the upload reads,
     // and what the host found out about the coordinates' order
     std::vector<unsigned char> dist_key, dist_hv;
-    // what the host derives from them, each true only with every latitude within +-90 degrees (cos >= 0): longitudes in
-    // order round the whole circle, and the largest step | the steps j -> j+1, j < nx-1 (without the closing one) all
-    // one way, and the largest of them | latitudes stepping one way.  k_dist_bits' `nearest` needs the first and the
-    // third; k_dist_wide takes its cuts one by one.
-    bool dist_circle = false, dist_inner = false, dist_latmono = false;
-    double dist_maxstep = 0.0, dist_maxstep_inner = 0.0;
+    SbDistTraits dist_traits;           // what the host found out about the coordinates' order (sb_dist_plan.hpp)
     hipStream_t dist_upload_stream = nullptr;   // the stream the tables were uploaded on, until another stream has waited for it
     // staging buffers for the host-pointer entry points
     std::vector<DevBuf> stage;
@@ -1016,41 +1011,7 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
         if ((rc = ensure(c, c->vecs, c->dist_hv.size()))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->vecs.p, hv, c->dist_hv.size(), hipMemcpyHostToDevice, st));   // (dist_hv lives on with the context)
         c->dist_upload_stream = st;
-        // k_dist_bits may keep only the nearest hit on each side of a source row when the haversine term grows with
-        // the index distance inside the window: longitudes that step strictly eastwards once round the circle (the
-        // closing step from the last column to the first included); and may stop its walk over the rows early when the
-        // latitudes step one way.  (Whether the window stays short of half the circle depends on k: checked per call.)
-        double turn = 0.0, maxstep = 0.0;
-        bool mono = nx > 1;
-        for (int j = 0; j < nx && mono; ++j) {
-            double d = std::fmod((double)lon[(j + 1) % nx] - (double)lon[j], 360.0);
-            if (d < 0) d += 360.0;
-            mono = d > 1.0e-6;
-            turn += d;
-            maxstep = d > maxstep ? d : maxstep;
-        }
-        bool latin = true;                        // cos(phi) >= 0: the haversine term grows with sin^2 of either difference
-        for (int i = 0; i < ny && latin; ++i) latin = std::fabs((double)lat[i]) <= 90.0;
-        bool latmono = latin;                     // sp^2 grows with the row distance: latitudes step one way
-        for (int i = 0; i + 2 < ny && latmono; ++i)
-            latmono = ((double)lat[i + 1] - (double)lat[i]) * ((double)lat[i + 2] - (double)lat[i + 1]) > 0.0;
-        c->dist_circle = latin && mono && turn < 360.0 + 1.0e-3;
-        c->dist_latmono = latmono;
-        c->dist_maxstep = maxstep;
-        // k_dist_wide decides the column cut per target: a window that stays inside the frame never meets the closing
-        // step, so for it the steps inside the frame decide (eastwards or westwards, folded to +-180 degrees)
-        bool east = nx > 1, west = nx > 1;
-        double maxin = 0.0;
-        for (int j = 0; j + 1 < nx && (east || west); ++j) {
-            double d = std::fmod((double)lon[j + 1] - (double)lon[j], 360.0);
-            if (d > 180.0) d -= 360.0;
-            if (d <= -180.0) d += 360.0;
-            east = east && d > 1.0e-6;
-            west = west && d < -1.0e-6;
-            maxin = std::fabs(d) > maxin ? std::fabs(d) : maxin;
-        }
-        c->dist_inner = latin && (east || west);
-        c->dist_maxstep_inner = maxin;
+        c->dist_traits = sb_dist_traits<T>(lon, lat, nx, ny);
         c->dist_key.resize(kb + sizeof(dims));
         std::memcpy(c->dist_key.data(), dims, sizeof(dims));
         std::memcpy(c->dist_key.data() + sizeof(dims), lon, (size_t)nx * sizeof(T));
@@ -1063,16 +1024,8 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
     }
     const T *dphi = (const T *)c->vecs.p, *dlam = dphi + ny;
     if ((rc = ensure(c, c->coastbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
-    // bit 0: k_dist_bits' `nearest` (k <= 31); bits 1-3: k_dist_wide's cuts (sb_coast_kernels.hip), each with its own condition
-    const bool circle = c->dist_circle && (double)k * c->dist_maxstep < 170.0;
-    int cuts = (circle && c->dist_latmono) ? 1 : 0;
-    if (circle) cuts |= 2;
-#ifndef SB_DIST_NO_INNER_CUT                                     // (A/B builds: what the per-target rule buys, tools/dist_wide_cost.py)
-    if (c->dist_inner && (double)k * c->dist_maxstep_inner < 170.0) cuts |= 4;
-#endif
-    if (c->dist_latmono) cuts |= 8;
     HIPCHK(c, sb_launch_dist<T>(coast, mask, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist, nx, ny, k, maxdist,
-                                (uint64_t *)c->coastbits.p, cuts, st));
+                                (uint64_t *)c->coastbits.p, sb_dist_cuts(c->dist_traits, k), st));
     // a distance field made here bounds the search radius of the following diag calls
     c->radius_hint = k + 1;
     return SB_OK;
@@ -1131,34 +1084,6 @@ int check_dist_um(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, con
     return SB_OK;
 }
 
-template <typename T>
-int get_dist_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat, const T *tlon,
-                    T maxdist, T *cdist, void *stream) {
-    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
-    if (rc) return rc;
-    // the coordinates are device fields: nothing is derived from them on the host, nothing is kept between calls
-    if ((rc = ensure(c, c->umbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, sb_launch_dist_um<T>(coast, lf, tlat, tlon, cdist, nx, ny, hi, hj, maxdist, (uint64_t *)c->umbits.p, st));
-    return SB_OK;
-}
-
-template <typename T>
-int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat,
-                     const T *tlon, T maxdist, T *cdist) {
-    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
-    if (rc) return rc;
-    const size_t n = (size_t)nx * ny, nl = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
-    Stager s(c);
-    // (cdist in as well: its ghost cells stay; with cdist == coast both copies hold the same field)
-    T *dco = s.in(coast, nl), *dl = s.in(lf, n), *dla = s.in(tlat, n), *dlo = s.in(tlon, n), *dcd = s.in((const T *)cdist, nl);
-    if (s.rc) return s.rc;
-    rc = get_dist_um_dev<T>(c, nx, ny, hi, hj, dco, dl, dla, dlo, maxdist, dcd, nullptr);
-    if (rc) return rc;
-    s.back(cdist, dcd, nl);
-    return s.finish();
-}
-
 // sb_get_dist_um_win_*: the window stated apart from the layout (halo_i, halo_j >= 0 say where the interior lies)
 template <typename T>
 int check_dist_um_win(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *coast, const T *lf, const T *tlat,
@@ -1178,6 +1103,7 @@ int get_dist_um_win_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int w
                         const T *tlat, const T *tlon, T maxdist, T *cdist, void *stream) {
     int rc = check_dist_um_win<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, cdist);
     if (rc) return rc;
+    // the coordinates are device fields: nothing is derived from them on the host, nothing is kept between calls
     if ((rc = ensure(c, c->umbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIPCHK(c, sb_launch_dist_um_win<T>(coast, lf, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, maxdist, (uint64_t *)c->umbits.p, st));
@@ -1191,13 +1117,30 @@ int get_dist_um_win_host(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int 
     if (rc) return rc;
     const size_t n = (size_t)nx * ny, nl = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
     Stager s(c);
-    // (as get_dist_um_host: cdist goes in as well, its ghost cells stay)
+    // (cdist in as well: its ghost cells stay; with cdist == coast both copies hold the same field)
     T *dco = s.in(coast, nl), *dl = s.in(lf, n), *dla = s.in(tlat, n), *dlo = s.in(tlon, n), *dcd = s.in((const T *)cdist, nl);
     if (s.rc) return s.rc;
     rc = get_dist_um_win_dev<T>(c, nx, ny, hi, hj, wi, wj, dco, dl, dla, dlo, maxdist, dcd, nullptr);
     if (rc) return rc;
     s.back(cdist, dcd, nl);
     return s.finish();
+}
+
+// sb_get_dist_um_*: the window is the layout's ghost width, at most 31 cells each way
+template <typename T>
+int get_dist_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat, const T *tlon,
+                    T maxdist, T *cdist, void *stream) {
+    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    return get_dist_um_win_dev<T>(c, nx, ny, hi, hj, hi, hj, coast, lf, tlat, tlon, maxdist, cdist, stream);
+}
+
+template <typename T>
+int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, const T *lf, const T *tlat,
+                     const T *tlon, T maxdist, T *cdist) {
+    int rc = check_dist_um<T>(c, nx, ny, hi, hj, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    return get_dist_um_win_host<T>(c, nx, ny, hi, hj, hi, hj, coast, lf, tlat, tlon, maxdist, cdist);
 }
 
 }  // namespace

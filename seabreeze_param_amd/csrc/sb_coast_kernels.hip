@@ -11,72 +11,39 @@
 //            window; every other call takes the bit-plane kernels: k_dist_bits[_small] for
 //            k <= 31, k_dist_wide for 32 <= k <= SB_DIST_MAX_WINDOW (71 and 115 times faster than
 //            k_dist at k = 40 and 100 on 2560 x 1920).
+// Which kernel runs, and what it may leave out, is decided in sb_dist_plan.hpp; what the kernels share with the UM
+// layout's (the Sobel block, the bit plane, the epilogues, the one-word walk, why each cut is exact) is in
+// sb_coast_common.hpp.
 #include "../../include/seabreeze_hip.h"
 #include "sb_device.hpp"
 #include "sb_launch.hpp"
+#include "sb_coast_common.hpp"
 
+// k_edges' layout: the boundary mapping of sb_map_cell (cyclic longitudes with the f2py flavour's column quirk, clamped
+// latitudes; ref: sobel.f90:60-66, generic :340-352) and either flavour's land rule
 template <typename T>
-__device__ __forceinline__ int land_rule(T l, T c, int rule) {
-    if (rule == 0) return (l + c > T(0.4)) ? 1 : 0;            // ref: sobel.f90:51,69
-    if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;             // ref: generic :325-330
-    return (l + c >= T(0.5)) ? 1 : 0;                          // ref: generic :332-336
-}
-
-// A workgroup classifies the cells of a 256-column x EDGE_ROWS-row block and of the ring round it once (18 rows read
-// for 16 written: 1.125 x the compulsory reads; with 8-row blocks the PMC passes showed 1.47 x)
-// (two loads per cell instead of eighteen), keeps the land flags in LDS and takes the nine-point sums
-// from there.  The boundary mapping (cyclic longitudes with the f2py flavour's column quirk, clamped
-// latitudes; ref: sobel.f90:60-66, generic :340-352) is applied to the staged cell, so a flag means
-// exactly what the reference's inner loop would have read at that offset.
-#define EDGE_ROWS 16
-#define EDGE_PITCH 264
+struct EdgesGrid {
+    static constexpr bool tail_by_index = false;
+    Geo g;
+    int rule;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X, Y;
+        sb_map_cell(g, x, y, X, Y);
+        return (size_t)Y * g.nx + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)y * g.nx + x; }
+    __device__ __forceinline__ int land(T l, T c) const {
+        if (rule == 0) return (l + c > T(0.4)) ? 1 : 0;            // ref: sobel.f90:51,69
+        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;             // ref: generic :325-330
+        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: generic :332-336
+    }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_edges(const T *__restrict__ lsm, const T *__restrict__ ci,
                                                T *__restrict__ coast, Geo g, int rule) {
-    __shared__ unsigned char s_land[(EDGE_ROWS + 2) * EDGE_PITCH];
-    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * EDGE_ROWS;
-    constexpr int NCELL = (EDGE_ROWS + 2) * 258, NIT = (NCELL + 255) / 256;
-    T l[NIT], c[NIT];
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {                      // every load issued before the first is used
-        const int i = threadIdx.x + 256 * j, r = i / 258, cc = i - r * 258;
-        int X, Y;
-        sb_map_cell(g, x0 - 1 + cc, y0 - 1 + (r < EDGE_ROWS + 2 ? r : 0), X, Y);
-        const size_t o = (size_t)Y * g.nx + X;
-        l[j] = lsm[o];
-        c[j] = ci[o];
-    }
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {
-        const int i = threadIdx.x + 256 * j, r = i / 258, cc = i - r * 258;
-        const int land = land_rule(l[j], c[j], rule);
-        if (i < NCELL) s_land[r * EDGE_PITCH + cc] = (unsigned char)land;
-    }
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    if (x >= g.nx) return;
-    // weight = reshape((/-1,-2,-1, 0,0,0, 1,2,1/),(3,3)) column-major: w(r,c) = (1,2,1)(r) * (-1,0,1)(c)
-    // px += w(a+2, b+2)*m, py += w(b+2, a+2)*m     ref: sobel.f90:74-75
-    // -> px = sum_a (1,2,1)(a) * (m[a][2] - m[a][0]),  py = sum_b (1,2,1)(b) * (m[2][b] - m[0][b])
-    int m[3][3];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) m[a + 1][b] = s_land[a * EDGE_PITCH + threadIdx.x + b];
-#pragma unroll
-    for (int r = 0; r < EDGE_ROWS; ++r) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            m[0][b] = m[1][b];
-            m[1][b] = m[2][b];
-            m[2][b] = s_land[(r + 2) * EDGE_PITCH + threadIdx.x + b];
-        }
-        const int px = (m[0][2] - m[0][0]) + 2 * (m[1][2] - m[1][0]) + (m[2][2] - m[2][0]);
-        const int py = (m[2][0] - m[0][0]) + 2 * (m[2][1] - m[0][1]) + (m[2][2] - m[0][2]);
-        const int y = y0 + r;
-        if (y < g.ny) coast[(size_t)y * g.nx + x] = (px == 0 && py == 0) ? T(0) : T(1);   // sqrt(px^2+py^2) == 0
-    }
+    __shared__ unsigned char s_land[EDGE_LDS];
+    sb_edges_block(lsm, ci, coast, s_land, g.nx, g.ny, EdgesGrid<T>{g, rule});
 }
 
 
@@ -101,8 +68,7 @@ __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const
     const int xx = x0 + lx, yy = y0 + ly;
     if (xx >= nx || yy >= ny) return;
 
-    const T R = T(6370.9989);                                   // ref: sobel.f90:115
-    const T big = T(12000.);
+    const T big = SbDist<T>::big;
     const T phit = phi[yy], lamt = lamf[xx];
     const T cost = cos(phit);
     T m_early = big, m_late = big;
@@ -118,20 +84,15 @@ __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const
             const T dphi = phis - phit;                          // phi1(i) - phi1(yy)
             const T dlam = lamf[xs] - lamt;                      // l1 - l2
             const T sp = sin(dphi / T(2)), sl = sin(dlam / T(2));
-            const T a = sp * sp + (cos(phis) * (cost * (sl * sl)));   // ref: sobel.f90:176
-            const T c = (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5);   // ref :177
+            const T c = dist_of(sb_hav(sp * sp, cos(phis), cost, sl));
             const bool early = (ys < yy) || (ys == yy && xs <= xx);
             if (early) m_early = c < m_early ? c : m_early;
             else m_late = c < m_late ? c : m_late;
         }
     }
-    // the reference resets cdist(j,i) to 12000 when its own sweep position is reached and
-    // the value so far exceeds 2*maxdist (ref: sobel.f90:188); later sources may still lower it
-    if (m_early > T(2) * maxdist) m_early = big;
-    const T m = m_early < m_late ? m_early : m_late;
+    // (the minimum over distances, not over a: one distance per hit)
     const size_t o = (size_t)yy * nx + xx;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
+    sb_dist_write(cdist + o, sb_dist_reset_min(m_early, m_late, maxdist), mask + o);
 }
 
 // ------------------------------------------------------------------------------------
@@ -139,52 +100,10 @@ __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const
 // grid): k_coastbits packs coast > 0 into one 64-bit word per 64-cell longitude segment
 // (a wave ballot); k_dist_bits pulls the (2k+1)-column window of each source row out of at
 // most four words and visits set bits only.  Nine targets in ten have an empty window and
-// cost a few hundred instructions instead of (2k+1)^2 byte probes.
-//
-// Two further cuts, both exact up to the last place of atan2:
-//   * the distance c = 2R atan2(sqrt(a), sqrt(1-a)) + 0.5 (ref: sobel.f90:176-177) grows with a,
-//     so the minimum of c over a class of sources is c at the minimum of a: the kernel keeps
-//     min(a) of the sources swept before and after the target and takes two atan2 per cell
-//     instead of one per coast hit;
-//   * within one source row a = sp^2 + cos(phis) cos(phit) sin^2(dlam/2) grows with the
-//     longitude distance, so of the hits left of (or at) the target column only the nearest can
-//     be the minimum, and likewise on the right: two hits per row instead of up to 2k+1.  On the
-//     target's own row the sweep order splits each side once more where the window crosses the
-//     seam (xs <= xx is decided on wrapped indices, ref: sobel.f90:188), so up to four there.
-//   * a >= sp^2, which grows with the row distance: the walk away from the target row stops early.
-//     `nearest` (both row cuts) is set by the host only when the longitudes step one way round the circle,
-//     the window spans less than half of it and the latitudes step one way (sb_capi.hip); otherwise every
-//     hit of every row is visited.
+// cost a few hundred instructions instead of (2k+1)^2 byte probes.  min(a) per sweep class and
+// the cuts `nearest` stands for (SB_CUT_NEAREST): sb_coast_common.hpp.
 // Same arithmetic per visited hit as k_dist, same early/late bookkeeping.
 // ------------------------------------------------------------------------------------
-#define COASTBITS_ROWS 8              // rows per workgroup of k_coastbits: eight loads in flight per thread
-template <typename T>
-__global__ __launch_bounds__(256) void k_coastbits(const T *__restrict__ coast, uint64_t *__restrict__ bits,
-                                                   int nx, int ny, int nw) {
-    const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * COASTBITS_ROWS;
-    T v[COASTBITS_ROWS];
-#pragma unroll
-    for (int r = 0; r < COASTBITS_ROWS; ++r) {
-        const int y = y0 + r < ny ? y0 + r : ny - 1;                 // (clamped: every load unconditional)
-        v[r] = coast[(size_t)y * nx + (x < nx ? x : nx - 1)];
-    }
-#pragma unroll
-    for (int r = 0; r < COASTBITS_ROWS; ++r) {
-        const uint64_t w = __ballot(x < nx && v[r] > T(0));          // ref: sobel.f90:157
-        if ((threadIdx.x & 63) == 0 && (x >> 6) < nw && y0 + r < ny) bits[(size_t)(y0 + r) * nw + (x >> 6)] = w;
-    }
-}
-
-// bits p .. p+l-1 (l <= 63, p+l <= nx) of a row of the plane
-__device__ __forceinline__ uint64_t row_bits(const uint64_t *__restrict__ rw, int p, int l) {
-    const int w = p >> 6, o = p & 63;
-    uint64_t v = rw[w] >> o;
-    if (o + l > 64) v |= rw[w + 1] << (64 - o);
-    return v & ((1ull << l) - 1ull);
-}
-
-__device__ __forceinline__ uint64_t top_bit(uint64_t x) { return x ? 1ull << (63 - __builtin_clzll(x)) : 0ull; }
-__device__ __forceinline__ uint64_t low_bit(uint64_t x) { return x & (0ull - x); }
 
 // k_dist_bits as rounds 1-3 had it (every word and table entry from global memory, per target and row): kept for grids
 // narrower than 2k + 1 + 256 columns, where the staged reach of a workgroup would wrap round the seam more than once
@@ -196,11 +115,8 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
                                                    T maxdist, int nearest) {
     __shared__ T s_sp2[64], s_cosp[64], s_cost;
     const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
-    const T big = T(12000.);
-    // Which of the 2k+1 source rows hold any coast cell within reach of this wave's 64 targets?  Lane i ORs the
-    // (at most three) words of row yy - k + i that cover columns x0 - k .. x0 + 63 + k; the ballot is a row mask in
-    // scalar registers, and rows without a bit are skipped by the whole wave.  Four targets in five see no coast
-    // at all and end here after one load round.  A wave whose reach crosses the seam keeps every row.
+    const T big = SbDist<T>::big;
+    // the row mask of k_dist_bits, but a wave whose reach crosses the seam keeps every row
     uint64_t rowmask;
     {
         const int lane = threadIdx.x & 63, wx0 = blockIdx.x * 256 + ((int)threadIdx.x & ~63);
@@ -214,116 +130,41 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
         }
         rowmask = __ballot(any != 0);
     }
-    // Four workgroups in five have no coast cell within reach of any of their 256 targets: they write the "unreached"
-    // value and leave before any trigonometry (round 2 formed the latitude factors of the 2k+1 source rows and
-    // cos(phi) of the target row -- the same for the whole workgroup -- in every workgroup and every thread).
+    // no coast cell within reach of any of the 256 targets: "unreached", before any trigonometry
     if (!__syncthreads_or(rowmask != 0 ? 1 : 0)) {
         if (xx < nx) cdist[(size_t)yy * nx + xx] = big;
         return;
     }
-    // the latitude factors of the 2k+1 source rows are the same for every target of this row: once per workgroup
-    const T phit = phi[yy];
-    if ((int)threadIdx.x <= 2 * k) {
-        int ys = yy + (int)threadIdx.x - k;
-        ys = ys < 0 ? 0 : (ys >= ny ? ny - 1 : ys);
-        const T phis = phi[ys];
-        const T dphi = phis - phit;                              // phi1(i) - phi1(yy)
-        const T sp = sin(dphi / T(2));
-        s_sp2[threadIdx.x] = sp * sp;
-        s_cosp[threadIdx.x] = cos(phis);
-    } else if ((int)threadIdx.x == 2 * k + 1) s_cost = cos(phit);
+    sb_stage_lat(phi, ny, yy, k, (int)threadIdx.x, s_sp2, s_cosp, &s_cost);
     __syncthreads();
     if (xx >= nx) return;
     if (rowmask == 0) {                                          // wave-uniform: none of this wave's targets is reached
         cdist[(size_t)yy * nx + xx] = big;
         return;
     }
-    const T R = T(6370.9989);                                   // ref: sobel.f90:115
     const T lamt = lamf[xx];
-    const T cost = s_cost;
-    // fp64: sin((l1 - l2) / 2) = sin(l1/2) cos(l2/2) - cos(l1/2) sin(l2/2) from per-column tables (the host forms
-    // them with the folded longitudes): two loads, two products and a difference per hit where the library sine took some eighty
-    // instructions.  The difference of products carries an absolute error of 1e-16, i.e. <= 4e-13 relative in the
-    // distance at the finest spacing in use (0.07 degrees); the tests hold 1e-12.  fp32 keeps the sine: there the same
-    // identity would cost four digits.
     T sht = T(0), cht = T(0);
     if constexpr (sizeof(T) == 8) { sht = shl[xx]; cht = chl[xx]; }
     const int L = 2 * k + 1;
     int start = (xx - k) % nx;                                   // first window column, circular
     if (start < 0) start += nx;
     const int len1 = L < nx - start ? L : nx - start;
-    // window bit b is column xx - k + b: bits 0 .. k lie left of or at the target, the rest right of it;
-    // bits below k - xx and from nx - xx + k on have wrapped round the seam
-    const uint64_t left = (2ull << k) - 1ull;
-    const uint64_t wrapl = (k - xx > 0) ? (1ull << (k - xx)) - 1ull : 0ull;
-    const uint64_t wrapr = (nx - xx + k < 64) ? ~0ull << (nx - xx + k) : 0ull;
-    const T none = T(4);                                         // a <= 1: "no source in this class"
-    T a_early = none, a_late = none;
-    auto row = [&](int ii) {
-        const int ys = yy + ii;
-        const uint64_t *rw = bits + (size_t)ys * nw;
-        uint64_t wb = row_bits(rw, start, len1);
-        if (len1 < L) wb |= row_bits(rw, 0, L - len1) << len1;
-        if (!wb) return;
-        if (nearest) {
-            const uint64_t wl = wb & left, wr = wb & ~left;
-            if (ii != 0) wb = top_bit(wl) | low_bit(wr);
-            else wb = top_bit(wl & ~wrapl) | top_bit(wl & wrapl) | low_bit(wr & ~wrapr) | low_bit(wr & wrapr);
-        }
-        const T sp2 = s_sp2[ii + k], cosp = s_cosp[ii + k];
-        while (wb) {
-            const int b = __builtin_ctzll(wb);
-            wb &= wb - 1;
-            int xs = start + b;
-            if (xs >= nx) xs -= nx;
-            T sl;
-            // (two rounded products, no fma: for the target's own column they are the same product and the difference
-            // is exactly zero -- a coast cell's own distance stays exactly 0.5 km, SURVEY.md section 4's anchor)
-            if constexpr (sizeof(T) == 8) sl = shl[xs] * cht - chl[xs] * sht;
-            else {
-                const T dlam = lamf[xs] - lamt;                  // l1 - l2
-                sl = sin(dlam / T(2));
-            }
-            const T a = sp2 + (cosp * (cost * (sl * sl)));       // ref: sobel.f90:176
-            const bool early = (ys < yy) || (ys == yy && xs <= xx);
-            if (early) a_early = a < a_early ? a : a_early;
-            else a_late = a < a_late ? a : a_late;
-        }
-    };
-    // Rows above the target are swept before it, rows below after it.  a >= sp2 of its row, and with latitudes
-    // that step one way (the host's condition for `nearest`) sp2 grows with the row distance: a walk away
-    // from the target can stop at the first row whose sp2 is no smaller than the class's minimum so far.
-    if ((rowmask >> k) & 1) row(0);
-    for (int d = 1; d <= k && yy - d >= 0; ++d) {                // clamped rows add no new sources
-        if (!((rowmask >> (k - d)) & 1)) continue;               // wave-uniform
-        if (nearest && !(s_sp2[k - d] < a_early)) break;
-        row(-d);
-    }
-    for (int d = 1; d <= k && yy + d < ny; ++d) {
-        if (!((rowmask >> (k + d)) & 1)) continue;
-        if (nearest && !(s_sp2[k + d] < a_late)) break;
-        row(d);
-    }
-    T m_early = big, m_late = big;
-    if (a_early < none) m_early = (R * T(2)) * atan2(sqrt(a_early), sqrt(T(1) - a_early)) + T(0.5);   // ref :177
-    if (a_late < none) m_late = (R * T(2)) * atan2(sqrt(a_late), sqrt(T(1) - a_late)) + T(0.5);
-    if (m_early > T(2) * maxdist) m_early = big;                 // ref: sobel.f90:188 at sweep time
-    const T m = m_early < m_late ? m_early : m_late;
+    T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
+    sb_dist_walk<T, uint64_t>(
+        rowmask, k, nearest, xx, yy, nx, start, s_sp2, s_cosp, s_cost,
+        [&](int ii) {
+            const uint64_t *rw = bits + (size_t)(yy + ii) * nw;
+            uint64_t wb = row_bits(rw, start, len1);
+            if (len1 < L) wb |= row_bits(rw, 0, L - len1) << len1;
+            return wb;
+        },
+        [&](int, int xs) -> T {
+            if constexpr (sizeof(T) == 8) return shl[xs] * cht - chl[xs] * sht;
+            else return sin((lamf[xs] - lamt) / T(2));           // l1 - l2
+        },
+        a_early, a_late);
     const size_t o = (size_t)yy * nx + xx;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
-}
-
-// 64 bits of a row of the plane from circular column p on (0 <= p < nx, nx >= 64): across the seam where need be
-__device__ __forceinline__ uint64_t row_bits64(const uint64_t *__restrict__ rw, int p, int nx) {
-    if (p + 64 <= nx) {
-        const int w = p >> 6, o = p & 63;
-        uint64_t v = rw[w] >> o;
-        if (o) v |= rw[w + 1] << (64 - o);
-        return v;
-    }
-    const int l1 = nx - p;                                       // 1 .. 63 columns up to the seam, the rest from column 0
-    return row_bits(rw, p, l1) | (row_bits(rw, 0, 64 - l1) << l1);
+    sb_dist_write(cdist + o, sb_dist_finish_both(a_early, a_late, maxdist), mask + o);
 }
 
 #define DIST_SPAN (256 + 2 * 31)                                 // columns a workgroup's 256 targets can reach (k <= 31)
@@ -353,11 +194,11 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     const int x0 = blockIdx.x * 256, y0 = blockIdx.y * DIST_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
     const bool rowok = yy < ny;                                  // (an odd number of rows: the last workgroup's second row)
-    const T big = T(12000.);
+    const T big = SbDist<T>::big;
     // Which of the 2k+1 source rows hold any coast cell within reach of this wave's 64 targets?  Lane i ORs the
     // (at most three) words of row yy - k + i that cover columns x0 - k .. x0 + 63 + k; the ballot is a row mask in
     // scalar registers, and rows without a bit are skipped by the whole wave.  Four targets in five see no coast
-    // at all and end here after one load round.  A wave whose reach crosses the seam keeps every row.
+    // at all and end here after one load round.
     uint64_t rowmask;
     {
         const int lane = tx & 63, wx0 = x0 + (tx & ~63);
@@ -392,19 +233,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     int c0 = (x0 - k) % nx;                                      // first column in reach, circular
     if (c0 < 0) c0 += nx;
     // ---- staging ----
-    {
-        const int yt = rowok ? yy : ny - 1;
-        const T phit = phi[yt];
-        if (tx <= 2 * k) {
-            int ys = yt + tx - k;
-            ys = ys < 0 ? 0 : (ys >= ny ? ny - 1 : ys);
-            const T phis = phi[ys];
-            const T dphi = phis - phit;                          // phi1(i) - phi1(yy)
-            const T sp = sin(dphi / T(2));
-            s_sp2a[ty][tx] = sp * sp;
-            s_cospa[ty][tx] = cos(phis);
-        } else if (tx == 2 * k + 1) s_costa[ty] = cos(phit);
-    }
+    sb_stage_lat(phi, ny, rowok ? yy : ny - 1, k, tx, s_sp2a[ty], s_cospa[ty], &s_costa[ty]);
     for (int i = tid; i < (L + DIST_ROWS - 1) * DIST_WORDS; i += 256 * DIST_ROWS) {
         const int r = i / DIST_WORDS, j = i - r * DIST_WORDS;
         const int ys = y0 + r - k;
@@ -433,35 +262,25 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     const T *s_sp2 = s_sp2a[ty], *s_cosp = s_cospa[ty];
     const T s_cost = s_costa[ty];
     const uint64_t (*s_bwt)[DIST_WORDS] = s_bw + ty;             // row ii of this target: s_bwt[ii + k]
-    const T R = T(6370.9989);                                   // ref: sobel.f90:115
+    // sb_dist_walk's walk (sb_coast_common.hpp: the window's bits, the sine of the longitude term, the stops), written out
+    // here: through the function template this kernel's code comes out 2 to 9 instructions longer and get_dist with the
+    // automatic window 2.0 % slower at 2560 x 1920 fp64, 1.2 % at 5120 x 3840 fp32 (profiles/coast_common_ab.json)
     const T cost = s_cost;
-    // fp64: sin((l1 - l2) / 2) = sin(l1/2) cos(l2/2) - cos(l1/2) sin(l2/2) from the per-column tables: two products and
-    // a difference per hit where the library sine took some eighty instructions.  The difference of products carries an
-    // absolute error of 1e-16, i.e. <= 4e-13 relative in the distance at the finest spacing in use (0.07 degrees); the
-    // tests hold 1e-12.  fp32 keeps the sine: there the same identity would cost four digits.
     const int t = tx;                                            // this target's window starts at bit t of the rows' bit strings
     const T ta_t = s_ta[t + k], tb_t = sizeof(T) == 8 ? s_tb[t + k] : T(0);
     int start = c0 + t;                                          // first window column, circular
     start -= start >= nx ? nx : 0;
-    // window bit b is column xx - k + b: bits 0 .. k lie left of or at the target, the rest right of it;
-    // bits below k - xx and from nx - xx + k on have wrapped round the seam
     const WB one = 1;
     const WB left = (WB)((WB)(one << k) << 1) - one;
     const WB wrapl = (k - xx > 0) ? (WB)(one << (k - xx)) - one : (WB)0;
     const WB wrapr = (nx - xx + k < (int)(8 * sizeof(WB))) ? (WB)((WB)~(WB)0 << (nx - xx + k)) : (WB)0;
     const WB lmask = (WB)(((uint64_t)1 << L) - 1ull);
     const int tw = t >> 6, to = t & 63;
-    auto topb = [](WB x) -> WB {
-        if constexpr (sizeof(WB) == 8) return (WB)top_bit((uint64_t)x);
-        else return x ? (WB)(1u << (31 - __builtin_clz((unsigned)x))) : (WB)0;
+    T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
+    auto sinl = [&](int b, int) -> T {
+        if constexpr (sizeof(T) == 8) return s_ta[t + b] * tb_t - s_tb[t + b] * ta_t;
+        else return sin((s_ta[t + b] - ta_t) / T(2));
     };
-    auto lowb = [](WB x) -> WB { return (WB)(x & ((WB)0 - x)); };
-    auto ctzw = [](WB x) -> int {
-        if constexpr (sizeof(WB) == 8) return __builtin_ctzll((uint64_t)x);
-        else return __builtin_ctz((unsigned)x);
-    };
-    const T none = T(4);                                         // a <= 1: "no source in this class"
-    T a_early = none, a_late = none;
     auto row = [&](int ii) {
         const int ys = yy + ii;
         uint64_t w64 = s_bwt[ii + k][tw] >> to;
@@ -470,33 +289,22 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
         if (!wb) return;
         if (nearest) {
             const WB wl = wb & left, wr = wb & (WB)~left;
-            if (ii != 0) wb = topb(wl) | lowb(wr);
-            else wb = topb(wl & (WB)~wrapl) | topb(wl & wrapl) | lowb(wr & (WB)~wrapr) | lowb(wr & wrapr);
+            if (ii != 0) wb = top_bit<WB>(wl) | low_bit<WB>(wr);
+            else wb = top_bit<WB>(wl & (WB)~wrapl) | top_bit<WB>(wl & wrapl) | low_bit<WB>(wr & (WB)~wrapr) | low_bit<WB>(wr & wrapr);
         }
         const T sp2 = s_sp2[ii + k], cosp = s_cosp[ii + k];
         while (wb) {
-            const int b = ctzw(wb);
+            const int b = low_idx<WB>(wb);
             wb &= (WB)(wb - one);
             int xs = start + b;
             if (xs >= nx) xs -= nx;
-            T sl;
-            // (two rounded products, no fma: for the target's own column they are the same product and the difference
-            // is exactly zero -- a coast cell's own distance stays exactly 0.5 km, SURVEY.md section 4's anchor)
-            if constexpr (sizeof(T) == 8) sl = s_ta[t + b] * tb_t - s_tb[t + b] * ta_t;
-            else {
-                const T dlam = s_ta[t + b] - ta_t;               // l1 - l2
-                sl = sin(dlam / T(2));
-            }
-            const T a = sp2 + (cosp * (cost * (sl * sl)));       // ref: sobel.f90:176
+            const T sl = sinl(b, xs);
+            const T a = sb_hav(sp2, cosp, cost, sl);
             const bool early = (ys < yy) || (ys == yy && xs <= xx);
             if (early) a_early = a < a_early ? a : a_early;
             else a_late = a < a_late ? a : a_late;
         }
     };
-    // Rows above the target are swept before it, rows below after it.  a >= sp2 of its row, and with latitudes
-    // that step one way (the host's condition for `nearest`) sp2 grows with the row distance: a walk away
-    // from the target can stop at the first row whose sp2 is no smaller than the class's minimum so far.  Only rows
-    // whose bit is set in the wave's row mask are visited (scalar bit scans: the mask is wave-uniform).
     if ((rowmask >> k) & 1) row(0);
     for (WB m = (WB)(rowmask & ((1ull << k) - 1ull)); m;) {      // rows above, nearest first
         const int idx = (int)(8 * sizeof(WB)) - 1 - (sizeof(WB) == 8 ? __builtin_clzll((uint64_t)m) : __builtin_clz((unsigned)m));
@@ -505,42 +313,13 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
         row(idx - k);
     }
     for (WB m = (WB)(rowmask >> (k + 1)); m;) {                  // rows below, nearest first
-        const int d = ctzw(m) + 1;
+        const int d = low_idx<WB>(m) + 1;
         m &= (WB)(m - one);
         if (nearest && !(s_sp2[k + d] < a_late)) break;
         row(d);
     }
-    // The distance grows with a, so of the two classes' distances only the smaller a's is needed -- one atan2 for the
-    // whole wave -- unless it is the early class's and the sweep-time reset (ref: sobel.f90:188) throws it away: then,
-    // rarely, the late class's as well.
-    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref :177
-    // atan2(sqrt(a), sqrt(1 - a)) = asin(sqrt(a)) = sqrt(a) (1 + a/6 + 3a^2/40 + 15a^3/336 + 105a^4/3456 + 945a^5/42240 + ...):
-    // for a < 2^-10 (distances below 400 km: every hit of a maxdist = 180 km window) five terms are exact to 1e-20
-    // relative, and the result is within two or three units in the last place of the library's atan2 of the two rounded
-    // roots (the tests hold 1e-12) -- for a fifth of the instructions.  a = 0 gives exactly 0.5 km either way.
-    auto dist_small = [&](T a) {
-        const double ad = (double)a;
-        double pl = __builtin_fma(ad, 945.0 / 42240.0, 105.0 / 3456.0);
-        pl = __builtin_fma(pl, ad, 15.0 / 336.0);
-        pl = __builtin_fma(pl, ad, 3.0 / 40.0);
-        pl = __builtin_fma(pl, ad, 1.0 / 6.0);
-        pl = __builtin_fma(pl, ad, 1.0);
-        return (R * T(2)) * (T)(sqrt(ad) * pl) + T(0.5);
-    };
-    const bool late_wins = a_late < a_early;
-    const T a_sel = late_wins ? a_late : a_early;
-    T m = big;
-    if (sizeof(T) == 8 && __ballot(a_sel < none && a_sel >= T(0x1p-10)) == 0) {      // wave-uniform
-        if (a_sel < none) m = dist_small(a_sel);
-    } else if (a_sel < none) m = dist_of(a_sel);
-    const bool again = !late_wins && m > T(2) * maxdist;         // ref: sobel.f90:188 at sweep time
-    if (__ballot(again) != 0) {                                  // wave-uniform
-        const T m2 = a_late < none ? dist_of(a_late) : big;
-        if (again) m = m2;
-    }
     const size_t o = (size_t)yy * nx + xx;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
+    sb_dist_write(cdist + o, sb_dist_finish_wave(a_early, a_late, maxdist), mask + o);
 }
 
 // ------------------------------------------------------------------------------------
@@ -558,17 +337,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
 // with nothing in reach leaves before any trigonometry, min(a) per sweep class and one distance per cell, dist_small,
 // the exact zero of the own column's difference of products.
 //
-// `cuts` (host, sb_capi.hip) says what may be left out; each is exact:
-//   WIDE_CUT_CIRCLE  nearest hit per side in every row (k_dist_bits' rule: longitudes step one way round the whole
-//                    circle and the window spans less than half of it);
-//   WIDE_CUT_INNER   the same for a target whose window xx-k .. xx+k lies inside 0 .. nx-1: the steps j -> j+1, j < nx-1
-//                    (not the closing one) go one way and k of the largest stay below 170 degrees, so inside such a window
-//                    the angular separation grows with the column distance and stays below 180 degrees, where
-//                    sin^2(dlam/2) grows with it (the fold of longitudes beyond 180 shifts dlam by 2 pi: sin^2 does not
-//                    see it).  A regional grid's closing step of 300-odd degrees forbids WIDE_CUT_CIRCLE for every target
-//                    although only the windows within k of the frame's edge cross it;
-//   WIDE_CUT_ROWS    a >= sp^2, which grows with the row distance when latitudes step one way: a sweep class stops at
-//                    the first row that cannot lower its minimum.
+// `cuts` (SB_CUT_CIRCLE, _INNER, _ROWS: sb_dist_plan.hpp, sb_coast_common.hpp) says what may be left out, one by one.
 // Windows that may not be cut visit every hit; so does the own row of a window across the seam (xs <= xx is decided
 // on wrapped indices there, ref: sobel.f90:188).  With 2k+1 >= nx the window is the nx columns from xx-k on: every
 // column once (the reference's loop meets some twice, which changes no minimum).
@@ -578,28 +347,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
 #define WIDE_SLOTS (2 * WIDE_A + WIDE_ROWS)                      // rows resident in LDS: one per lane of a wave
 #define WIDE_SPAN (256 + 2 * SB_DIST_MAX_WINDOW)                 // columns a workgroup's 256 targets can reach
 #define WIDE_WORDS ((WIDE_SPAN + 63) / 64)
-#define WIDE_CUT_CIRCLE 2
-#define WIDE_CUT_INNER 4
-#define WIDE_CUT_ROWS 8
 static_assert(WIDE_SLOTS == 64 && WIDE_ROWS == 2, "k_dist_wide: a slot per lane, and the walk names both target rows");
-
-// 64 bits of a row of the plane from circular column p on (0 <= p < nx), round the seam as often as it takes
-__device__ __forceinline__ uint64_t circ_bits64(const uint64_t *__restrict__ rw, int p, int nx) {
-    uint64_t v = 0;
-    for (int f = 0; f < 64;) {
-        const int l = nx - p < 64 - f ? nx - p : 64 - f;
-        if (l == 64) {
-            const int w = p >> 6, o = p & 63;
-            v = rw[w] >> o;
-            if (o) v |= rw[w + 1] << (64 - o);
-            return v;
-        }
-        v |= row_bits(rw, p, l) << f;
-        f += l;
-        p = 0;
-    }
-    return v;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *__restrict__ bits, const T *__restrict__ mask,
@@ -614,15 +362,14 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
     const int x0 = blockIdx.x * 256, y0 = blockIdx.y * WIDE_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
     const bool active = xx < nx && yy < ny;                      // (every thread stays for the barriers)
-    const T big = T(12000.);
     const int span = 256 + 2 * k, nws = (span + 63) >> 6;
     int c0 = (x0 - k) % nx;                                      // first column in reach, circular
     if (c0 < 0) c0 += nx;
     const int t = tx, P = t + k;                                 // this target's window starts at bit t; its own column
     const int hi = t + (2 * k + 1 < nx ? 2 * k + 1 : nx) - 1;    // ... and ends at bit hi
     const bool inside = xx - k >= 0 && xx + k <= nx - 1;
-    const bool colcut = (cuts & WIDE_CUT_CIRCLE) || ((cuts & WIDE_CUT_INNER) && inside);
-    const bool rowcut = (cuts & WIDE_CUT_ROWS) != 0;
+    const bool colcut = (cuts & SB_CUT_CIRCLE) || ((cuts & SB_CUT_INNER) && inside);
+    const bool rowcut = (cuts & SB_CUT_ROWS) != 0;
     // slot s of pass j: the row of the plane it holds (may lie outside 0 .. ny-1), and its distance from the nearer
     // target row
     auto slot_row = [&](int s, int j) {
@@ -632,8 +379,7 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
     };
     auto slot_dist = [&](int s, int j) { return s < 2 * WIDE_A ? 1 + WIDE_A * j + (s < WIDE_A ? s : s - WIDE_A) : 0; };
 
-    const T none = T(4);                                         // a <= 1: "no source in this class"
-    T a_early = none, a_late = none;
+    T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
     T ta_t = T(0), tb_t = T(0), cost = T(0);
     bool stop_up = !active, stop_dn = !active;                   // this target's sweep class cannot improve any more
     bool tables = false;                                         // (workgroup-uniform)
@@ -707,7 +453,7 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
                     const T dlam = s_ta[q] - ta_t;               // l1 - l2
                     sl = sin(dlam / T(2));
                 }
-                const T a = sp2 + (cosp * (cost * (sl * sl)));   // ref: sobel.f90:176
+                const T a = sb_hav(sp2, cosp, cost, sl);
                 if (early) a_early = a < a_early ? a : a_early;
                 else a_late = a < a_late ? a : a_late;
             };
@@ -772,34 +518,11 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
                 row(s, d);
             }
     }
-    // One distance per cell, as in k_dist_bits: at the smaller a, unless that is the early class's and the sweep-time
-    // reset (ref: sobel.f90:188) throws it away; the series for a < 2^-10 (see there).
-    const T R = T(6370.9989);                                   // ref: sobel.f90:115
-    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref :177
-    auto dist_small = [&](T a) {
-        const double ad = (double)a;
-        double pl = __builtin_fma(ad, 945.0 / 42240.0, 105.0 / 3456.0);
-        pl = __builtin_fma(pl, ad, 15.0 / 336.0);
-        pl = __builtin_fma(pl, ad, 3.0 / 40.0);
-        pl = __builtin_fma(pl, ad, 1.0 / 6.0);
-        pl = __builtin_fma(pl, ad, 1.0);
-        return (R * T(2)) * (T)(sqrt(ad) * pl) + T(0.5);
-    };
-    const bool late_wins = a_late < a_early;
-    const T a_sel = late_wins ? a_late : a_early;
-    T m = big;
-    if (sizeof(T) == 8 && __ballot(a_sel < none && a_sel >= T(0x1p-10)) == 0) {      // wave-uniform
-        if (a_sel < none) m = dist_small(a_sel);
-    } else if (a_sel < none) m = dist_of(a_sel);
-    const bool again = !late_wins && m > T(2) * maxdist;         // ref: sobel.f90:188 at sweep time
-    if (__ballot(again) != 0) {                                  // wave-uniform
-        const T m2 = a_late < none ? dist_of(a_late) : big;
-        if (again) m = m2;
-    }
+    // One distance per cell, as in k_dist_bits.
+    const T m = sb_dist_finish_wave(a_early, a_late, maxdist);
     if (!active) return;
     const size_t o = (size_t)yy * nx + xx;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (mask[o] > T(0)) ? m : -m;                   // ref :179-183
+    sb_dist_write(cdist + o, m, mask + o);
 }
 
 template <typename T>
@@ -813,33 +536,31 @@ hipError_t sb_launch_edges(const T *lsm, const T *ci, T *coast, int nx, int ny, 
 template <typename T>
 hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
                           int nx, int ny, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st) {
-    const int nearest = cuts & 1;
-    if (bits && k >= 32) {                                       // any nx >= 1; the C ABI holds k <= SB_DIST_MAX_WINDOW
-        if (k > SB_DIST_MAX_WINDOW) return hipErrorInvalidValue;
-        const int nw = (nx + 63) / 64;
-        hipLaunchKernelGGL(k_coastbits<T>, dim3((nx + 255) / 256, (ny + COASTBITS_ROWS - 1) / COASTBITS_ROWS), dim3(256), 0, st, coast, bits, nx, ny, nw);
+    if (k > SB_DIST_MAX_WINDOW || !bits) return hipErrorInvalidValue;    // (the C ABI holds k <= SB_DIST_MAX_WINDOW)
+    const SbDistKernel kern = sb_dist_kernel(nx, k);
+    const int nw = (nx + 63) / 64, nearest = cuts & SB_CUT_NEAREST;
+    if (kern != SbDistKernel::BYTES) sb_launch_coastbits<T>(coast, bits, nx, ny, nw, nx, 0, st);
+    const dim3 gr((nx + 255) / 256, (ny + DIST_ROWS - 1) / DIST_ROWS), bl(256, DIST_ROWS);
+    switch (kern) {
+    case SbDistKernel::BYTES:
+        hipLaunchKernelGGL(k_dist<T>, dim3((nx + 63) / 64, (ny + SB_DIST_TY - 1) / SB_DIST_TY), dim3(256),
+                           (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k), st, coast, mask, phi, lamf, cdist, nx, ny, k, maxdist);
+        break;
+    case SbDistKernel::BITS_SMALL:
+        hipLaunchKernelGGL(k_dist_bits_small<T>, dim3((nx + 255) / 256, ny), dim3(256), 0, st, bits, mask, phi, lamf, shl, chl, cdist,
+                           nx, ny, nw, k, maxdist, nearest);
+        break;
+    case SbDistKernel::BITS32:
+        hipLaunchKernelGGL((k_dist_bits<T, uint32_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
+        break;
+    case SbDistKernel::BITS64:
+        hipLaunchKernelGGL((k_dist_bits<T, uint64_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
+        break;
+    case SbDistKernel::WIDE:
         hipLaunchKernelGGL(k_dist_wide<T>, dim3((nx + 255) / 256, (ny + WIDE_ROWS - 1) / WIDE_ROWS), dim3(256, WIDE_ROWS), 0, st, bits, mask,
                            phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, cuts);
-        return hipGetLastError();
+        break;
     }
-    if (bits && k <= 31 && 2 * k + 1 <= nx) {
-        const int nw = (nx + 63) / 64;
-        hipLaunchKernelGGL(k_coastbits<T>, dim3((nx + 255) / 256, (ny + COASTBITS_ROWS - 1) / COASTBITS_ROWS), dim3(256), 0, st, coast, bits, nx, ny, nw);
-        if (2 * k + 1 + 256 <= nx)
-        {
-            const dim3 gr((nx + 255) / 256, (ny + DIST_ROWS - 1) / DIST_ROWS), bl(256, DIST_ROWS);
-            if (k <= 15) hipLaunchKernelGGL((k_dist_bits<T, uint32_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
-            else hipLaunchKernelGGL((k_dist_bits<T, uint64_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
-        }
-        else
-            hipLaunchKernelGGL(k_dist_bits_small<T>, dim3((nx + 255) / 256, ny), dim3(256), 0, st, bits, mask, phi, lamf, shl, chl, cdist,
-                               nx, ny, nw, k, maxdist, nearest);
-        return hipGetLastError();
-    }
-    const size_t lds = (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k);   // (k <= 31 with 2k + 1 > nx, or no workspace)
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dist<T>, dim3((nx + 63) / 64, (ny + SB_DIST_TY - 1) / SB_DIST_TY), dim3(256), lds, st, coast, mask,
-                       phi, lamf, cdist, nx, ny, k, maxdist);
     return hipGetLastError();
 }
 

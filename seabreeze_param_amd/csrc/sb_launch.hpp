@@ -2,6 +2,7 @@
 #pragma once
 #include "sb_device.hpp"
 #include "sb_diag_plan.hpp"
+#include "sb_dist_plan.hpp"
 
 #define SB_STATS_MAX_BLOCKS 2048
 #define SB_DIST_TY 4                // rows per k_dist tile
@@ -122,22 +123,17 @@ template <typename T>
 hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *lamf,
                           const T *shl, const T *chl,         // sin, cos of half the folded longitudes (k_dist_bits, fp64)
                           T *cdist, int nx, int ny,
-                          int k, T maxdist, uint64_t *bits,   // bits: ny*ceil(nx/64) words of workspace, or nullptr
-                          int cuts,                           // bit 0: nearest hit per side of a source row only (see k_dist_bits);
-                                                              // bits 1-3: k_dist_wide's WIDE_CUT_CIRCLE, _INNER, _ROWS (k >= 32)
+                          int k, T maxdist, uint64_t *bits,   // bits: ny*ceil(nx/64) words of workspace
+                          int cuts,                           // SB_CUT_* (sb_dist_plan.hpp); the kernel: sb_dist_kernel(nx, k)
                           hipStream_t st);
 
 // the UM vn10.7 copy's coast setup on the tdims_l layout (sb_um_coast_kernels.hip): lf, ci, coast are
 // (nx + 2hi) x (ny + 2hj) with hi, hj >= 1; coast's interior is written, its ghost cells are not
 template <typename T>
 hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st);
-// coast, cdist: (nx + 2hi) x (ny + 2hj), 0 <= hi, hj <= 31, cdist may be coast; landfrac, tlat, tlon: nx x ny (degrees);
-// bits: ny * ceil(nx/64) words of workspace
-template <typename T>
-hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
-                             int hi, int hj, T maxdist, uint64_t *bits, hipStream_t st);
-// the same with the window +-wi x +-wj (0 .. SB_DIST_UM_MAX_WINDOW) apart from the layout's ghost width hi, hj >= 0:
-// k_dist_um where wi == hi <= 31 and wj == hj <= 31, k_dist_um_wide otherwise
+// coast, cdist: (nx + 2hi) x (ny + 2hj), hi, hj >= 0, cdist may be coast; landfrac, tlat, tlon: nx x ny (degrees);
+// bits: ny * ceil(nx/64) words of workspace.  The window is +-wi x +-wj (0 .. SB_DIST_UM_MAX_WINDOW), stated apart from
+// the layout's ghost width: k_dist_um where wi == hi <= 31 and wj == hj <= 31, k_dist_um_wide otherwise
 template <typename T>
 hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                                  int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st);

@@ -3,7 +3,7 @@
 //   k_edges_um     binary 3x3 Sobel of the ice-aware land mask on the tdims_l layout: the rule is applied to the
 //                  interior and the one-cell ring of ghost cells round it (what swap_bounds filled), 0/1 goes into the
 //                  interior only                          ref: UM/vn10.7/sea_breeze_diag.F90:386-440 (get_edges)
-//   k_coastbits_um coast > 0 of the interior, one 64-bit word per 64 columns (a wave ballot)
+//   k_coastbits    (sb_coast_common.hpp) coast > 0 of the interior, one 64-bit word per 64 columns (a wave ballot)
 //   k_dist_um      signed haversine distance to the nearest interior coast cell within +-halo_i columns x +-halo_j
 //                  rows, from per-cell coordinates     ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)
 //   k_dist_um_wide the same rule for a window of up to +-255 cells stated apart from the ghost width (sb_get_dist_um_win_*)
@@ -15,94 +15,35 @@
 // over sources swept after it, as k_dist does (sb_coast_kernels.hip).
 #include "../../include/seabreeze_hip.h"
 #include "sb_launch.hpp"
+#include "sb_coast_common.hpp"
 
+// k_edges_um's layout: the interior offset by (hi, hj) inside the ghost-celled field of NX x NY cells.  The ring cells are
+// ghost cells of the caller; cells past the ring are clamped into the field (their flags are never read for a written
+// cell).
 template <typename T>
-__device__ __forceinline__ int land_rule_um(T l, T c) {
-    if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
-    return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
-}
+struct EdgesUm {
+    static constexpr bool tail_by_index = true;
+    int NX, NY, hi, hj;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X = x + hi, Y = y + hj;
+        X = X < NX ? X : NX - 1;
+        Y = Y < NY ? Y : NY - 1;
+        return (size_t)Y * NX + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + hj) * NX + x + hi; }
+    __device__ __forceinline__ int land(T l, T c) const {
+        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
+        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
+    }
+};
 
-// k_edges' block scheme (256 columns x UM_EDGE_ROWS rows per workgroup, land flags of the block and its ring in LDS),
-// with the interior offset by (hi, hj) inside the ghost-celled field.  The ring cells are ghost cells of the caller.
-#define UM_EDGE_ROWS 16
-#define UM_EDGE_PITCH 264
 template <typename T>
 __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, const T *__restrict__ ci, T *__restrict__ coast,
                                                   int nx, int ny, int hi, int hj) {
-    __shared__ unsigned char s_land[(UM_EDGE_ROWS + 2) * UM_EDGE_PITCH];
-    const int NX = nx + 2 * hi, NY = ny + 2 * hj;
-    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * UM_EDGE_ROWS;
-    constexpr int NCELL = (UM_EDGE_ROWS + 2) * 258, NIT = (NCELL + 255) / 256;
-    T l[NIT], c[NIT];
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {                      // every load issued before the first is used
-        const int i = threadIdx.x + 256 * j, r = i < NCELL ? i / 258 : 0, cc = i - (i / 258) * 258;
-        // field column / row of interior cell (x0 - 1 + cc, y0 - 1 + r); cells past the ring are clamped into the
-        // field (their flags are never read for a written cell)
-        int X = x0 - 1 + cc + hi, Y = y0 - 1 + r + hj;
-        X = X < NX ? X : NX - 1;
-        Y = Y < NY ? Y : NY - 1;
-        const size_t o = (size_t)Y * NX + X;
-        l[j] = lf[o];
-        c[j] = ci[o];
-    }
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {
-        const int i = threadIdx.x + 256 * j, r = i / 258, cc = i - r * 258;
-        if (i < NCELL) s_land[r * UM_EDGE_PITCH + cc] = (unsigned char)land_rule_um(l[j], c[j]);
-    }
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    if (x >= nx) return;
-    // the Sobel of k_edges: px = sum_a (1,2,1)(a) * (m[a][2] - m[a][0]), py = sum_b (1,2,1)(b) * (m[2][b] - m[0][b])
-    // (ref: UM :420-427 with weight = reshape((/-1,-2,-1, 0,0,0, 1,2,1/),(3,3)))
-    int m[3][3];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) m[a + 1][b] = s_land[a * UM_EDGE_PITCH + threadIdx.x + b];
-#pragma unroll
-    for (int r = 0; r < UM_EDGE_ROWS; ++r) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            m[0][b] = m[1][b];
-            m[1][b] = m[2][b];
-            m[2][b] = s_land[(r + 2) * UM_EDGE_PITCH + threadIdx.x + b];
-        }
-        const int px = (m[0][2] - m[0][0]) + 2 * (m[1][2] - m[1][0]) + (m[2][2] - m[2][0]);
-        const int py = (m[2][0] - m[0][0]) + 2 * (m[2][1] - m[0][1]) + (m[2][2] - m[0][2]);
-        const int y = y0 + r;
-        if (y < ny) coast[(size_t)(y + hj) * NX + x + hi] = (px == 0 && py == 0) ? T(0) : T(1);   // ref: UM :429-435
-    }
+    __shared__ unsigned char s_land[EDGE_LDS];
+    sb_edges_block(lf, ci, coast, s_land, nx, ny, EdgesUm<T>{nx + 2 * hi, ny + 2 * hj, hi, hj});   // ref: UM :420-435
 }
 
-// coast > 0 of the interior, one word per 64 columns of a row (bits past nx are zero)
-#define UM_BITS_ROWS 8
-template <typename T>
-__global__ __launch_bounds__(256) void k_coastbits_um(const T *__restrict__ coast, uint64_t *__restrict__ bits,
-                                                      int nx, int ny, int hi, int hj, int nw) {
-    const int NX = nx + 2 * hi;
-    const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * UM_BITS_ROWS;
-    T v[UM_BITS_ROWS];
-#pragma unroll
-    for (int r = 0; r < UM_BITS_ROWS; ++r) {
-        const int y = y0 + r < ny ? y0 + r : ny - 1;                 // (clamped: every load unconditional)
-        v[r] = coast[(size_t)(y + hj) * NX + (x < nx ? x : nx - 1) + hi];
-    }
-#pragma unroll
-    for (int r = 0; r < UM_BITS_ROWS; ++r) {
-        const uint64_t w = __ballot(x < nx && v[r] > T(0));          // ref: UM :551
-        if ((threadIdx.x & 63) == 0 && (x >> 6) < nw && y0 + r < ny) bits[(size_t)(y0 + r) * nw + (x >> 6)] = w;
-    }
-}
-
-// 64 bits of row `rw` of the plane from column p on (p may be negative; columns outside 0 .. 64*nw - 1 read as 0)
-__device__ __forceinline__ uint64_t um_row_bits64(const uint64_t *__restrict__ rw, int p, int nw) {
-    const int w0 = p >= 0 ? p >> 6 : -((63 - p) >> 6), o = p - 64 * w0;      // floor division
-    const uint64_t a = (w0 >= 0 && w0 < nw) ? rw[w0] : 0ull;
-    const uint64_t b = (w0 + 1 >= 0 && w0 + 1 < nw) ? rw[w0 + 1] : 0ull;
-    return o ? (a >> o) | (b << (64 - o)) : a;
-}
 
 // The gather.  A workgroup holds UM_DIST_TY target rows of 64 columns (one wave per row).  Its reach is the
 // (64 + 2hi) x (UM_DIST_TY + 2hj) cells round them; every reach row is one 128-bit string of coast bits in LDS, starting at
@@ -140,7 +81,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
     const bool valid = xx < nx && yy < ny;
     const int NX = nx + 2 * hi;
     const int RR = UM_DIST_TY + 2 * hj, W = 64 + 2 * hi, L = 2 * hi + 1;
-    const T big = T(12000.);
+    const T big = SbDist<T>::big;
     // ---- the coast bits of the reach, and which reach rows hold any ----
     bool any = false;
     for (int i = tid; i < 2 * RR; i += 64 * UM_DIST_TY) {
@@ -159,7 +100,6 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
     }
     // ---- this target's own terms ----
     const T pi = T(3.1415926), r2d = T(180.0) / pi, d2r = pi / T(180.0);      // ref: UM :509-512
-    const T R = T(6370.9989);
     T phit = T(0), cost = T(0), sht = T(0), cht = T(0), l2 = T(0), lf = T(0);
     if (valid) {
         const size_t o = (size_t)yy * nx + xx;
@@ -170,8 +110,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
         if constexpr (sizeof(T) == 8) { sht = sin(phit / T(2)); cht = cos(phit / T(2)); }
         lf = landfrac[o];
     }
-    const T none = T(4);                                           // a <= 1: "no source in this class"
-    T a_early = none, a_late = none;
+    T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
     const uint64_t lmask = (1ull << L) - 1ull;                     // (L <= 63)
     // ---- UM_DIST_CH reach rows at a time: stage the coast cells' terms, then every wave walks the rows of its window ----
     for (int r0 = 0; r0 < RR; r0 += UM_DIST_CH) {
@@ -210,7 +149,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
                 else sp = sin((s_sh[rc][cc] - phit) / T(2));
                 const T dlam = s_l1[rc][cc] - l2;                  // l1 - l2 (ref: UM :565)
                 const T sl = sin(dlam / T(2));
-                const T a = sp * sp + (s_cp[rc][cc] * (cost * (sl * sl)));    // ref: UM :566
+                const T a = sb_hav(sp * sp, s_cp[rc][cc], cost, sl);
                 const bool early = ii < 0 || (ii == 0 && b <= hi);
                 if (early) a_early = a < a_early ? a : a_early;
                 else a_late = a < a_late ? a : a_late;
@@ -218,14 +157,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
         }
     }
     if (!valid) return;
-    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref: UM :567
-    T m_early = a_early < none ? dist_of(a_early) : big;
-    const T m_late = a_late < none ? dist_of(a_late) : big;
-    if (m_early > T(2) * maxdist) m_early = big;                   // ref: UM :578 at the target's sweep position
-    const T m = m_early < m_late ? m_early : m_late;
-    const size_t o = (size_t)(yy + hj) * NX + xx + hi;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (lf > T(0)) ? m : -m;                          // ref: UM :568-574
+    sb_dist_write(cdist + (size_t)(yy + hj) * NX + xx + hi, sb_dist_finish_both(a_early, a_late, maxdist), &lf);
 }
 
 // ------------------------------------------------------------------------------------
@@ -297,9 +229,7 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__
     const int W = 64 + 2 * wi, nws = (W + 63) >> 6;              // the reach: W columns from x0 - wi on, nws <= UMW_WORDS words
     const uint64_t lastmask = (W & 63) ? (1ull << (W & 63)) - 1ull : ~0ull;
     const int qlo = tx, qhi = tx + 2 * wi, qown = tx + wi;       // this target's window in the strings, its own column
-    const T big = T(12000.);
     const T pi = T(3.1415926), r2d = T(180.0) / pi, d2r = pi / T(180.0);      // ref: UM :509-512
-    const T R = T(6370.9989);
     // slot s of pass j: the distance of its row from the block of target rows (0: a target row) and the row itself
     // (which may lie outside 0 .. ny-1)
     auto slot_k = [&](int s, int j) { return j == 0 ? (s < UMW_TY ? 0 : 1 + ((s - UMW_TY) >> 1)) : 1 + UMW_A * j + (s >> 1); };
@@ -308,8 +238,7 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__
         const int k = slot_k(s, j), below = (j == 0 ? s - UMW_TY : s) & 1;
         return below ? y0 + UMW_TY - 1 + k : y0 - k;
     };
-    const T none = T(4);                                         // a <= 1: "no source in this class"
-    T a_early = none, a_late = none;
+    T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
     T phit = T(0), cost = T(0), l2 = T(0);
     bool have = false;                                           // this target's own terms are loaded (workgroup-uniform)
     const int npass = wj == 0 ? 1 : (wj + UMW_A - 1) / UMW_A;
@@ -403,7 +332,7 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__
 #endif
                             const T dlam = s_l1[e] - l2;         // l1 - l2 (ref: UM :565)
                             const T sl = um_sin_as_written<T>(dlam / T(2));
-                            const T a = sp2 + (cps * (cost * (sl * sl)));     // ref: UM :566
+                            const T a = sb_hav(sp2, cps, cost, sl);
                             if (early) a_early = a < a_early ? a : a_early;
                             else a_late = a < a_late ? a : a_late;
                         }
@@ -413,33 +342,14 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__
         }
     }
     if (!valid) return;
-    auto dist_of = [&](T a) { return (R * T(2)) * atan2(sqrt(a), sqrt(T(1) - a)) + T(0.5); };   // ref: UM :567
-    T m_early = a_early < none ? dist_of(a_early) : big;
-    const T m_late = a_late < none ? dist_of(a_late) : big;
-    if (m_early > T(2) * maxdist) m_early = big;                 // ref: UM :578 at the target's sweep position
-    const T m = m_early < m_late ? m_early : m_late;
-    const size_t o = (size_t)(yy + hj) * NX + xx + hi;
-    if (m >= big) cdist[o] = big;
-    else cdist[o] = (landfrac[(size_t)yy * nx + xx] > T(0)) ? m : -m;       // ref: UM :568-574
+    sb_dist_write(cdist + (size_t)(yy + hj) * NX + xx + hi, sb_dist_finish_both(a_early, a_late, maxdist),
+                  landfrac + (size_t)yy * nx + xx);
 }
 
 template <typename T>
 hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st) {
-    hipLaunchKernelGGL(k_edges_um<T>, dim3((nx + 255) / 256, (ny + UM_EDGE_ROWS - 1) / UM_EDGE_ROWS), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_edges_um<T>, dim3((nx + 255) / 256, (ny + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st,
                        lf, ci, coast, nx, ny, hi, hj);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t sb_launch_dist_um(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
-                             int hi, int hj, T maxdist, uint64_t *bits, hipStream_t st) {
-    if (hi < 0 || hi > 31 || hj < 0 || hj > 31) return hipErrorInvalidValue;
-    const int nw = (nx + 63) / 64;
-    // (two launches: the bit plane is complete before any cdist cell is written, so cdist may be coast)
-    hipLaunchKernelGGL(k_coastbits_um<T>, dim3((nx + 255) / 256, (ny + UM_BITS_ROWS - 1) / UM_BITS_ROWS), dim3(256), 0, st,
-                       coast, bits, nx, ny, hi, hj, nw);
-    hipLaunchKernelGGL(k_dist_um<T>, dim3((nx + 63) / 64, (ny + UM_DIST_TY - 1) / UM_DIST_TY), dim3(64 * UM_DIST_TY), 0, st,
-                       bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, nw, maxdist);
     return hipGetLastError();
 }
 
@@ -447,23 +357,22 @@ template <typename T>
 hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                                  int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st) {
     if (hi < 0 || hj < 0 || wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
+    const int nw = (nx + 63) / 64, NX = nx + 2 * hi;
+    // (two launches: the bit plane is complete before any cdist cell is written, so cdist may be coast)
+    sb_launch_coastbits<T>(coast, bits, nx, ny, nw, NX, (size_t)hj * NX + hi, st);
     // window = ghost width <= 31: sb_get_dist_um_*'s call, its kernel and its field, bit for bit
     if (wi == hi && wj == hj && wi <= 31 && wj <= 31)
-        return sb_launch_dist_um<T>(coast, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, maxdist, bits, st);
-    const int nw = (nx + 63) / 64;
-    hipLaunchKernelGGL(k_coastbits_um<T>, dim3((nx + 255) / 256, (ny + UM_BITS_ROWS - 1) / UM_BITS_ROWS), dim3(256), 0, st,
-                       coast, bits, nx, ny, hi, hj, nw);
-    hipLaunchKernelGGL(k_dist_um_wide<T>, dim3((nx + 63) / 64, (ny + UMW_TY - 1) / UMW_TY), dim3(64 * UMW_TY), 0, st,
-                       bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist);
+        hipLaunchKernelGGL(k_dist_um<T>, dim3((nx + 63) / 64, (ny + UM_DIST_TY - 1) / UM_DIST_TY), dim3(64 * UM_DIST_TY), 0, st,
+                           bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, nw, maxdist);
+    else
+        hipLaunchKernelGGL(k_dist_um_wide<T>, dim3((nx + 63) / 64, (ny + UMW_TY - 1) / UMW_TY), dim3(64 * UMW_TY), 0, st,
+                           bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist);
     return hipGetLastError();
 }
 
 template hipError_t sb_launch_edges_um<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges_um<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
-template hipError_t sb_launch_dist_um<float>(const float *, const float *, const float *, const float *, float *, int, int,
-                                             int, int, float, uint64_t *, hipStream_t);
-template hipError_t sb_launch_dist_um<double>(const double *, const double *, const double *, const double *, double *, int,
-                                              int, int, int, double, uint64_t *, hipStream_t);
+
 template hipError_t sb_launch_dist_um_win<float>(const float *, const float *, const float *, const float *, float *, int,
                                                  int, int, int, int, int, float, uint64_t *, hipStream_t);
 template hipError_t sb_launch_dist_um_win<double>(const double *, const double *, const double *, const double *, double *,

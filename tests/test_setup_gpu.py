@@ -91,7 +91,7 @@ def _every_hit_path(hipctx, orc, dt, lons, nx, ny, kwin):
 
 @pytest.mark.parametrize("kwin", [32, 40])
 def test_get_dist_wide_window_lds_kernel(hipctx, oracles, kwin):
-    """Windows wider than 63 columns do not fit the bit-plane kernel: k_dist (flags in LDS) takes over."""
+    """Windows wider than 63 columns do not fit one word of the bit-plane kernel: k_dist_wide takes over."""
     nx, ny = 192, 48
     dt, orc = np.float64, oracles[8]
     lon, lat = synth.grid(nx, ny)
