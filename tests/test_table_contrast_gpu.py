@@ -14,6 +14,7 @@ k_scan, k_prep, the row pass, the column pass, the query, k_wind: two table pass
 import numpy as np
 import pytest
 
+import table_ref as tr
 from conftest import relerr
 from oracle import fp32_criterion as crit
 from seabreeze_param_amd import hip, synth
@@ -27,24 +28,12 @@ NAMES = ("ws", "wd", "thc", "sb_con")
 f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
 
 
-def _close64(a, b, what):
-    """|a - b| <= 1e-7 max(|b|, 1e-2); NaN exactly where b has NaN"""
-    assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what}: NaN pattern differs"
-    e = relerr(a, b, floor=1e-2)
-    assert e < 1e-7, f"{what}: rel err {e}"
+_close64, _mask = tr.close64, tr.mask_of          # the rule and the mask: shared with tests/test_table_shapes_gpu.py
 
 
 def _block_land(nx, ny, w, dx=0, dy=0, x0=0, y0=0):
-    """the block on columns x0 .. x0 + nx - 1 and rows y0 .. y0 + ny - 1 of the plane (period NX along longitude; rows below
-    0 continue the block), moved by dx columns and dy rows (the rows it leaves are sea)"""
-    x = np.arange(x0, x0 + nx)[None, :] - dx
-    y = np.arange(y0, y0 + ny)[:, None] - dy
-    land = (((x - (NX - 40)) % NX) < w) & (y < w)
-    return land & (y >= 0) if dy else land
-
-
-def _mask(land, dt):
-    return np.where(land, 100.0, -100.0).astype(dt)
+    """table_ref.block_land on this grid's circle of NX columns"""
+    return tr.block_land(nx, ny, w, NX, dx=dx, dy=dy, x0=x0, y0=y0)
 
 
 def _zeros(n, dt, ny=NY, nx=NX):
