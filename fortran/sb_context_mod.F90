@@ -22,7 +22,7 @@ module sb_context_mod
   private
   public :: sb_ctx, sb_ensure_ctx, sb_fail, sb_release_ctx
   public :: sb_comm_get_unique_id, sb_comm_init, sb_comm_finalize, sb_comm_active, sb_comm_rank
-  public :: sb_set_static_sigma, sb_set_table_contrast, sb_last_step_report
+  public :: sb_set_static_sigma, sb_set_table_contrast, sb_set_table_window_cache, sb_last_step_report
   public :: sb_dev_alloc, sb_dev_free, sb_dev_upload, sb_dev_download, sb_device_synchronize
 
   type(c_ptr), save :: sb_ctx = c_null_ptr
@@ -65,6 +65,11 @@ module sb_context_mod
       integer(c_int), value :: on
     end function
     integer(c_int) function c_set_table_contrast(ctx, on) bind(C, name="sb_set_table_contrast")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function c_set_table_window_cache(ctx, on) bind(C, name="sb_set_table_window_cache")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
       integer(c_int), value :: on
@@ -210,6 +215,17 @@ contains
     rc = c_set_table_contrast(sb_ctx, merge(1_c_int, 0_c_int, on))
     if (rc /= 0) call sb_fail('sb_set_table_contrast', rc)
   end subroutine sb_set_table_contrast
+
+  !> Opt-in, with sb_set_table_contrast: a table call keeps every band cell's window (radius, land-side count) while the
+  !! coast stands -- k_scan finds a changed mask by content -- and later calls neither build nor search the count table.
+  !! The same bits as the table path.  include/seabreeze_hip.h: sb_set_table_window_cache.
+  subroutine sb_set_table_window_cache(on)
+    logical, intent(in) :: on
+    integer(c_int) :: rc
+    call sb_ensure_ctx()
+    rc = c_set_table_window_cache(sb_ctx, merge(1_c_int, 0_c_int, on))
+    if (rc /= 0) call sb_fail('sb_set_table_window_cache', rc)
+  end subroutine sb_set_table_window_cache
 
   !> What the last diag call / band step enqueued: kernel launches, RCCL operations, RCCL groups, device copies.
   subroutine sb_last_step_report(launches, rccl_ops, rccl_groups, copies)

@@ -139,6 +139,31 @@ int  sb_set_static_sigma(sb_ctx *ctx, int on);
    chosen automatically, whatever the radius hint.  sb_profile_end reports the row pass under [2] and the column pass
    and the query together under [3] for such calls.                                                                 */
 int  sb_set_table_contrast(sb_ctx *ctx, int on);
+/* Opt-in, off by default, for the table contrast above: keep every band cell's window while the coast stands.  The radius
+   of a cell's window and the land-side cells in it follow from the land-side plane (mask >= 0) and the geometry alone, and
+   mask -- the signed coast distance -- changes only when the host model's ice mask does.  A table call that searches
+   ("fills") leaves radius and count of every band cell in one more plane; the calls after it take them from there and
+   neither build nor read the count table: the two passes move 16 instead of 20 bytes per frame cell, the query one word
+   per band cell instead of a bisection.  Cells the tables do not answer are marked and take the global-memory path every
+   call, counted as ever.
+   Dropped: by content, on the device -- k_scan compares every word of the band plane and of the land-side plane with
+   what the call before left, and the first difference makes this call search again; nothing is stated by the caller, and
+   the host-pointer entry points are served like the device-pointer ones.  And by the host whenever the planes k_scan
+   compared with are not those of the stored windows: after any other diag call or band step on this context (the f2py
+   flavour, sb_diag_stream_*, a band step, a call with this switch or the table contrast off, another grid, boundary rule
+   or ghost width), after a failed launch, a reallocated workspace, and when this switch is set.  No synchronisation, no
+   further launch: six launches, as without it.
+   Results are those of the table path bit for bit, counters included, whether a call fills or not.
+   Workspace: 4 bytes per interior cell, grow-only, allocated with the tables while the switch is on.
+   Takes effect exactly where sb_set_table_contrast does; silently ignored wherever that is ignored and while it is off.
+   It is never chosen automatically.                                                                                  */
+int  sb_set_table_window_cache(sb_ctx *ctx, int on);
+/* [0] band cells of the last diag call that were answered from a stored window, [1] band cells of that call whose window
+   was searched (found or not); both 0 when that call did not run with the window cache in effect.  [2] calls whose
+   kernels searched, [3] calls that ran with the cache in effect, both since sb_set_table_window_cache(ctx, 1) last.
+   A call that failed counts as a call without the cache.  Synchronises the device, as sb_last_counters does (a diag
+   call may have been enqueued on a stream of the caller's).                                                         */
+int  sb_table_cache_report(sb_ctx *ctx, long long rep[4]);
 /* What the last diag call or band step enqueued on this rank: [0] kernel launches, [1] RCCL operations (sends,
    receives, all-gathers), [2] RCCL groups, [3] device-to-device copies.  No synchronisation.               */
 int  sb_last_step_report(sb_ctx *ctx, int report[4]);

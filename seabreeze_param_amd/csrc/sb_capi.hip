@@ -137,6 +137,14 @@ struct sb_ctx {
     int no_wide_strip = 0;              // sb_set_wide_strip(ctx, 0): radii beyond 16 take the tile kernel in single precision too
     int band_late_wind = 0;             // sb_set_band_order(ctx, 1): a band step runs the contrast before k_wind (measurement)
     int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
+    // sb_set_table_window_cache(ctx, 1): a table call keeps every band cell's window in W while the coast stands.  tabc: what
+    // the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half (sb_table_cache_report)
+    int table_cache = 0;
+    SbTabCache tabc;
+    bool tab_rep_reset = true;          // no call has run with the cache in effect since the switch was turned on
+    bool tab_last = false;              // the last diag call ran with the cache in effect
+    long long tab_calls = 0;            // such calls since the switch was turned on
+    int tab_waves = 0;                  // waves of the last such call's query: the slots of the report it wrote
     const void *stats_sigma = nullptr;
     int stats_dims[4] = {0, 0, 0, 0};   // nx, ny, halo, sizeof(T)
     int stats_ngathered = 0;            // bands whose moments the kept scalars were merged from (0: this domain's own)
@@ -146,6 +154,7 @@ struct sb_ctx {
     DevBuf t0, bandbits, clsbits, tiles, vecs, nws, nwd, coastbits, tile_list, seg_list, stamps, jobcopy, plan;
     DevBuf umbits;                      // the coast bit plane of sb_get_dist_um_*
     DevBuf tabA, tabL, tabC, tabS;      // the device-wide summed-area tables (SbTables), allocated by the first call that builds them
+    DevBuf tabW, tabRep;                // the stored windows and the report's device words, allocated with them while the cache is on
     // the strip kernel's plan (sb_strip_kernel.hip): [64 bytes: number of the last call whose band plane changed |
     // ncu x SB_PLAN_STRIDE]; plan_key: the geometry it was made for; call_seq numbers the diag calls
     int plan_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -254,6 +263,7 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     const size_t ncell = (size_t)g.nxh * g.nyh;
     const size_t nbits = (size_t)g.nyh * g.nw * sizeof(uint64_t);
     int rc;
+    c->tab_last = false;                // (sb_table_cache_report: until this call has been enqueued with the cache in effect)
     if ((rc = ensure(c, c->bandbits, nbits))) return rc;
     if ((rc = ensure(c, c->clsbits, nbits))) return rc;
     SbPlanIn in = plan_input<T>(c, g.nx, g.rows);
@@ -308,8 +318,12 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     }
     if ((rc = ensure(c, c->jobcopy, sizeof(DiagJob<double>)))) return rc;
     job.self = (DiagJob<T> *)c->jobcopy.p;
-    if (strip) {
-        const size_t need = 64 + (size_t)c->ncu * SB_PLAN_STRIDE;
+    // a table call that keeps its windows (sb_set_table_window_cache): as sb_plan_diag decides `table`, and the switch.  Its
+    // k_scan watches the planes whatever the contrast kernel of the domain would be: the header of the plan alone then
+    const bool cache = c->table_cache != 0 && c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC &&
+                       (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0 && phases == 3 && c->gathered == nullptr;
+    if (strip || cache) {
+        const size_t need = 64 + (strip ? (size_t)c->ncu * SB_PLAN_STRIDE : (size_t)0);
         if (c->plan.cap < need) {
             if ((rc = ensure(c, c->plan, need))) return rc;
             HIPCHK(c, hipMemsetAsync(c->plan.p, 0, need, st));   // no plan stored, no change seen (stream-ordered)
@@ -324,15 +338,17 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
                 c->plan_bits = nullptr;
             }
             ++c->call_seq;
-            const int key[8] = {g.nx, g.ny, g.h, g.bnd, g.rows, c->ncu, tx, ty | (vb << 24)};     // (the two strip kernels' plans differ)
-            c->plan_use = c->plan_bits == c->bandbits.p && std::memcmp(key, c->plan_key, sizeof(key)) == 0 ? 1 : 0;
-            std::memcpy(c->plan_key, key, sizeof(key));
-            c->plan_bits = c->bandbits.p;
+            if (strip) {
+                const int key[8] = {g.nx, g.ny, g.h, g.bnd, g.rows, c->ncu, tx, ty | (vb << 24)};     // (the two strip kernels' plans differ)
+                c->plan_use = c->plan_bits == c->bandbits.p && std::memcmp(key, c->plan_key, sizeof(key)) == 0 ? 1 : 0;
+                std::memcpy(c->plan_key, key, sizeof(key));
+                c->plan_bits = c->bandbits.p;
+            } else c->plan_bits = nullptr;                   // (as below: no strip kernel's plan follows from this call's planes)
         }
         job.plan = (char *)c->plan.p + 64;
         job.plan_gen = (int *)c->plan.p;
         job.call_id = c->call_seq;
-        job.plan_use = c->no_plan_cache ? 0 : c->plan_use;
+        job.plan_use = strip && !c->no_plan_cache ? c->plan_use : 0;
     } else if (phases & 1) c->plan_bits = nullptr;           // (the tile kernel rewrites nothing of the plan, but k_scan does not watch the plane for it)
 #ifdef SB_STAMPS
     if ((rc = ensure(c, c->stamps, (size_t)4096 * SB_NSTAMP * sizeof(long long)))) return rc;
@@ -365,6 +381,18 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         lc.tables.A = (unsigned long long *)c->tabA.p; lc.tables.L = (unsigned long long *)c->tabL.p; lc.tables.C = (unsigned *)c->tabC.p;
         lc.tables.SA = (unsigned long long *)c->tabS.p; lc.tables.SL = lc.tables.SA + nsum; lc.tables.SC = (unsigned *)(lc.tables.SL + nsum);
     }
+    // the stored windows: 4 bytes per interior cell.  Whether this call searches: the host's half here, the device's in the
+    // table kernels (sb_tab_fill) -- no synchronisation, no launch
+    SbTabKey tkey{};
+    if (plan.table && cache) {
+        if ((rc = ensure(c, c->tabW, (size_t)g.nx * g.ny * sizeof(unsigned)))) return rc;
+        if ((rc = ensure(c, c->tabRep, (SB_TAB_REP_HDR + (size_t)2 * SB_TAB_QUERY_WAVES_PER_CU * c->ncu_dev) * sizeof(unsigned)))) return rc;
+        tkey = SbTabKey{g.nx, g.ny, g.h, g.bnd, g.rows, c->bandbits.p, c->clsbits.p, c->tabW.p, c->tabC.p};
+        lc.tables.W = (unsigned *)c->tabW.p; lc.tables.rep = (unsigned *)c->tabRep.p;
+        lc.tables.gen = job.plan_gen; lc.tables.call_id = job.call_id;
+        lc.tables.force = sb_tab_cache_decide(c->tabc, tkey, job.call_id) != SB_TAB_STEADY ? 1 : 0;
+        lc.tables.rep_reset = c->tab_rep_reset ? 1 : 0;
+    }
     // this call's wind speed / direction at band cells, where k_wind runs ahead of the contrast (k_wind -> k_thc3)
     if (plan.wind_scratch) {
         if ((rc = ensure(c, c->nws, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
@@ -379,11 +407,21 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
             c->plan_bits = nullptr;
             c->segs_built = false;
             c->stats_valid = false;
+            sb_tab_cache_launch_failed(c->tabc);
         }
         if (le == hipErrorInvalidValue) return fail(c, SB_ERR_ARG, "no contrast kernel instance for this halo / tile shape");
         if (le != hipSuccess) return hipfail(c, le, "sb_launch_diag");
     }
     c->rep_launches += plan.nsteps;
+    // W belongs to the planes of the last call that ran with the cache in effect: any other call that ran k_scan on them
+    // (or a part of a band step) drops the key
+    if (lc.tables.W) {
+        sb_tab_cache_filled(c->tabc, tkey, job.call_id);
+        c->tab_rep_reset = false;
+        c->tab_waves = SB_TAB_QUERY_WAVES_PER_CU * c->ncu;
+        ++c->tab_calls;
+    } else sb_tab_cache_other_call(c->tabc);
+    c->tab_last = lc.tables.W != nullptr;
     if (!(phases & 2)) return SB_OK;          // the flag buffers swap when the call is complete
     c->segs_built = plan.segs_built;
     if (c->static_sigma && c->host_depth == 0 && !in.reuse_stats) {
@@ -1227,7 +1265,8 @@ int sb_destroy(sb_ctx *c) {
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
-                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS})
+                      &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS, &c->tabW,
+                      &c->tabRep})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -1803,6 +1842,28 @@ int sb_set_static_sigma(sb_ctx *c, int on) {
 int sb_set_table_contrast(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->table_contrast = on ? 1 : 0;
+    return SB_OK;
+}
+
+int sb_set_table_window_cache(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->table_cache = on ? 1 : 0;
+    sb_tab_cache_toggled(c->tabc);                   // (whatever W holds, the next call that uses it fills it)
+    if (on) { c->tab_rep_reset = true; c->tab_calls = 0; }
+    return SB_OK;
+}
+
+int sb_table_cache_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null pointer");
+    rep[0] = rep[1] = rep[2] = rep[3] = 0;
+    if (c->tab_rep_reset || !c->tabRep.p) return SB_OK;      // (no call with the cache in effect since the switch was turned on)
+    HIPCHK(c, hipDeviceSynchronize());
+    std::vector<unsigned> d(SB_TAB_REP_HDR + (size_t)2 * c->tab_waves);
+    HIPCHK(c, hipMemcpy(d.data(), c->tabRep.p, d.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (c->tab_last)
+        for (int w = 0; w < c->tab_waves; ++w) { rep[0] += d[SB_TAB_REP_HDR + 2 * w]; rep[1] += d[SB_TAB_REP_HDR + 2 * w + 1]; }
+    rep[2] = d[0]; rep[3] = c->tab_calls;
     return SB_OK;
 }
 

@@ -36,10 +36,24 @@
 #define SB_TAB_RB 16                // rows per workgroup of the row pass = rows of a block of S
 static_assert((2 * SB_TAB_REACH + 1) * (2 * SB_TAB_REACH + 1) < (1 << (63 - 11 - SB_TAB_FB)), "a window at the reach must fit 63 bits");
 static_assert((2 * SB_TAB_REACH + 3) * (2 * SB_TAB_REACH + 3) >= (1 << (63 - 11 - SB_TAB_FB)), "the reach is the largest the format holds");
+#include "sb_table_cache.hpp"
+// With sb_set_table_window_cache in effect (W != nullptr) a call whose planes stand builds A, L, SA and SL alone and takes
+// every band cell's window from W (sb_table_cache.hpp); the three kernels agree on that by one predicate over the same words:
+// force (the host's half) || *gen == call_id (k_scan of this call found a plane changed).  rep: device words of
+// sb_table_cache_report: [0] calls that searched (the row pass counts them); from SB_TAB_REP_HDR on two words per wave of
+// the query, the band cells of this call it answered from W and those it searched (every wave writes its own, the host
+// adds them up).
+#define SB_TAB_REP_HDR 2
+#define SB_TAB_QUERY_WAVES_PER_CU 16    // the query's grid: 4 workgroups of 4 waves per compute unit
 struct SbTables {
     unsigned long long *A, *L, *SA, *SL;
     unsigned *C, *SC;
+    unsigned *W;                    // nx * ny words, or nullptr: the cache is not in effect, C is built and searched every call
+    unsigned *rep;
+    const int *gen;                 // DiagJob::plan_gen
+    int call_id, force, rep_reset;  // rep_reset: the first such call since the switch was turned on, rep[0] starts over
 };
+__device__ __forceinline__ bool sb_tab_fill(const SbTables &tb) { return !tb.W || tb.force || *tb.gen == tb.call_id; }
 
 // Everything of the context a diag launch needs besides the job itself.
 struct SbLaunchCtx {

@@ -15,6 +15,15 @@
 //                  whose square holds both classes by galloping and bisection on the count table alone, then the two
 //                  window sums, the means, thc.  Cells the tables cannot answer take contrast_global, here.
 // The sums are wrapping unsigned adds: a window sum is the exact sum of once-rounded values, whatever the launch geometry.
+//
+// sb_set_table_window_cache: the radius of a band cell's window and the land-side cells in it follow from the land-side
+// plane and the geometry alone, so a call that searches ("fills") leaves them in plane W and the calls after it, while
+// k_scan finds both planes standing, neither build nor read the count table: the two passes move 16 instead of 20 bytes
+// per frame cell, the query one word of W instead of about ten dependent probes of C.  Fill or not is one predicate
+// (sb_tab_fill, sb_launch.hpp), uniform over each launch and the same in all three.  The row and the column pass are
+// compiled in both forms and pick one at their top -- with the switch off, the form that builds C is the code as it was.
+// The query has one form: a launch-uniform branch in the band-cell body takes the search or the word of W, and both
+// meet again at tab_window (four to five registers more than without the switch, the same occupancy, no scratch).
 #include "sb_thc_common.hpp"
 #include "sb_strip_common.hpp"
 
@@ -37,8 +46,8 @@ __device__ __forceinline__ u64 tab_readlane63(u64 v) {
 }
 
 // ---- the row pass
-template <typename T>
-__global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTables tb) {
+template <typename T, bool WC>                           // WC: with the count table
+__device__ __forceinline__ void tab_rows_body(const DiagJob<T> &job, const SbTables &tb, u64 *sA, u64 *sL, unsigned *sC) {
     const Geo g = job.g;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int Y = __builtin_amdgcn_readfirstlane((int)blockIdx.x * SB_TAB_RB + wv);
@@ -46,8 +55,6 @@ __global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTa
     const size_t row = (size_t)(rowok ? Y : g.nyh - 1) * g.nxh;
     const uint64_t *cls = job.clsbits + (size_t)(rowok ? Y : g.nyh - 1) * g.nw;
     const T sd = job.stats[0], rr = job.stats[1];
-    __shared__ u64 sA[TAB_ROWS_NT], sL[TAB_ROWS_NT];
-    __shared__ unsigned sC[TAB_ROWS_NT];
     u64 carA = 0, carL = 0;
     unsigned carC = 0;
     struct In { T th, zz, sg; uint64_t word; };
@@ -67,21 +74,23 @@ __global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTa
         u64 a = in ? tab_fixed((double)t0v) : 0ull, l = land ? a : 0ull;
         int c = land ? 1 : 0;
         sb_scan2_u64(a, l);                              // (all 64 lanes)
-        c = sb_wave_scan_add(c);
+        if (WC) c = sb_wave_scan_add(c);
         a += carA; l += carL;
         const unsigned cc = (unsigned)c + carC;
         carA = tab_readlane63(a); carL = tab_readlane63(l);
-        carC = (unsigned)__builtin_amdgcn_readlane((int)cc, 63);
+        if (WC) carC = (unsigned)__builtin_amdgcn_readlane((int)cc, 63);
         if (in) {
-            tb.A[row + X] = a; tb.L[row + X] = l; tb.C[row + X] = cc;
+            tb.A[row + X] = a; tb.L[row + X] = l;
+            if (WC) tb.C[row + X] = cc;
             const int k = X & (TAB_ROWS_NT - 1);
             atomicAdd((unsigned long long *)&sA[k], (unsigned long long)a);
             atomicAdd((unsigned long long *)&sL[k], (unsigned long long)l);
-            atomicAdd(&sC[k], cc);
+            if (WC) atomicAdd(&sC[k], cc);
         }
     };
     for (int w0 = 0; w0 < g.nw; w0 += TAB_CH) {
-        sA[tid] = 0; sL[tid] = 0; sC[tid] = 0;           // (this thread read its column of the chunk before: see below)
+        sA[tid] = 0; sL[tid] = 0;                        // (this thread read its column of the chunk before: see below)
+        if (WC) sC[tid] = 0;
         __syncthreads();
         if (rowok) {
             const int w1 = min(w0 + TAB_CH, g.nw);
@@ -96,13 +105,25 @@ __global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTa
         const int X = w0 * 64 + tid;
         if (X < g.nxh) {
             const size_t si = (size_t)blockIdx.x * g.nxh + X;
-            tb.SA[si] = sA[tid]; tb.SL[si] = sL[tid]; tb.SC[si] = sC[tid];
+            tb.SA[si] = sA[tid]; tb.SL[si] = sL[tid];
+            if (WC) tb.SC[si] = sC[tid];
         }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTables tb) {
+    __shared__ u64 sA[TAB_ROWS_NT], sL[TAB_ROWS_NT];
+    __shared__ unsigned sC[TAB_ROWS_NT];
+    const bool fill = sb_tab_fill(tb);                   // (k_scan of this call has finished: uniform over the launch)
+    // sb_table_cache_report [2]: calls that searched
+    if (tb.W && blockIdx.x == 0 && threadIdx.x == 0) tb.rep[0] = (tb.rep_reset ? 0u : tb.rep[0]) + (fill ? 1u : 0u);
+    if (fill) tab_rows_body<T, true>(job, tb, sA, sL, sC);
+    else tab_rows_body<T, false>(job, tb, sA, sL, sC);
+}
 
 // ---- the column pass
-__global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, int nbx, SbTables tb) {
+template <bool WC>
+__device__ __forceinline__ void tab_cols_body(int nxh, int nyh, int nbx, const SbTables &tb) {
     const int bx = (int)(blockIdx.x % (unsigned)nbx), b = (int)(blockIdx.x / (unsigned)nbx);
     const int X = bx * TAB_COLS_NT + (int)threadIdx.x;
     if (X >= nxh) return;
@@ -115,7 +136,8 @@ __global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, in
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const size_t si = (size_t)(j + q) * nxh + X;
-            a[q] = tb.SA[si]; l[q] = tb.SL[si]; c[q] = tb.SC[si];
+            a[q] = tb.SA[si]; l[q] = tb.SL[si];
+            c[q] = WC ? tb.SC[si] : 0u;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) { ra += a[q]; rl += l[q]; rc += c[q]; }
@@ -127,17 +149,23 @@ __global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, in
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const size_t i = (size_t)min(Ys + q, Y1 - 1) * nxh + X;
-            a[q] = tb.A[i]; l[q] = tb.L[i]; c[q] = tb.C[i];
+            a[q] = tb.A[i]; l[q] = tb.L[i];
+            c[q] = WC ? tb.C[i] : 0u;
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             if (Ys + q < Y1) {
                 const size_t i = (size_t)(Ys + q) * nxh + X;
                 ra += a[q]; rl += l[q]; rc += c[q];
-                tb.A[i] = ra; tb.L[i] = rl; tb.C[i] = rc;
+                tb.A[i] = ra; tb.L[i] = rl;
+                if (WC) tb.C[i] = rc;
             }
         }
     }
+}
+__global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, int nbx, SbTables tb) {
+    if (sb_tab_fill(tb)) tab_cols_body<true>(nxh, nyh, nbx, tb);
+    else tab_cols_body<false>(nxh, nyh, nbx, tb);
 }
 
 // ---- the query
@@ -203,11 +231,14 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
     };
     const T sd = job.stats[0], rr = job.stats[1];
     const bool limited = g.bnd == BND_HALO;
+    const bool fill = sb_tab_fill(tb);                       // (uniform over the launch)
+    unsigned ncell = 0;                                      // (wave-uniform) this wave's cells of the report
     for (int e = gw; e < total; e += nwaves) {               // (wave-uniform)
         const SbSegEntry cur = entry(e);
         const unsigned Y = cur.seg / (unsigned)g.nw, Xw = cur.seg - Y * (unsigned)g.nw;
         const int x = (int)(Xw * 64u) + lane - g.h, y = (int)Y - g.h;
         int nnmax = 0, flag = -1;
+        bool stored = false;                                 // this lane's cell is answered from its stored window
         if ((cur.word >> lane) & 1ull) {                     // band bits are set for interior cells of processed rows only
             const unsigned o = (unsigned)y * (unsigned)g.nx + (unsigned)x;
             // the largest radius the tables answer for this cell: the reach of the format; the frame (no wrap, no clamp:
@@ -219,7 +250,11 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
             // between it and the last that did not
             bool found = false;
             int hi = 0, nl = 0, below = 0;
-            if (cap >= 1) {
+            if (!fill) {
+                // the window the last fill left: one coalesced load, and the reads of L and A below depend on nothing else
+                const unsigned w = tb.W[o];
+                found = stored = w != 0u; hi = sb_tab_radius(w); nl = sb_tab_nl(w);
+            } else if (cap >= 1) {
                 for (int r = 1;;) {
                     const int c = count(r);
                     if (mixed(c, r)) { found = true; hi = r; nl = c; break; }
@@ -232,6 +267,7 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
                     if (mixed(c, mid)) { hi = mid; nl = c; } else lo = mid + 1;
                 }
             }
+            if (fill && tb.W) tb.W[o] = found ? sb_tab_pack(hi, nl) : 0u;
             const T mul = sb_bit(job.clsbits, g.nw, x + g.h, y + g.h) ? T(1) : T(-1);
             if (found) {
                 const TabWin w = tab_window(g, x, y, hi);
@@ -254,6 +290,8 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
             }
             flag = (x >> job.thc_txs) * job.tile_sx + (y / job.thc_ty) * job.tile_sy + job.tile_off;
         }
+        // sb_table_cache_report: the band cells searched (found or not), or those a stored window answered
+        if (tb.W) ncell += (unsigned)__popcll((unsigned long long)(fill ? cur.word : __ballot(stored)));
         // the largest radius per block / tile (diagnostic, read by sb_last_counters; the flag k_scan raised is 1): one atomic
         // per flag the segment's cells fall under
         for (uint64_t todo = __ballot(nnmax > 1); todo;) {
@@ -263,6 +301,12 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
             if (lane == SB_WAVE - 1) atomicMax(&job.tile_nnmax[f], v);
             todo &= ~__ballot(mine);
         }
+    }
+    // Every wave leaves its count in a slot of its own and the host adds them up: no atomics (atomics on one word are
+    // served one after the other, and there would be one per segment or per wave, most of them at the kernel's end)
+    if (tb.W && lane == 0) {
+        unsigned *slot = tb.rep + SB_TAB_REP_HDR + 2 * gw;
+        slot[0] = fill ? 0u : ncell; slot[1] = fill ? ncell : 0u;
     }
 }
 
@@ -281,6 +325,7 @@ hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st
 template <typename T>
 hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st) {
     if (!job.wind_final) return hipErrorInvalidValue;   // (the update is k_wind's: the plan sees to it)
+    static_assert(4 * (TAB_QUERY_NT / SB_WAVE) == SB_TAB_QUERY_WAVES_PER_CU, "the report has a slot per wave");
     hipLaunchKernelGGL(k_table_query<T>, dim3(ncu * 4), dim3(TAB_QUERY_NT), 0, st, job, tb);
     return hipGetLastError();
 }

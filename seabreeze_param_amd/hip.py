@@ -158,6 +158,18 @@ class Context:
         to 127 at a cost that does not depend on the radius (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_table_contrast(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast")
 
+    def set_table_window_cache(self, on: bool):
+        """Opt-in, with set_table_contrast: a table call keeps every band cell's window while the coast stands; the same
+        bits, less work per call (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_table_window_cache(self.h, C.c_int(1 if on else 0)), "sb_set_table_window_cache")
+
+    def table_cache_report(self):
+        """Band cells of the last diag call answered from stored windows / searched; calls that searched / ran with the
+        cache in effect since it was switched on."""
+        arr = (C.c_longlong * 4)()
+        self._chk(self.lib.sb_table_cache_report(self.h, arr), "sb_table_cache_report")
+        return dict(stored_cells=arr[0], searched_cells=arr[1], fills=arr[2], calls=arr[3])
+
     def last_step_report(self):
         """What the last diag call / band step enqueued on this rank."""
         arr = (C.c_int * 4)()

@@ -1,6 +1,6 @@
 """Cost of the contrast from device-wide summed-area tables (sb_set_table_contrast).
 
-    python tools/table_contrast_cost.py --part fixed|board|board160 [--nx 2560 --ny 1920] [--n 50] [--out FILE]
+    python tools/table_contrast_cost.py --part fixed|board|board160|cache [--nx 2560 --ny 1920] [--n 50] [--out FILE]
 
 Every part times whole sb_seabreeze_diag_f64_dev calls with HIP events on one torch stream (warm, median of N) and the
 kernels of a call with sb_profile_begin / sb_profile_end, one profiled call at a time (median of N).  In a table call the
@@ -13,6 +13,11 @@ the k_thc of a call on the same grid with an empty band (the query then finds no
   board     a periodic checkerboard of 80 x 80 land and sea blocks, every cell in the band (radii up to 40): the path of
             the parent commit -- switch off, radius hint 32 -- against the tables
   board160  the same with 160-cell blocks (radii up to 80), the tables only
+  cache     sb_set_table_window_cache off and on in turn within one process (five blocks of N / 5 warm calls each way, the
+            first calls after every switch -- among them the call that searches and stores -- not timed): the whole call,
+            the row pass, the column pass and the query, on the checkerboard of 80-cell blocks at 640 x 480 and at
+            2560 x 1920 (4 levels) and on the grid and mask of `fixed` (56 levels); the report of the last timed call
+            shows that it was answered from stored windows
 u and v are uniform random numbers (the level k_wind picks depends on p alone).  Each part prints one JSON line and,
 with --out, merges it into that file under its name.  Run every part under a time limit of its own.
 """
@@ -64,8 +69,8 @@ class Case:
         self.stream.synchronize()
         return a.elapsed_time(b)
 
-    def measure(self, n, mask=None):
-        """-> whole-call and per-kernel medians in us, the counters and the launches of the last call"""
+    def samples(self, n, mask=None):
+        """-> n warm whole-call times and n times per kernel, in us"""
         for _ in range(3):
             self.one_call_ms(mask)
         whole = np.array([self.one_call_ms(mask) for _ in range(n)]) * 1e3
@@ -77,6 +82,11 @@ class Case:
             ms, _ = self.ctx.profile_end()
             for k in PROF:
                 ker[k].append(ms[k] * 1e3)
+        return whole, ker
+
+    def measure(self, n, mask=None):
+        """-> whole-call and per-kernel medians in us, the counters and the launches of the last call"""
+        whole, ker = self.samples(n, mask)
         out = dict(call_us=float(np.median(whole)), call_min_us=float(whole.min()), n=n,
                    kernels_us={k: float(np.median(v)) for k, v in ker.items()})
         out["counters"] = self.ctx.last_counters()
@@ -98,6 +108,30 @@ def table_parts(case, n):
     return on
 
 
+def cache_parts(case, n, blocks=5):
+    """the table call with the window cache off and on, in alternating blocks: medians over all blocks"""
+    per = max(1, n // blocks)
+    acc = {m: dict(call=[], rows=[], thc=[], cols=[], empty_call=[]) for m in ("off", "on")}
+    out = {}
+    for _ in range(blocks):
+        for m in ("off", "on"):
+            case.ctx.set_table_window_cache(m == "on")
+            whole, ker = case.samples(per)
+            acc[m]["call"] += list(whole); acc[m]["rows"] += ker["k_t0"]; acc[m]["thc"] += ker["k_thc"]
+            out[m] = dict(report=case.ctx.table_cache_report(), counters=case.ctx.last_counters(),
+                          launches=case.ctx.last_step_report()["kernel_launches"])
+            whole, ker = case.samples(per, case.none)
+            acc[m]["empty_call"] += list(whole); acc[m]["cols"] += ker["k_thc"]
+    case.ctx.set_table_window_cache(False)
+    for m in ("off", "on"):
+        med = {k: float(np.median(v)) for k, v in acc[m].items()}
+        out[m].update(call_us=med["call"], call_min_us=float(np.min(acc[m]["call"])), n=len(acc[m]["call"]),
+                      empty_band_call_us=med["empty_call"],
+                      table_kernels_us=dict(rows=med["rows"], cols=med["cols"], query=med["thc"] - med["cols"]))
+    out["saved_us"] = out["off"]["call_us"] - out["on"]["call_us"]
+    return out
+
+
 def board(nx, ny, w):
     x, y = np.arange(nx)[None, :], np.arange(ny)[:, None]
     return np.where(((x // w) + (y // w)) % 2 == 0, 100.0, -100.0)
@@ -105,7 +139,7 @@ def board(nx, ny, w):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=("fixed", "board", "board160"))
+    ap.add_argument("--part", required=True, choices=("fixed", "board", "board160", "cache"))
     ap.add_argument("--n", type=int, default=50)
     ap.add_argument("--nx", type=int, default=2560)
     ap.add_argument("--ny", type=int, default=1920)
@@ -116,7 +150,16 @@ def main():
     ctx = hip.Context(0)
     stream = torch.cuda.Stream()
     res = dict(tool="table_contrast_cost", part=a.part, nx=nx, ny=ny, dtype="f64")
-    if a.part == "fixed":
+    if a.part == "cache":
+        ctx.set_table_contrast(True)
+        for name, cnx, cny in (("board", 640, 480), ("board", nx, ny), ("fixed", nx, ny)):
+            if name == "fixed":
+                st = synth.static_fields(cnx, cny, np.float64)
+                mask, nz = ctx.get_dist(ctx.get_edges(st.landfrac, st.icefrac), st.landfrac, st.lon, st.lat), a.nz or 56
+            else:
+                mask, nz = board(cnx, cny, 80), a.nz or 4
+            res[f"{name}_{cnx}x{cny}"] = dict(nz=nz, **cache_parts(Case(ctx, cnx, cny, nz, mask, stream), a.n))
+    elif a.part == "fixed":
         nz = a.nz or 56
         st = synth.static_fields(nx, ny, np.float64)
         cdist = ctx.get_dist(ctx.get_edges(st.landfrac, st.icefrac), st.landfrac, st.lon, st.lat)
@@ -148,7 +191,7 @@ def main():
     print(json.dumps(res))
     if a.out:
         allres = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        allres[f"{a.part}_{nx}x{ny}"] = res
+        allres["cache" if a.part == "cache" else f"{a.part}_{nx}x{ny}"] = res
         with open(a.out, "w") as f:
             json.dump(allres, f, indent=1)
             f.write("\n")
