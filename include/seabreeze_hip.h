@@ -106,6 +106,14 @@ int  sb_set_wide_strip(sb_ctx *ctx, int on);
    (0, the default), or k_scan | join | contrast kernel, k_wind -- the three kernels of a single-domain call, one
    launch less, but less work to cover the communication with (1).  A measurement knob: results never depend on it.  */
 int  sb_set_band_order(sb_ctx *ctx, int contrast_first);
+/* k_wind's column walk in double precision with the generic flavour's first-minimum rule on a whole call: two cells per
+   lane and two pressure levels per 16-byte load where nx and the ghost width are even and p lies on a 16-byte boundary
+   (on, the default), or one cell and one level per load everywhere, as every other call walks (off).  The level found
+   is the same bit for bit.  A measurement and test knob: results never depend on it.                             */
+int  sb_set_wind_pairs(sb_ctx *ctx, int on);
+/* *ran = 1: the k_wind of the last diag call on this context was the paired instance, 0: it was not.  The host decides
+   that when it enqueues the call: no synchronisation.                                                           */
+int  sb_last_wind_pairs(sb_ctx *ctx, int *ran);
 /* The kernels that run one persistent workgroup per compute unit (k_scan, the contrast kernel; k_wind four per unit)
    take n workgroups instead (1 .. the device's compute units; 0: back to the default).  A test knob -- with a few
    workgroups a small grid exercises what only grids far beyond the BASELINE sizes reach otherwise: shares of the

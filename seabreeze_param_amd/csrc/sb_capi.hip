@@ -136,6 +136,8 @@ struct sb_ctx {
     int no_plan_cache = 0;              // sb_set_plan_cache(ctx, 0): the strip kernel plans its march afresh every call
     int no_wide_strip = 0;              // sb_set_wide_strip(ctx, 0): radii beyond 16 take the tile kernel in single precision too
     int band_late_wind = 0;             // sb_set_band_order(ctx, 1): a band step runs the contrast before k_wind (measurement)
+    int no_wind_pairs = 0;              // sb_set_wind_pairs(ctx, 0): k_wind walks one cell per lane everywhere
+    int last_wind_pairs = 0;            // the last call's k_wind was the paired instance (sb_last_wind_pairs)
     int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
     // sb_set_table_window_cache(ctx, 1): a table call keeps every band cell's window in W while the coast stands.  tabc: what
     // the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half (sb_table_cache_report)
@@ -361,6 +363,7 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     }
     lc.stream = st; lc.partials = c->partials; lc.stats = c->stats;
     lc.gathered = c->gathered; lc.ngathered = c->ngathered; lc.ncu = c->ncu;
+    lc.wind_pairs = c->no_wind_pairs ? 0 : 1; lc.wind_pairs_ran = &c->last_wind_pairs;
     lc.moments_out = (phases == 1) ? c->band_moments_out : nullptr;   // (a band step: k_scan publishes this band's moments)
     lc.moments_event = (phases == 1 && c->nranks > 1) ? c->ev_mom : nullptr;   // (one rank: nobody waits for them)
     lc.stats_ticket = (int *)c->ticket + 1;
@@ -1816,6 +1819,18 @@ int sb_set_workgroups(sb_ctx *c, int n) {
 int sb_set_band_order(sb_ctx *c, int contrast_first) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->band_late_wind = contrast_first ? 1 : 0;
+    return SB_OK;
+}
+
+int sb_set_wind_pairs(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->no_wind_pairs = on ? 0 : 1;
+    return SB_OK;
+}
+
+int sb_last_wind_pairs(sb_ctx *c, int *ran) {
+    if (!c || !ran) return fail(c, SB_ERR_ARG, "sb_last_wind_pairs: null argument");
+    *ran = c->last_wind_pairs;
     return SB_OK;
 }
 

@@ -23,6 +23,7 @@
 // A band step of a multi-GPU run launches k_wind before its ghost rows arrive (instance <0>: the winds go
 // to scratch planes); the contrast kernel applies thresholds and update behind its march.
 // Memory-bound integer/fp64 work: no MFMA anywhere.
+#include <climits>
 #include "sb_device.hpp"
 #include "sb_launch.hpp"
 #include "sb_scan_body.hpp"
@@ -427,7 +428,16 @@ template <> struct WindCfg<float> { static constexpr int UN = SB_WIND_UN_F32, WG
 #define SB_WT(i) do { } while (0)
 #endif
 
-template <typename T, int UN, int MODE>
+// PAIR (double precision, first-minimum rule; launch_wind decides): the column walk takes two cells per lane and two
+// levels per load instruction.  Lane l loads the aligned cell pair 2*(l & 31), 2*(l & 31) + 1 of the segment as one
+// 16-byte access, at level 2*i + (l >> 5) in instruction i: the lines of the one-cell walk with half its load
+// instructions (the cost of a gathered load is per instruction as much as per line: tools/probe_gather.hip).  Each lane
+// keeps the first strict minimum of its two cells over the levels of its parity; the two halves combine through lane
+// l ^ 32 -- the smaller difference wins, and where neither is smaller (equal, or one of them NaN) the lower level -- which
+// is the level the one-cell walk finds, bit for bit; then lane j takes cell j's level from lane j >> 1.  Everything else
+// of a segment stays one cell per lane.  The host launches this instance only where nx and the ghost width are even and
+// p is 16-byte aligned: a pair then lies inside the row and the line of its band cell, and inside p.
+template <typename T, int UN, int MODE, bool PAIR = false>
 __global__ __launch_bounds__(WIND_NT, WindCfg<T>::WGS) void k_wind(DiagJob<T> job) {
     constexpr bool FINAL = MODE != 0;
     const Geo g = job.g;
@@ -474,12 +484,59 @@ __global__ __launch_bounds__(WIND_NT, WindCfg<T>::WGS) void k_wind(DiagJob<T> jo
 #endif
         const unsigned Y = cur.seg / (unsigned)g.nw, Xw = cur.seg - Y * (unsigned)g.nw;
         const int x = (int)(Xw * 64u) + lane - g.h, y = (int)Y - g.h;
-        if (!((cur.word >> lane) & 1ull)) return;               // band bits are set for interior cells of processed rows only
+        if constexpr (!PAIR) {
+            if (!((cur.word >> lane) & 1ull)) return;           // band bits are set for interior cells of processed rows only
+        }
+        const bool mine = PAIR ? ((cur.word >> lane) & 1ull) != 0 : true;      // (PAIR: every lane stays for the walk)
         const size_t o = (size_t)y * g.nx + x;
         // the final update's inputs: issued ahead of the column walk
         T n_thc = T(0), ws_old = T(0), wd_old = T(0);
-        if constexpr (FINAL) { n_thc = job.thc[o]; ws_old = job.ws[o]; wd_old = job.wd[o]; }
+        if constexpr (FINAL) {
+            if (mine) { n_thc = job.thc[o]; ws_old = job.ws[o]; wd_old = job.wd[o]; }
+        }
         int lev = lev1;
+        if constexpr (PAIR) {
+            // (wave-uniform; launch_wind picks this instance for the generic flavour's first-minimum rule only)
+            typedef T pair_t __attribute__((ext_vector_type(2)));
+            constexpr int UNP = SB_WIND_UN_PAIR;
+            const int m = lane & 31, h = lane >> 5;
+            const uint64_t pairmask = (cur.word | cur.word >> 1) & 0x5555555555555555ull;
+            T best0 = T(INFINITY), best1 = T(INFINITY);
+            int lev0 = h ? INT_MAX : 0, lev1p = lev0;
+            if ((pairmask >> (2 * m)) & 1ull) {
+                const T *pc = job.p + ((size_t)y * g.nx + (size_t)((int)(Xw * 64u) + 2 * m - g.h));
+                const int ni = (nz + 1) >> 1;
+                for (int i0 = 0; i0 < ni; i0 += UNP) {
+                    // whole batches, as below: a slot past the last level re-reads level nz-1 and is never compared
+                    pair_t d[UNP];
+#pragma unroll
+                    for (int q = 0; q < UNP; ++q) {
+                        const int k = 2 * (i0 + q) + h;
+                        d[q] = __builtin_nontemporal_load((const pair_t *)(pc + (size_t)(k < nz ? k : nz - 1) * pl));
+                    }
+#pragma unroll
+                    for (int q = 0; q < UNP; ++q) {
+                        const int k = 2 * (i0 + q) + h;
+                        const T a0 = fabs(d[q].x - job.target_plev), a1 = fabs(d[q].y - job.target_plev);
+                        if (k == 0) { best0 = a0; best1 = a1; }              // the search starts at level 1 (ref :223)
+                        else if (k < nz) {
+                            if (a0 < best0) { best0 = a0; lev0 = k; }
+                            if (a1 < best1) { best1 = a1; lev1p = k; }
+                        }
+                    }
+                }
+            }
+            // even and odd levels meet: the even half began at level 0 as the one-cell walk does, the odd half at (+inf, no level)
+            {
+                const T o0 = __shfl_xor(best0, 32), o1 = __shfl_xor(best1, 32);
+                const int p0 = __shfl_xor(lev0, 32), p1 = __shfl_xor(lev1p, 32);
+                if (o0 < best0 || (!(best0 < o0) && p0 < lev0)) lev0 = p0;
+                if (o1 < best1 || (!(best1 < o1) && p1 < lev1p)) lev1p = p1;
+            }
+            const int le = __shfl(lev0, lane >> 1), lo = __shfl(lev1p, lane >> 1);
+            if (!mine) return;
+            lev = (lane & 1) ? lo : le;
+        } else
         if (job.flavour == SB_FLAVOUR_GENERIC && job.level_rule == 0) {
             // whole batches of UN levels in flight; the last batch is padded by re-reading level
             // nz-1 (never a new minimum: the comparison is strict), so no serial tail of single
@@ -621,8 +678,20 @@ static void launch_scan(const DiagJob<T> &job, int nblk, Moments *partials, bool
 }
 
 template <typename T>
-static void launch_wind(const DiagJob<T> &job, int ncu, hipStream_t st) {
+static void launch_wind(const DiagJob<T> &job, const SbLaunchCtx &lc, hipStream_t st) {
+    const int ncu = lc.ncu;
     const dim3 wg(ncu * WindCfg<T>::WGS), wb(WIND_NT);
+    // the paired walk (k_wind<.., PAIR>): double precision, the generic flavour's first-minimum rule, the update in k_wind;
+    // nx and the ghost width even (a pair of the 64-cell frame segments is then a pair of interior cells of one row, and
+    // every plane starts at an even cell) and p on a 16-byte boundary.  Everything else takes the one-cell walk.
+    bool pairs = false;
+    if constexpr (sizeof(T) == 8)
+        pairs = lc.wind_pairs && job.wind_final && job.flavour == SB_FLAVOUR_GENERIC && job.level_rule == 0 &&
+                job.g.nx % 2 == 0 && job.g.h % 2 == 0 && ((uintptr_t)job.p & 15u) == 0;
+    if (lc.wind_pairs_ran) *lc.wind_pairs_ran = pairs ? 1 : 0;
+    if constexpr (sizeof(T) == 8) {
+        if (pairs) { hipLaunchKernelGGL((k_wind<T, WindCfg<T>::UN, 1, true>), wg, wb, 0, st, job); return; }
+    }
     if (job.wind_final) hipLaunchKernelGGL((k_wind<T, WindCfg<T>::UN, 1>), wg, wb, 0, st, job);
     else hipLaunchKernelGGL((k_wind<T, WindCfg<T>::UN, 0>), wg, wb, 0, st, job);
 }
@@ -668,7 +737,7 @@ hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const S
         case SB_K_CONTRAST:
             if ((e = s.table ? sb_launch_table_query<T>(j, lc.tables, lc.ncu, st) : launch_contrast<T>(j, plan.contrast.Hk, lc.ncu, st)) != hipSuccess) return e;
             break;
-        case SB_K_WIND: launch_wind<T>(j, lc.ncu, st); break;
+        case SB_K_WIND: launch_wind<T>(j, lc, st); break;
         case SB_K_TABLE_ROWS: if ((e = sb_launch_table_rows<T>(j, lc.tables, st)) != hipSuccess) return e; break;
         case SB_K_TABLE_COLS: if ((e = sb_launch_table_cols(j.g, lc.tables, st)) != hipSuccess) return e; break;
         }

@@ -21,6 +21,10 @@
 #ifndef SB_WIND_WGS_PER_CU_F32      // Measured on one box (k_wind, 5120x3840x56 fp32): 8 loads x 4 workgroups 138.6 us,
 #define SB_WIND_WGS_PER_CU_F32 8    // 16 x 4 131.8, 16 x 6 126.4, 8 x 8 120.3, 14 x 7 119.1, 19 x 8 117.6, 28 x 8 118.1,
 #endif                              // 14 x 8 114.3-118.1; 2560x1920x56 fp32: 50.1 -> 39.7 us
+#ifndef SB_WIND_UN_PAIR
+#define SB_WIND_UN_PAIR 7           // 16-byte loads (two cells x two levels each) in flight per lane of k_wind's paired walk.
+#endif                              // Measured (k_wind, 2560x1920x56 fp64, tools/wind_pairs_ab.py): 4 loads 63.3-63.9 us, 7 loads
+                                    // 61.1-61.4, 14 loads 72.8-73.6 (128 registers, spills); the one-cell walk 71.7-72.6
 
 // The device-wide summed-area tables of sb_set_table_contrast (sb_table_kernels.hip) over the (nxh, nyh) frame: inclusive
 // 2-D prefix sums of t0 in fixed point with SB_TAB_FB fractional bits (A), of the same over land-side cells (L) and of
@@ -68,6 +72,8 @@ struct SbLaunchCtx {
     hipEvent_t moments_event;       // ... and this event is recorded behind k_scan, or nullptr
     int *stats_ticket;              // ... with this device word (zero between launches) as the workgroups' ticket
     int ncu;                        // compute units (k_scan and the contrast kernel run one workgroup per CU)
+    int wind_pairs;                 // sb_set_wind_pairs: k_wind may take its paired walk where the call is eligible
+    int *wind_pairs_ran;            // ... and launch_wind notes here whether it did (host memory), or nullptr
     SbTables tables;                // a call whose plan builds the device-wide tables (SbDiagPlan::table)
 };
 

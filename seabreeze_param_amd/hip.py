@@ -149,6 +149,16 @@ class Context:
         """A band step runs k_scan, k_wind | join | contrast (default) or k_scan | join | contrast, k_wind (measurement knob)."""
         self._chk(self.lib.sb_set_band_order(self.h, C.c_int(1 if contrast_first else 0)), "sb_set_band_order")
 
+    def set_wind_pairs(self, on: bool):
+        """k_wind walks two cells and two levels per 16-byte load where the call allows it (default) or one everywhere (measurement / test knob)."""
+        self._chk(self.lib.sb_set_wind_pairs(self.h, C.c_int(1 if on else 0)), "sb_set_wind_pairs")
+
+    def last_wind_pairs(self) -> int:
+        """1: the last diag call's k_wind was the paired instance; 0: it was not."""
+        ran = C.c_int(0)
+        self._chk(self.lib.sb_last_wind_pairs(self.h, C.byref(ran)), "sb_last_wind_pairs")
+        return ran.value
+
     def set_static_sigma(self, on: bool):
         """Opt-in: sigma does not change between calls; its statistics are formed once (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_static_sigma(self.h, C.c_int(1 if on else 0)), "sb_set_static_sigma")

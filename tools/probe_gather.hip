@@ -69,6 +69,57 @@ __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ p, si
     }
 }
 
+// Two (LV = 2) or four (LV = 4) levels per 16-byte load: a lane takes an aligned PAIR of cells of the segment (double2),
+// the 64 / LV lanes of one group cover 128 / LV cells of one level and group h = lane / (64 / LV) loads level LV*i + h
+// in instruction i -- the lines of k_gather<UN, false>, 1 / LV of its load instructions.  UN: instructions per batch.
+// A run that starts at an odd cell begins (and may end) in a pair that holds one band cell.  Each lane keeps (best, lev)
+// of its two cells over the levels of its group; the groups combine at the end (smaller best wins; where neither is
+// smaller the lower level), then lane j takes cell j's result from lane j >> 1.  Same output as k_gather.
+typedef double probe_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void pair_combine(double &best, int &lev, int mask) {
+    const double ob = __shfl_xor(best, mask);
+    const int ol = __shfl_xor(lev, mask);
+    if (ob < best || (!(best < ob) && ol < lev)) { best = ob; lev = ol; }
+}
+template <int UN, int LV>
+__global__ __launch_bounds__(256) void k_gather_pair(const double *__restrict__ p, size_t plane, int nz, int nseg, int act,
+                                                     int stride, int misalign, double *__restrict__ out) {
+    constexpr int NP = 64 / LV;                          // lanes (pairs) per level
+    const int gw = (blockIdx.x * 256 + threadIdx.x) >> 6, nw = (gridDim.x * 256) >> 6;
+    const int lane = threadIdx.x & 63, m = lane & (NP - 1), h = lane / NP;
+    const int ni = (nz + LV - 1) / LV;
+    for (int s = gw; s < nseg; s += nw) {
+        const size_t b = (size_t)s * stride + (misalign ? (s * 7) % 16 : 0), a = b & ~(size_t)1;
+        const bool on = a + 2 * m < b + act;             // the pair holds a cell of the run
+        double best0 = 1e300, best1 = 1e300;
+        int lev0 = h ? 0x7fffffff : 0, lev1 = lev0;
+        if (on) {
+            const double *pc = p + a + 2 * m;
+            for (int i0 = 0; i0 < ni; i0 += UN) {
+                probe_d2 d[UN];
+#pragma unroll
+                for (int q = 0; q < UN; ++q) {
+                    const int k = LV * (i0 + q) + h;
+                    d[q] = __builtin_nontemporal_load((const probe_d2 *)(pc + (size_t)(k < nz ? k : nz - 1) * plane));
+                }
+#pragma unroll
+                for (int q = 0; q < UN; ++q) {
+                    const int k = LV * (i0 + q) + h;
+                    const double a0 = fabs(d[q].x - 70000.0), a1 = fabs(d[q].y - 70000.0);
+                    if (k < nz && a0 < best0) { best0 = a0; lev0 = k; }
+                    if (k < nz && a1 < best1) { best1 = a1; lev1 = k; }
+                }
+            }
+        }
+#pragma unroll
+        for (int mask = 32; mask >= NP; mask >>= 1) { pair_combine(best0, lev0, mask); pair_combine(best1, lev1, mask); }
+        const double e0 = __shfl(best0, lane >> 1), e1 = __shfl(best1, lane >> 1);
+        const int f0 = __shfl(lev0, lane >> 1), f1 = __shfl(lev1, lane >> 1);
+        const size_t cell = a + lane;
+        if (lane < 2 * NP && cell >= b && cell < b + act) out[cell] = (lane & 1) ? e1 + f1 : e0 + f0;
+    }
+}
+
 // a wave takes MS ADJACENT segments (neighbours along longitude: the same pages of every plane) and walks them together,
 // UN levels of each in flight: per level one page of the plane serves MS loads of the wave
 template <int UN, int MS>
@@ -150,6 +201,21 @@ int main() {
         }
         return median(t) * 1e3;
     };
+    struct Mmm { double mn, md, mx; };
+    auto timeit3 = [&](auto fn) {                     // min, median, max of 9 repetitions, us
+        std::vector<float> t;
+        for (int r = 0; r < 9; ++r) {
+            CHK(hipEventRecord(e0, s1));
+            fn();
+            CHK(hipEventRecord(e1, s1));
+            CHK(hipEventSynchronize(e1));
+            float ms;
+            CHK(hipEventElapsedTime(&ms, e0, e1));
+            t.push_back(ms);
+        }
+        std::sort(t.begin(), t.end());
+        return Mmm{t.front() * 1e3, t[t.size() / 2] * 1e3, t.back() * 1e3};
+    };
     struct Case { const char *name; int nseg, act, stride, misalign; };
     // all cases move ~214 MB of algorithmic bytes except where noted
     const Case cases[] = {
@@ -185,6 +251,21 @@ int main() {
             const double a82 = timeit([&] { hipLaunchKernelGGL((k_gather_adj<8, 2>), g, b, 0, s1, p, plane, nz, c.nseg, c.act, c.stride, c.misalign, out); });
             printf("              adjacent segments walked together (levels x segments in flight): 4x2 %.1f us  4x4 %.1f (%.0f GB/s of lines)  2x8 %.1f  8x2 %.1f\n",
                    a24, a44, fetched / a44 / 1e3, a28, a82);
+#define PROBE_ARGS g, b, 0, s1, p, plane, nz, c.nseg, c.act, c.stride, c.misalign, out
+            const Mmm r8 = timeit3([&] { hipLaunchKernelGGL((k_gather<8, false>), PROBE_ARGS); });
+            const Mmm p4 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<4, 2>), PROBE_ARGS); });
+            const Mmm p7 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<7, 2>), PROBE_ARGS); });
+            const Mmm p14 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<14, 2>), PROBE_ARGS); });
+            printf("              min/median/max of 9: cell-major un8 %.1f/%.1f/%.1f us | pairs, two levels per 16-byte load: un4 %.1f/%.1f/%.1f  un7 %.1f/%.1f/%.1f  un14 %.1f/%.1f/%.1f\n",
+                   r8.mn, r8.md, r8.mx, p4.mn, p4.md, p4.mx, p7.mn, p7.md, p7.mx, p14.mn, p14.md, p14.mx);
+            if (c.act <= 32 - c.misalign) {          // four levels per load: 16 pairs = 32 cells hold the run (recorded only)
+                const Mmm q4 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<4, 4>), PROBE_ARGS); });
+                const Mmm q7 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<7, 4>), PROBE_ARGS); });
+                const Mmm q14 = timeit3([&] { hipLaunchKernelGGL((k_gather_pair<14, 4>), PROBE_ARGS); });
+                printf("              pairs, four levels per load: un4 %.1f/%.1f/%.1f  un7 %.1f/%.1f/%.1f  un14 %.1f/%.1f/%.1f\n",
+                       q4.mn, q4.md, q4.mx, q7.mn, q7.md, q7.mx, q14.mn, q14.md, q14.mx);
+            }
+#undef PROBE_ARGS
         }
     }
     // k_scan-shaped stream
