@@ -31,6 +31,10 @@
 !                                static fields get their ghost rows once through swap_bounds, every step is one
 !                                band_seabreeze_diag; output.bin then holds this band's rows only
 !                                (cdist(nx,nyl), then per step the four (nx,nyl) fields)
+!     bandsetup                  the coast setup per latitude band: coast and distance of the grid with the whole-grid
+!                                routines, then, in this process, of three bands in frames cut here
+!                                (band_get_edges, band_get_dist); stops at the first cell that differs, prints
+!                                "bandsetup ok" otherwise.  No steps are run, output.bin holds cdist only
 ! The tests write input.bin with numpy and compare output.bin with the CPU oracle.
 !
 ! Two deliberate differences from the outline, both documented in INTEGRATION.md:
@@ -61,7 +65,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | bandsetup | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -108,6 +112,8 @@ program dummy_model
     call run_um2d()
   case ('status')
     call check_status()
+  case ('bandsetup')
+    call run_band_setup()
   case default
     error stop 'unknown mode'
   end select
@@ -133,6 +139,64 @@ contains
     integer, intent(in) :: timestep_number
     call seabreeze_diag(timestep, timestep_number, p, u, v, theta, mask, z, sigma, windspeed, winddir, thc, sb_con)
   end subroutine physics
+
+  !---------------------------------------------------------------------------
+  ! The coast setup band by band against the whole-grid routines: three bands of uneven height, each in a frame of
+  ! halo_size ghost cells cut out of the global fields here (what swap_bounds delivers on a multi-rank run: the
+  ! neighbours' rows on a cut side).  Ghost rows beyond a pole, their latitudes and the east-west ghost columns are
+  ! NaN: they are never read.  The window is +-halo_size cells, as in atmos_step.
+  !---------------------------------------------------------------------------
+  subroutine run_band_setup()
+    use, intrinsic :: ieee_arithmetic, only : ieee_value, ieee_quiet_nan
+    use sea_breeze_diag_mod, only : get_edges, get_dist, band_get_edges, band_get_dist
+    integer :: h, b, r0, r1, nyl, i, j, lo, hi, cuts(4)
+    real :: nan
+    real, allocatable :: lf(:,:), ic(:,:), cf(:,:), df(:,:), latf(:)
+    h = halo_size
+    nan = ieee_value(nan, ieee_quiet_nan)
+    call get_edges(mask, ice_frac, land_frac, h)
+    call get_dist(mask, land_frac, lon, lat, 180, cdist, h)
+    write (uout) cdist
+    cuts = [0, ny/3 - 1, 2*(ny/3) + 2, ny]
+    if (cuts(2) < 1 .or. cuts(3) <= cuts(2) .or. cuts(3) >= ny) error stop 'bandsetup: grid too small for three bands'
+    do b = 1, 3
+      r0 = cuts(b); r1 = cuts(b+1); nyl = r1 - r0                ! rows r0+1 .. r1 (1-based) of the grid
+      allocate(lf(nx+2*h, nyl+2*h), ic(nx+2*h, nyl+2*h), cf(nx+2*h, nyl+2*h), df(nx+2*h, nyl+2*h), latf(nyl+2*h))
+      lf = nan; ic = nan; latf = nan; cf = -777.; df = -777.
+      lo = max(r0 - h, 0); hi = min(r1 + h, ny)                  ! the grid rows lo+1 .. hi lie in the frame
+      lf(1+h:nx+h, lo-r0+h+1:hi-r0+h) = land_frac(:, lo+1:hi)
+      ic(1+h:nx+h, lo-r0+h+1:hi-r0+h) = ice_frac(:, lo+1:hi)
+      latf(lo-r0+h+1:hi-r0+h) = lat(lo+1:hi)
+      call band_get_edges(cf, ic, lf, h, b == 1, b == 3)
+      do j = 1, nyl
+        do i = 1, nx
+          if (cf(i+h, j+h) /= mask(i+h, r0+j+h)) then
+            print '(a,i0,a,i0,a,i0)', 'bandsetup: coast differs in band ', b, ' at ', i, ',', r0 + j
+            error stop 'bandsetup: band_get_edges differs from get_edges'
+          end if
+        end do
+      end do
+      if (any(cf(:, :h) /= -777.) .or. any(cf(:, nyl+h+1:) /= -777.) .or. any(cf(:h, :) /= -777.) .or. &
+          any(cf(nx+h+1:, :) /= -777.)) error stop 'bandsetup: band_get_edges wrote ghost cells'
+      ! (the exchange of coast's ghost rows: the neighbours' rows of the whole-grid coast, which the bands reproduce)
+      cf = nan
+      cf(1+h:nx+h, lo-r0+h+1:hi-r0+h) = mask(1+h:nx+h, lo+1+h:hi+h)
+      call band_get_dist(cf, lf, lon, latf, 180, df, h, b == 1, b == 3)
+      do j = 1, nyl
+        do i = 1, nx
+          if (df(i+h, j+h) /= cdist(i, r0+j)) then
+            print '(a,i0,a,i0,a,i0,2es24.16)', 'bandsetup: distance differs in band ', b, ' at ', i, ',', r0 + j, &
+                  df(i+h, j+h), cdist(i, r0+j)
+            error stop 'bandsetup: band_get_dist differs from get_dist'
+          end if
+        end do
+      end do
+      if (any(df(:, :h) /= -777.) .or. any(df(:, nyl+h+1:) /= -777.) .or. any(df(:h, :) /= -777.) .or. &
+          any(df(nx+h+1:, :) /= -777.)) error stop 'bandsetup: band_get_dist wrote ghost cells'
+      deallocate(lf, ic, cf, df, latf)
+    end do
+    print '(a)', 'bandsetup ok'
+  end subroutine run_band_setup
 
   !---------------------------------------------------------------------------
   ! fields resident on the device: static ones go up once, per step theta, u, v

@@ -42,6 +42,7 @@ module sea_breeze_diag_mod
   public :: band_seabreeze_diag, seabreeze_diag_dev, band_seabreeze_diag_dev
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
   public :: get_edges_um, get_dist_um, get_dist_um_win
+  public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
 #ifdef SB_REAL8
@@ -57,6 +58,10 @@ module sea_breeze_diag_mod
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f64"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f64"
 #define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f64"
+#define SB_BAND_GET_EDGES "sb_band_get_edges_f64"
+#define SB_BAND_GET_DIST  "sb_band_get_dist_f64"
+#define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f64_dev"
+#define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f64_dev"
 #else
   integer, parameter :: rk = c_float
 #define SB_SEABREEZE_DIAG "sb_seabreeze_diag_f32"
@@ -70,9 +75,18 @@ module sea_breeze_diag_mod
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f32"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f32"
 #define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f32"
+#define SB_BAND_GET_EDGES "sb_band_get_edges_f32"
+#define SB_BAND_GET_DIST  "sb_band_get_dist_f32"
+#define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f32_dev"
+#define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f32_dev"
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
+
+  interface band_get_dist       ! (maxdist as a real or as the integer literal, like get_dist)
+    module procedure band_get_dist_r
+    module procedure band_get_dist_i
+  end interface
 
   interface get_dist            ! the reference's caller passes the integer literal 180 for
     module procedure get_dist_r ! maxdist (ref: generic/dummy_model.f90:33); accept both
@@ -169,6 +183,37 @@ module sea_breeze_diag_mod
       real(rk), value :: maxdist
       real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
       real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_band_get_edges(ctx, nx, ny, halo, south, north, lsm, ci, rule, coast) &
+        bind(C, name=SB_BAND_GET_EDGES)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, halo, south, north, rule
+      real(rk), intent(in) :: lsm(*), ci(*)
+      real(rk), intent(inout) :: coast(*)
+    end function
+    integer(c_int) function c_band_get_dist(ctx, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, cdist) &
+        bind(C, name=SB_BAND_GET_DIST)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, halo, south, north, kwin
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: coast(*), mask(*), lon(*), lat(*)
+      real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_band_get_edges_dev(ctx, nx, ny, halo, south, north, lsm, ci, rule, coast, stream) &
+        bind(C, name=SB_BAND_GET_EDGES_DEV)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, lsm, ci, coast, stream
+      integer(c_int), value :: nx, ny, halo, south, north, rule
+    end function
+    integer(c_int) function c_band_get_dist_dev(ctx, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, &
+        cdist, stream) bind(C, name=SB_BAND_GET_DIST_DEV)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx, coast, mask, cdist, stream
+      integer(c_int), value :: nx, ny, halo, south, north, kwin
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: lon(*), lat(*)
     end function
   end interface
 
@@ -391,6 +436,92 @@ contains
     real, intent(out), contiguous :: cdist(:,:)
     call get_dist_r(coast, landfrac, lon, lat, real(maxdist), cdist, halo_size)
   end subroutine get_dist_i
+
+  !---------------------------------------------------------------------------
+  ! get_edges and get_dist for ONE LATITUDE BAND of a multi-GPU run: the dummy order of the generic routines plus the
+  ! band arguments.  Every field is in the band step's frame, (nx+2*halo_size, ny+2*halo_size) with the band's own
+  ! rows in the interior; lon has nx entries, lat ny+2*halo_size (one per frame row).  south / north: the band touches
+  ! that pole.  On a cut side the ghost rows next to the interior are read -- one row of landfrac and icefrac, kwin
+  ! rows of coast -- and must have been filled (halo_exchange_mod::swap_bounds); ghost rows beyond a pole and the
+  ! east-west ghost columns are never read.  Only the interior of mask / cdist is written: call swap_bounds on them
+  ! afterwards.  The interior is the whole-grid routines' field, bit for bit.  The window is +-halo_size cells as in
+  ! get_dist, or +-kwin <= halo_size where kwin is given.
+  !---------------------------------------------------------------------------
+  subroutine band_get_edges(mask, icefrac, landfrac, halo_size, south, north)
+    integer, intent(in) :: halo_size
+    logical, intent(in) :: south, north
+    real, intent(inout), contiguous :: mask(:,:)
+    real, intent(in), contiguous :: landfrac(:,:), icefrac(:,:)
+    integer(c_int) :: nx, ny, rc
+    nx = size(landfrac, 1) - 2*halo_size; ny = size(landfrac, 2) - 2*halo_size
+    if (halo_size < 0 .or. nx < 1 .or. ny < 1 .or. any(shape(icefrac) /= shape(landfrac)) .or. &
+        any(shape(mask) /= shape(landfrac))) &
+      call fail('band_get_edges: mask, icefrac, landfrac must be (nx+2*halo_size, ny+2*halo_size)', 1_c_int)
+    call ensure_ctx()
+    rc = c_band_get_edges(ctx, nx, ny, int(halo_size, c_int), merge(1_c_int, 0_c_int, south), merge(1_c_int, 0_c_int, north), &
+                          landfrac, icefrac, 1_c_int, mask)
+    if (rc /= 0) call fail('band_get_edges', rc)
+  end subroutine band_get_edges
+
+  subroutine band_get_dist_r(coast, landfrac, lon, lat, maxdist, cdist, halo_size, south, north, kwin)
+    integer, intent(in) :: halo_size
+    logical, intent(in) :: south, north
+    integer, intent(in), optional :: kwin
+    real, intent(in), contiguous :: lon(:), lat(:), landfrac(:,:), coast(:,:)
+    real, intent(in) :: maxdist
+    real, intent(inout), contiguous :: cdist(:,:)
+    integer(c_int) :: nx, ny, rc, k
+    nx = size(lon, 1); ny = size(lat, 1) - 2*halo_size
+    if (halo_size < 0 .or. ny < 1 .or. any(shape(coast) /= [nx + 2*halo_size, ny + 2*halo_size]) .or. &
+        any(shape(landfrac) /= shape(coast)) .or. any(shape(cdist) /= shape(coast))) &
+      call fail('band_get_dist: coast, landfrac, cdist must be (size(lon)+2*halo_size, size(lat)), lat one per frame row', &
+                1_c_int)
+    k = int(halo_size, c_int)
+    if (present(kwin)) k = int(kwin, c_int)
+    call ensure_ctx()
+    rc = c_band_get_dist(ctx, nx, ny, int(halo_size, c_int), merge(1_c_int, 0_c_int, south), merge(1_c_int, 0_c_int, north), &
+                         coast, landfrac, lon, lat, real(maxdist, rk), k, cdist)
+    if (rc /= 0) call fail('band_get_dist', rc)
+  end subroutine band_get_dist_r
+
+  subroutine band_get_dist_i(coast, landfrac, lon, lat, maxdist, cdist, halo_size, south, north, kwin)
+    integer, intent(in) :: halo_size, maxdist
+    logical, intent(in) :: south, north
+    integer, intent(in), optional :: kwin
+    real, intent(in), contiguous :: lon(:), lat(:), landfrac(:,:), coast(:,:)
+    real, intent(inout), contiguous :: cdist(:,:)
+    call band_get_dist_r(coast, landfrac, lon, lat, real(maxdist), cdist, halo_size, south, north, kwin)
+  end subroutine band_get_dist_i
+
+  ! Device-resident forms: the fields are device pointers (sb_context_mod::sb_dev_alloc) in the same frames, lon and lat
+  ! host arrays; the calls only enqueue on the context's stream.
+  subroutine band_get_edges_dev(mask, icefrac, landfrac, nx, ny, halo_size, south, north)
+    type(c_ptr), intent(in) :: mask, icefrac, landfrac
+    integer, intent(in) :: nx, ny, halo_size
+    logical, intent(in) :: south, north
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_band_get_edges_dev(ctx, int(nx, c_int), int(ny, c_int), int(halo_size, c_int), merge(1_c_int, 0_c_int, south), &
+                              merge(1_c_int, 0_c_int, north), landfrac, icefrac, 1_c_int, mask, c_null_ptr)
+    if (rc /= 0) call fail('band_get_edges_dev', rc)
+  end subroutine band_get_edges_dev
+
+  subroutine band_get_dist_dev(coast, landfrac, lon, lat, maxdist, cdist, halo_size, south, north, kwin)
+    type(c_ptr), intent(in) :: coast, landfrac, cdist
+    real, intent(in), contiguous :: lon(:), lat(:)
+    real, intent(in) :: maxdist
+    integer, intent(in) :: halo_size
+    logical, intent(in) :: south, north
+    integer, intent(in), optional :: kwin
+    integer(c_int) :: rc, k
+    k = int(halo_size, c_int)
+    if (present(kwin)) k = int(kwin, c_int)
+    call ensure_ctx()
+    rc = c_band_get_dist_dev(ctx, int(size(lon), c_int), int(size(lat) - 2*halo_size, c_int), int(halo_size, c_int), &
+                             merge(1_c_int, 0_c_int, south), merge(1_c_int, 0_c_int, north), coast, landfrac, lon, lat, &
+                             real(maxdist, rk), k, cdist, c_null_ptr)
+    if (rc /= 0) call fail('band_get_dist_dev', rc)
+  end subroutine band_get_dist_dev
 
   !---------------------------------------------------------------------------
   ! The UM copy's get_edges(mask, icefrac, landfrac) (ref: UM/vn10.7/sea_breeze_diag.F90:328-446) in its argument

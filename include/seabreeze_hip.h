@@ -420,6 +420,55 @@ int sb_dist_window_f64(int nlons, int nlats, const double *lon, const double *la
 int sb_dist_window_f32(int nlons, int nlats, const float *lon, const float *lat, float maxdist, int *k);
 
 /* -------------------------------------------------------------------------------- */
+/* get_edges, get_dist -- one latitude band of a multi-GPU run                       */
+/* The coast setup of sb_get_edges_*(..., rule, SB_BND_GLOBAL) and                    */
+/* sb_get_dist_*(..., kwin) for a rank that holds only its own rows, in the layout of */
+/* the band step (sb_band_seabreeze_diag_*): every field is (nx+2*halo, ny+2*halo)    */
+/* with the interior at (halo, halo); ny counts the band's own rows; south / north    */
+/* != 0: the band touches that pole (meaning and row orientation as in                */
+/* sb_fill_ghosts_*_dev).  lon has nx entries, lat ny+2*halo: one per frame row.      */
+/* Read: on a cut side the north-south ghost rows next to the interior -- 1 row of    */
+/* lsm and ci for the Sobel, kwin rows of coast (and their lat entries) for the       */
+/* distance -- filled beforehand by sb_swap_bounds_* or the caller's own exchange.    */
+/* Never read: the ghost rows on a pole side and their lat entries (the Sobel clamps  */
+/* to the edge row, the window ends there, as on the globe), and the east-west ghost  */
+/* columns (longitude is periodic by index arithmetic).  mask is read in the interior */
+/* only.  Written: the interior of coast / cdist; their ghost cells are left to the   */
+/* caller's swap_bounds.  Ghost rows are sources only, never computed as targets.     */
+/* Result: the interior equals, bit for bit, rows r0 .. r1-1 of the whole-grid call   */
+/* on the grid of which the frame's rows are rows r0-halo .. r1+halo-1, on the same   */
+/* device and in the same precision: the Sobel's clamp at a pole row, the sweep-order */
+/* reset and the sign included.  Both land rules; SB_BND_WRAPPER's column quirk is    */
+/* not served.  south and north both set with halo = 0 is the whole grid.             */
+/* SB_ERR_ARG: kwin < 0 (the derived half-width needs the global latitudes: use       */
+/* sb_dist_window_* on those), kwin > SB_DIST_MAX_WINDOW, kwin > halo with a cut      */
+/* side, halo < 1 with a cut side (edges), coast overlapping cdist.                   */
+/* The _dev forms take device pointers for the fields and HOST pointers for lon, lat, */
+/* and enqueue without synchronising; the coordinate tables are keyed on the content  */
+/* of lon and of the lat entries that are read, as sb_get_dist_*_dev keeps them.      */
+/* -------------------------------------------------------------------------------- */
+int sb_band_get_edges_f64(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                          const double *lsm, const double *ci, int rule, double *coast);
+int sb_band_get_edges_f32(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                          const float *lsm, const float *ci, int rule, float *coast);
+int sb_band_get_edges_f64_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                          const double *lsm, const double *ci, int rule, double *coast, void *stream);
+int sb_band_get_edges_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                          const float *lsm, const float *ci, int rule, float *coast, void *stream);
+int sb_band_get_dist_f64(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                         const double *coast, const double *mask, const double *lon, const double *lat,
+                         double maxdist, int kwin, double *cdist);
+int sb_band_get_dist_f32(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                         const float *coast, const float *mask, const float *lon, const float *lat,
+                         float maxdist, int kwin, float *cdist);
+int sb_band_get_dist_f64_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                         const double *coast, const double *mask, const double *lon, const double *lat,
+                         double maxdist, int kwin, double *cdist, void *stream);
+int sb_band_get_dist_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                         const float *coast, const float *mask, const float *lon, const float *lat,
+                         float maxdist, int kwin, float *cdist, void *stream);
+
+/* -------------------------------------------------------------------------------- */
 /* get_edges -- UM vn10.7 layout (tdims_l), for curvilinear / rotated-pole grids      */
 /* replaces: get_edges(mask, icefrac, landfrac)                                      */
 /*           ref: UM/vn10.7/sea_breeze_diag.F90:328-446 (get_edges)                  */

@@ -147,9 +147,13 @@ class BandRunner:
     # -- uploads -----------------------------------------------------------------------
     def _halo_field(self, full2d):
         """Interior rows of this band inside a ghost-cell frame (ghosts zero until exchanged)."""
+        return self._halo_rows(full2d[self.r0:self.r1])
+
+    def _halo_rows(self, rows2d):
+        """This band's own rows (r1-r0, nx) inside a ghost-cell frame."""
         t, h = self.torch, self.h
         loc = t.zeros((self.nyl + 2 * h, self.nx + 2 * h), dtype=self.tdtype, device=self.dev)
-        src = t.from_numpy(np.ascontiguousarray(full2d[self.r0:self.r1])).to(self.dev)
+        src = t.from_numpy(np.ascontiguousarray(rows2d)).to(self.dev)
         loc[h:h + self.nyl, h:h + self.nx] = src
         return loc
 
@@ -161,9 +165,63 @@ class BandRunner:
                 exchange_ns(loc, self.nyl, self.h, self.rank, self.world, self.dist, self.torch)
                 fill_ew_ghosts(loc, self.nx, self.h)
 
-    def upload_static(self, z, sigma, mask):
-        self.z, self.sigma, self.mask = (self._halo_field(a) for a in (z, sigma, mask))
-        for a in (self.z, self.sigma, self.mask):      # static fields: ghosts exchanged once
+    def setup_mask(self, lsm, ci, lon, lat, rule: int, kwin: int, maxdist: float = 180.0):
+        """The signed coast distance of this band from this rank's rows alone -- get_edges(rule, SB_BND_GLOBAL) and
+        get_dist(kwin) of the whole grid, bit for bit, without any rank holding or computing the globe: framed lsm and
+        ci, their ghost rows from the band neighbours, the band edges call, coast's ghost rows, the band distance call,
+        the result's ghost cells; kept as self.mask for `step` (upload_static may then be called without a mask).
+        lsm, ci: the full (ny, nx) fields (only rows r0:r1 are touched) or this band's rows (r1-r0, nx); lon (nx) and lat
+        (ny) are the global vectors.  kwin <= halo: the half-width of the window, e.g. hip.dist_window(lon, lat)."""
+        t, h, nx, nyl = self.torch, self.h, self.nx, self.nyl
+        lon, lat = np.asarray(lon, dtype=self.dtype), np.asarray(lat, dtype=self.dtype)
+        if lon.shape != (nx,) or lat.shape != (self.ny,):
+            raise ValueError("lon and lat are the global vectors: nx and ny entries")
+        if kwin < 0 or (self.world > 1 and kwin > h):
+            raise ValueError(f"kwin = {kwin} must lie in 0 .. halo = {h}: the window reads kwin ghost rows")
+        mine = lambda a: a if a.shape == (nyl, nx) else a[self.r0:self.r1]
+        lsm_f, ci_f = (self._halo_rows(mine(np.asarray(a))) for a in (lsm, ci))
+        coast_f, mask_f = t.zeros_like(lsm_f), t.zeros_like(lsm_f)
+        south, north = self.rank == 0, self.rank == self.world - 1
+        latf = np.full(nyl + 2 * h, np.nan, dtype=self.dtype)    # one latitude per frame row; beyond a pole: never read
+        lo, hi = max(self.r0 - h, 0), min(self.r1 + h, self.ny)
+        latf[h - (self.r0 - lo):h + (hi - self.r0)] = lat[lo:hi]
+        stream = self._stream()
+
+        def hand_over():                                         # torch wrote (or exchanges next), the library wrote last
+            if not (self.world > 1 and self.comm == "native"):
+                self.ctx.synchronize()
+                t.cuda.synchronize()
+
+        for a in (lsm_f, ci_f):
+            self._fill_ghosts(a)
+        hand_over()
+        if self.world == 1:
+            self.ctx.get_edges_dev(self.dtype, nx, nyl, lsm_f.data_ptr(), ci_f.data_ptr(), coast_f.data_ptr(), rule=rule,
+                                   bnd=_hip.SB_BND_GLOBAL, stream=stream)
+            self.ctx.get_dist_dev(self.dtype, nx, nyl, coast_f.data_ptr(), lsm_f.data_ptr(), lon, lat, mask_f.data_ptr(),
+                                  maxdist=maxdist, kwin=kwin, stream=stream)
+        else:
+            self.ctx.band_get_edges_dev(self.dtype, nx, nyl, h, south, north, lsm_f.data_ptr(), ci_f.data_ptr(),
+                                        coast_f.data_ptr(), rule=rule, stream=stream)
+            hand_over()
+            self._fill_ghosts(coast_f)
+            hand_over()
+            self.ctx.band_get_dist_dev(self.dtype, nx, nyl, h, south, north, coast_f.data_ptr(), lsm_f.data_ptr(), lon, latf,
+                                       mask_f.data_ptr(), kwin, maxdist=maxdist, stream=stream)
+            hand_over()
+            self._fill_ghosts(mask_f)
+        self.mask = mask_f
+        self.synchronize()
+        return self.mask
+
+    def upload_static(self, z, sigma, mask=None):
+        """mask=None: the mask setup_mask left on the device stays."""
+        self.z, self.sigma = (self._halo_field(a) for a in (z, sigma))
+        if mask is not None:
+            self.mask = self._halo_field(mask)
+        elif getattr(self, "mask", None) is None:
+            raise ValueError("upload_static without a mask needs setup_mask first")
+        for a in (self.z, self.sigma) + ((self.mask,) if mask is not None else ()):      # static fields: ghosts exchanged once
             self._fill_ghosts(a)
         self.torch.cuda.synchronize()                  # (torch wrote them; the library reads them on streams of its own)
         self.ctx.synchronize()

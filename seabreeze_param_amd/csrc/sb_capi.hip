@@ -1011,27 +1011,16 @@ int dist_window(int nx, int ny, const T *lon, const T *lat, T maxdist, int *k) {
     return SB_OK;
 }
 
+// The coordinate tables on the device -- phi = d2r*lat, the folded longitudes in radians (ref: sobel.f90:130,165-174),
+// sin and cos of half of them (k_dist_bits, fp64) -- and what the host derives from the coordinates (may the kernel keep
+// only the nearest hit per side of a row?) stand for as long as the coordinates do: they are keyed on the CONTENT of
+// lon and lat (a byte comparison of two short vectors), made and uploaded when it changes, and left alone otherwise --
+// a `_dev` call then enqueues two kernels and returns, without a copy and without a synchronisation (round 3
+// recomputed, uploaded and waited in every call: a third of get_dist's 230 us).
+// lat: the ny latitudes of the SOURCE rows -- the whole grid's, or (sb_band_get_dist_*) the entries of a band's frame rows
+// that may hold a source; nothing else of the caller's vector is looked at.
 template <typename T>
-int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const T *lon, const T *lat, T maxdist,
-                 int kwin, T *cdist, void *stream) {
-    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    if (nx < 1 || ny < 1 || !coast || !mask || !lon || !lat || !cdist)
-        return fail(c, SB_ERR_ARG, "bad get_dist arguments");
-    int k = kwin;
-    if (kwin < 0) {
-        int rc = dist_window<T>(nx, ny, lon, lat, maxdist, &k);
-        if (rc) { c->err = g_err; return rc; }
-    }
-    if (k > SB_DIST_MAX_WINDOW)
-        return fail(c, SB_ERR_ARG, "get_dist: window half-width " + std::to_string(k) + " exceeds SB_DIST_MAX_WINDOW = " +
-                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
-    // The coordinate tables on the device -- phi = d2r*lat, the folded longitudes in radians (ref: sobel.f90:130,165-174),
-    // sin and cos of half of them (k_dist_bits, fp64) -- and what the host derives from the coordinates (may the kernel keep
-    // only the nearest hit per side of a row?) stand for as long as the coordinates do: they are keyed on the CONTENT of
-    // lon and lat (a byte comparison of two short vectors), made and uploaded when it changes, and left alone otherwise --
-    // a `_dev` call then enqueues two kernels and returns, without a copy and without a synchronisation (round 3
-    // recomputed, uploaded and waited in every call: a third of get_dist's 230 us).
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+int dist_tables(sb_ctx *c, int nx, int ny, const T *lon, const T *lat, hipStream_t st) {
     const size_t kb = ((size_t)nx + ny) * sizeof(T);
     bool same = c->dist_key.size() == kb + 3 * sizeof(int) && c->vecs.p != nullptr;
     const int dims[3] = {nx, ny, (int)sizeof(T)};
@@ -1063,6 +1052,26 @@ int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const
         HIPCHK(c, hipStreamSynchronize(c->dist_upload_stream));
         c->dist_upload_stream = nullptr;
     }
+    return SB_OK;
+}
+
+template <typename T>
+int get_dist_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const T *lon, const T *lat, T maxdist,
+                 int kwin, T *cdist, void *stream) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || !coast || !mask || !lon || !lat || !cdist)
+        return fail(c, SB_ERR_ARG, "bad get_dist arguments");
+    int k = kwin;
+    if (kwin < 0) {
+        int rc = dist_window<T>(nx, ny, lon, lat, maxdist, &k);
+        if (rc) { c->err = g_err; return rc; }
+    }
+    if (k > SB_DIST_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "get_dist: window half-width " + std::to_string(k) + " exceeds SB_DIST_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int rc;
+    if ((rc = dist_tables<T>(c, nx, ny, lon, lat, st))) return rc;
     const T *dphi = (const T *)c->vecs.p, *dlam = dphi + ny;
     if ((rc = ensure(c, c->coastbits, (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
     HIPCHK(c, sb_launch_dist<T>(coast, mask, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist, nx, ny, k, maxdist,
@@ -1083,6 +1092,105 @@ int get_dist_host(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, cons
     T *dco = s.in(coast, n), *dm = s.in(mask, n), *dcd = s.out<T>(n);
     if (s.rc) return s.rc;
     int rc = get_dist_dev<T>(c, nx, ny, dco, dm, lon, lat, maxdist, kwin, dcd, nullptr);
+    if (rc) return rc;
+    s.back(cdist, dcd, n);
+    return s.finish();
+}
+
+// ---- the coast setup of one latitude band (sb_band_get_edges_*, sb_band_get_dist_*) ----
+// Fields in the band step's frame, (nx + 2*halo) x (ny + 2*halo) with the interior at (halo, halo); the interior comes out
+// as rows of the whole-grid call's field.  What is read beyond the band's own rows: at a cut side one ghost row (edges),
+// kwin ghost rows of coast (distance); at a pole side nothing -- the kernels clamp (edges) or end their source range
+// (distance) there as on the globe.
+template <typename T>
+int check_band_edges(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lsm, const T *ci, int rule, T *coast) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || halo < 0 || !lsm || !ci || !coast) return fail(c, SB_ERR_ARG, "bad band_get_edges arguments");
+    if (rule < 0 || rule > 1) return fail(c, SB_ERR_ARG, "unknown mask rule");
+    if ((!south || !north) && halo < 1)
+        return fail(c, SB_ERR_ARG, "band_get_edges: a cut side needs halo >= 1 (the Sobel reads the neighbour band's edge row)");
+    return SB_OK;
+}
+
+template <typename T>
+int band_get_edges_dev(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lsm, const T *ci, int rule,
+                       T *coast, void *stream) {
+    int rc = check_band_edges<T>(c, nx, ny, halo, south, north, lsm, ci, rule, coast);
+    if (rc) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, sb_launch_edges_band<T>(lsm, ci, coast, nx, ny, halo, south ? 1 : 0, north ? 1 : 0, rule, st));
+    return SB_OK;
+}
+
+template <typename T>
+int band_get_edges_host(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lsm, const T *ci, int rule,
+                        T *coast) {
+    int rc = check_band_edges<T>(c, nx, ny, halo, south, north, lsm, ci, rule, coast);
+    if (rc) return rc;
+    const size_t n = (size_t)(nx + 2 * halo) * (ny + 2 * halo);
+    Stager s(c);
+    T *dl = s.in(lsm, n), *dc = s.in(ci, n), *dco = s.in((const T *)coast, n);   // (coast in as well: its ghost cells stay)
+    if (s.rc) return s.rc;
+    rc = band_get_edges_dev<T>(c, nx, ny, halo, south, north, dl, dc, rule, dco, nullptr);
+    if (rc) return rc;
+    s.back(coast, dco, n);
+    return s.finish();
+}
+
+template <typename T>
+int check_band_dist(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *coast, const T *mask, const T *lon,
+                    const T *lat, int kwin, T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || halo < 0 || !coast || !mask || !lon || !lat || !cdist)
+        return fail(c, SB_ERR_ARG, "bad band_get_dist arguments");
+    if (kwin < 0)
+        return fail(c, SB_ERR_ARG, "band_get_dist: kwin must be given (the derived half-width needs the global latitudes: "
+                                   "sb_dist_window_* on those)");
+    if (kwin > SB_DIST_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "band_get_dist: window half-width " + std::to_string(kwin) + " exceeds SB_DIST_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
+    if ((!south || !north) && kwin > halo)
+        return fail(c, SB_ERR_ARG, "band_get_dist: a cut side needs kwin <= halo (the window reads kwin ghost rows of coast), got kwin = " +
+                                       std::to_string(kwin) + ", halo = " + std::to_string(halo));
+    const size_t n = (size_t)(nx + 2 * halo) * (ny + 2 * halo);
+    const uintptr_t a = (uintptr_t)coast, b = (uintptr_t)cdist;
+    if (a < b + n * sizeof(T) && b < a + n * sizeof(T))
+        return fail(c, SB_ERR_ARG, "band_get_dist: coast and cdist overlap (a window reads coast's ghost rows, which are the "
+                                   "neighbour band's cells)");
+    return SB_OK;
+}
+
+template <typename T>
+int band_get_dist_dev(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *coast, const T *mask, const T *lon,
+                      const T *lat, T maxdist, int kwin, T *cdist, void *stream) {
+    int rc = check_band_dist<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, kwin, cdist);
+    if (rc) return rc;
+    // the source rows: frame rows f0 .. f0 + nys - 1, the band's own and kwin ghost rows on each cut side; the targets are
+    // source rows r0 .. r1 - 1.  The tables, their key and the traits see those rows' latitudes only.
+    const int k = kwin, ld = nx + 2 * halo;
+    const SbBandRows br = sb_band_rows(ny, halo, south != 0, north != 0, k);
+    const int f0 = br.f0, nys = br.nys, r0 = br.r0, r1 = br.r1;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if ((rc = dist_tables<T>(c, nx, nys, lon, lat + f0, st))) return rc;
+    const T *dphi = (const T *)c->vecs.p, *dlam = dphi + nys;
+    if ((rc = ensure(c, c->coastbits, (size_t)nys * ((nx + 63) / 64) * sizeof(uint64_t)))) return rc;
+    const size_t o = (size_t)f0 * ld + halo;
+    HIPCHK(c, sb_launch_dist_band<T>(coast + o, mask + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx, nys, r0, r1,
+                                     ld, k, maxdist, (uint64_t *)c->coastbits.p, sb_dist_cuts(c->dist_traits, k), st));
+    c->radius_hint = k + 1;
+    return SB_OK;
+}
+
+template <typename T>
+int band_get_dist_host(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *coast, const T *mask, const T *lon,
+                       const T *lat, T maxdist, int kwin, T *cdist) {
+    int rc = check_band_dist<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, kwin, cdist);
+    if (rc) return rc;
+    const size_t n = (size_t)(nx + 2 * halo) * (ny + 2 * halo);
+    Stager s(c);
+    T *dco = s.in(coast, n), *dm = s.in(mask, n), *dcd = s.in((const T *)cdist, n);   // (cdist in as well: its ghost cells stay)
+    if (s.rc) return s.rc;
+    rc = band_get_dist_dev<T>(c, nx, ny, halo, south, north, dco, dm, lon, lat, maxdist, kwin, dcd, nullptr);
     if (rc) return rc;
     s.back(cdist, dcd, n);
     return s.finish();
@@ -1441,6 +1549,24 @@ int sb_last_counters(sb_ctx *c, long long counters[4]) {
     int sb_get_dist_##SFX##_dev(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, const T *lon,             \
                                 const T *lat, T maxdist, int kwin, T *cdist, void *stream) {                        \
         return get_dist_dev<T>(c, nx, ny, coast, mask, lon, lat, maxdist, kwin, cdist, stream);                     \
+    }                                                                                                              \
+    int sb_band_get_edges_##SFX(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lsm,            \
+                                const T *ci, int rule, T *coast) {                                                  \
+        return band_get_edges_host<T>(c, nx, ny, halo, south, north, lsm, ci, rule, coast);                         \
+    }                                                                                                              \
+    int sb_band_get_edges_##SFX##_dev(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lsm,      \
+                                      const T *ci, int rule, T *coast, void *stream) {                              \
+        return band_get_edges_dev<T>(c, nx, ny, halo, south, north, lsm, ci, rule, coast, stream);                  \
+    }                                                                                                              \
+    int sb_band_get_dist_##SFX(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *coast,           \
+                               const T *mask, const T *lon, const T *lat, T maxdist, int kwin, T *cdist) {          \
+        return band_get_dist_host<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, cdist);   \
+    }                                                                                                              \
+    int sb_band_get_dist_##SFX##_dev(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *coast,     \
+                                     const T *mask, const T *lon, const T *lat, T maxdist, int kwin, T *cdist,      \
+                                     void *stream) {                                                                \
+        return band_get_dist_dev<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, cdist,     \
+                                    stream);                                                                        \
     }                                                                                                              \
     int sb_get_edges_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast) {       \
         return get_edges_um_host<T>(c, nx, ny, hi, hj, lf, ci, coast);                                              \

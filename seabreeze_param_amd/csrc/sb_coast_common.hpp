@@ -232,6 +232,31 @@ __device__ __forceinline__ T sb_dist_finish_wave(T a_early, T a_late, T maxdist)
     return m;
 }
 
+// ---- which rows a distance launch writes ----
+// A distance kernel indexes SOURCE rows 0 .. ny-1: the rows of the bit plane and of phi, the rows a window may find a coast
+// cell in (a window that reaches past them finds nothing there: the reference's latitude clamp adds no new sources).
+// A policy G, the kernel's last argument, says which of them are TARGETS and where a cell of the fields lies:
+//   DistWhole  the whole grid: every source row is a target, fields of pitch nx.  An empty type: the whole-grid instances
+//              are the kernels they were before the policy came (same registers, same occupancy).
+//   DistBand   one latitude band of a multi-GPU run in its ghost-celled frame: the source rows are the band's own and the
+//              kwin ghost rows on each cut side (none beyond a pole: there the source range ends as the globe's does), the
+//              targets r0 .. r1-1 are the band's own rows only -- ghost rows are never computed and thrown away -- and
+//              the fields have the frame's pitch.  The host hands every field pointer over at (column 0, source row 0),
+//              so a cell is y * ld + x and three scalars are all the kernels carry.
+// Tiling is from column 0 with one target row per wave under either policy: a wave holds the same 64 targets in a band as
+// on the globe, which is what sb_dist_finish_wave's ballots need for equal bits.
+struct DistWhole {
+    __device__ __forceinline__ int t0() const { return 0; }
+    __device__ __forceinline__ int t1(int ny) const { return ny; }
+    __device__ __forceinline__ size_t at(int x, int y, int nx) const { return (size_t)y * nx + x; }
+};
+struct DistBand {
+    int r0, r1, ld;
+    __device__ __forceinline__ int t0() const { return r0; }
+    __device__ __forceinline__ int t1(int) const { return r1; }
+    __device__ __forceinline__ size_t at(int x, int y, int) const { return (size_t)y * ld + x; }
+};
+
 // ---- what the cuts rest on (SB_CUT_*, sb_dist_plan.hpp; the host sets each only where it is exact) ----
 //   * within one source row a = sp^2 + cos(phis) cos(phit) sin^2(dlam/2) grows with the longitude distance when the
 //     longitudes step one way round the whole circle and the window spans less than half of it (CIRCLE), so of the hits

@@ -11,6 +11,10 @@
 //            window; every other call takes the bit-plane kernels: k_dist_bits[_small] for
 //            k <= 31, k_dist_wide for 32 <= k <= SB_DIST_MAX_WINDOW (71 and 115 times faster than
 //            k_dist at k = 40 and 100 on 2560 x 1920).
+// One latitude band of a multi-GPU run in its ghost-celled frame takes the same kernels: k_edges_band is the Sobel block
+// over the policy EdgesBand, and every distance kernel carries a target policy (DistWhole / DistBand, sb_coast_common.hpp)
+// that says which of its source rows it writes and with which pitch -- a template argument, so the whole-grid instances
+// are what they were.
 // Which kernel runs, and what it may leave out, is decided in sb_dist_plan.hpp; what the kernels share with the UM
 // layout's (the Sobel block, the bit plane, the epilogues, the one-word walk, why each cut is exact) is in
 // sb_coast_common.hpp.
@@ -39,6 +43,25 @@ struct EdgesGrid {
     }
 };
 
+// One latitude band of the global grid in its ghost-celled frame (the band step's layout: pitch nx + 2h, interior at
+// (h, h)): EdgesGrid's SB_BND_GLOBAL rule seen from a band.  Longitude is cyclic by index arithmetic (the east-west ghost
+// columns are never read); at a pole side the row clamps to the band's edge row (the ghost rows there are never read);
+// at a cut side the one ghost row next to the interior is read as the neighbour band's edge row.  Rows further out are
+// staged only for the unwritten rows of a ragged block: they are held at that ghost row, inside the frame.
+template <typename T>
+struct EdgesBand {
+    static constexpr bool tail_by_index = false;
+    int nx, ny, h, ld, south, north, rule;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X = x % nx;
+        X = X < 0 ? X + nx : X;
+        const int Y = y < 0 ? (south ? 0 : -1) : (y >= ny ? (north ? ny - 1 : ny) : y);
+        return (size_t)(Y + h) * ld + h + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + h) * ld + h + x; }
+    __device__ __forceinline__ int land(T l, T c) const { return EdgesGrid<T>{Geo{}, rule}.land(l, c); }
+};
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_edges(const T *__restrict__ lsm, const T *__restrict__ ci,
                                                T *__restrict__ coast, Geo g, int rule) {
@@ -46,27 +69,37 @@ __global__ __launch_bounds__(256) void k_edges(const T *__restrict__ lsm, const 
     sb_edges_block(lsm, ci, coast, s_land, g.nx, g.ny, EdgesGrid<T>{g, rule});
 }
 
-
 template <typename T>
+__global__ __launch_bounds__(256) void k_edges_band(const T *__restrict__ lsm, const T *__restrict__ ci,
+                                                    T *__restrict__ coast, EdgesBand<T> p) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    sb_edges_block(lsm, ci, coast, s_land, p.nx, p.ny, p);
+}
+
+
+// Every distance kernel takes a target policy G (DistWhole, DistBand: sb_coast_common.hpp) as its last argument: ny counts
+// the SOURCE rows (coast or its bit plane, phi), G says which of them are targets and where a cell of coast (k_dist),
+// mask and cdist lies.
+template <typename T, typename G>
 __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const T *__restrict__ mask,
                                               const T *__restrict__ phi, const T *__restrict__ lamf,
-                                              T *__restrict__ cdist, int nx, int ny, int k, T maxdist) {
+                                              T *__restrict__ cdist, int nx, int ny, int k, T maxdist, const G g) {
     extern __shared__ unsigned char sflag[];   // (64+2k) x (SB_DIST_TY+2k) coast flags
     const int W = 64 + 2 * k, HT = SB_DIST_TY + 2 * k;
-    const int x0 = blockIdx.x * 64, y0 = blockIdx.y * SB_DIST_TY;
+    const int x0 = blockIdx.x * 64, y0 = g.t0() + blockIdx.y * SB_DIST_TY;
     for (int i = threadIdx.x; i < W * HT; i += 256) {
         const int r = i / W, c = i - r * W;
         const int ys = y0 - k + r;
         int xs = (x0 - k + c) % nx;
         if (xs < 0) xs += nx;
         unsigned char f = 0;
-        if (ys >= 0 && ys < ny) f = coast[(size_t)ys * nx + xs] > T(0) ? 1 : 0;
+        if (ys >= 0 && ys < ny) f = coast[g.at(xs, ys, nx)] > T(0) ? 1 : 0;
         sflag[i] = f;
     }
     __syncthreads();
     const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
     const int xx = x0 + lx, yy = y0 + ly;
-    if (xx >= nx || yy >= ny) return;
+    if (xx >= nx || yy >= g.t1(ny)) return;
 
     const T big = SbDist<T>::big;
     const T phit = phi[yy], lamt = lamf[xx];
@@ -91,7 +124,7 @@ __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const
         }
     }
     // (the minimum over distances, not over a: one distance per hit)
-    const size_t o = (size_t)yy * nx + xx;
+    const size_t o = g.at(xx, yy, nx);
     sb_dist_write(cdist + o, sb_dist_reset_min(m_early, m_late, maxdist), mask + o);
 }
 
@@ -107,14 +140,14 @@ __global__ __launch_bounds__(256) void k_dist(const T *__restrict__ coast, const
 
 // k_dist_bits as rounds 1-3 had it (every word and table entry from global memory, per target and row): kept for grids
 // narrower than 2k + 1 + 256 columns, where the staged reach of a workgroup would wrap round the seam more than once
-template <typename T>
+template <typename T, typename G>
 __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restrict__ bits, const T *__restrict__ mask,
                                                    const T *__restrict__ phi, const T *__restrict__ lamf,
                                                    const T *__restrict__ shl, const T *__restrict__ chl,
                                                    T *__restrict__ cdist, int nx, int ny, int nw, int k,
-                                                   T maxdist, int nearest) {
+                                                   T maxdist, int nearest, const G g) {
     __shared__ T s_sp2[64], s_cosp[64], s_cost;
-    const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
+    const int xx = blockIdx.x * 256 + threadIdx.x, yy = g.t0() + blockIdx.y;
     const T big = SbDist<T>::big;
     // the row mask of k_dist_bits, but a wave whose reach crosses the seam keeps every row
     uint64_t rowmask;
@@ -132,14 +165,14 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
     }
     // no coast cell within reach of any of the 256 targets: "unreached", before any trigonometry
     if (!__syncthreads_or(rowmask != 0 ? 1 : 0)) {
-        if (xx < nx) cdist[(size_t)yy * nx + xx] = big;
+        if (xx < nx) cdist[g.at(xx, yy, nx)] = big;
         return;
     }
     sb_stage_lat(phi, ny, yy, k, (int)threadIdx.x, s_sp2, s_cosp, &s_cost);
     __syncthreads();
     if (xx >= nx) return;
     if (rowmask == 0) {                                          // wave-uniform: none of this wave's targets is reached
-        cdist[(size_t)yy * nx + xx] = big;
+        cdist[g.at(xx, yy, nx)] = big;
         return;
     }
     const T lamt = lamf[xx];
@@ -163,7 +196,7 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
             else return sin((lamf[xs] - lamt) / T(2));           // l1 - l2
         },
         a_early, a_late);
-    const size_t o = (size_t)yy * nx + xx;
+    const size_t o = g.at(xx, yy, nx);
     sb_dist_write(cdist + o, sb_dist_finish_both(a_early, a_late, maxdist), mask + o);
 }
 
@@ -176,12 +209,12 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
 // WB: the word a target's window (2k+1 columns) and the wave's row mask (2k+1 rows) are held in: 32 bits for k <= 15 (the
 // N1280 grid and coarser: the walk is bound by vector-integer issue, and 64-bit shifts and bit scans cost two to three
 // 32-bit ones), 64 bits beyond
-template <typename T, typename WB>
+template <typename T, typename WB, typename G>
 __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *__restrict__ bits, const T *__restrict__ mask,
                                                    const T *__restrict__ phi, const T *__restrict__ lamf,
                                                    const T *__restrict__ shl, const T *__restrict__ chl,
                                                    T *__restrict__ cdist, int nx, int ny, int nw, int k,
-                                                   T maxdist, int nearest) {
+                                                   T maxdist, int nearest, const G g) {
     __shared__ T s_sp2a[DIST_ROWS][64], s_cospa[DIST_ROWS][64], s_costa[DIST_ROWS];
     // everything the 512 targets of this workgroup read more than once, staged ONCE (round 4: the per-target walk used to
     // fetch two words of the bit plane and two table entries per hit from global memory, row after row -- a chain of
@@ -191,9 +224,9 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     __shared__ uint64_t s_bw[63 + DIST_ROWS - 1][DIST_WORDS];
     __shared__ T s_ta[DIST_SPAN], s_tb[DIST_SPAN];               // fp64: sin, cos of half the folded longitude; fp32: the folded longitude
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 256 + tx;
-    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * DIST_ROWS;
+    const int x0 = blockIdx.x * 256, y0 = g.t0() + blockIdx.y * DIST_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
-    const bool rowok = yy < ny;                                  // (an odd number of rows: the last workgroup's second row)
+    const bool rowok = yy < g.t1(ny);                            // (an odd number of rows: the last workgroup's second row)
     const T big = SbDist<T>::big;
     // Which of the 2k+1 source rows hold any coast cell within reach of this wave's 64 targets?  Lane i ORs the
     // (at most three) words of row yy - k + i that cover columns x0 - k .. x0 + 63 + k; the ballot is a row mask in
@@ -226,7 +259,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     // Four workgroups in five have no coast cell within reach of any of their targets: they write the "unreached"
     // value and leave before any trigonometry.
     if (!__syncthreads_or(rowmask != 0 ? 1 : 0)) {
-        if (xx < nx && rowok) cdist[(size_t)yy * nx + xx] = big;
+        if (xx < nx && rowok) cdist[g.at(xx, yy, nx)] = big;
         return;
     }
     const int L = 2 * k + 1;
@@ -256,7 +289,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     __syncthreads();
     if (xx >= nx || !rowok) return;
     if (rowmask == 0) {                                          // wave-uniform: none of this wave's targets is reached
-        cdist[(size_t)yy * nx + xx] = big;
+        cdist[g.at(xx, yy, nx)] = big;
         return;
     }
     const T *s_sp2 = s_sp2a[ty], *s_cosp = s_cospa[ty];
@@ -318,7 +351,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
         if (nearest && !(s_sp2[k + d] < a_late)) break;
         row(d);
     }
-    const size_t o = (size_t)yy * nx + xx;
+    const size_t o = g.at(xx, yy, nx);
     sb_dist_write(cdist + o, sb_dist_finish_wave(a_early, a_late, maxdist), mask + o);
 }
 
@@ -349,19 +382,19 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
 #define WIDE_WORDS ((WIDE_SPAN + 63) / 64)
 static_assert(WIDE_SLOTS == 64 && WIDE_ROWS == 2, "k_dist_wide: a slot per lane, and the walk names both target rows");
 
-template <typename T>
+template <typename T, typename G>
 __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *__restrict__ bits, const T *__restrict__ mask,
                                                    const T *__restrict__ phi, const T *__restrict__ lamf,
                                                    const T *__restrict__ shl, const T *__restrict__ chl,
                                                    T *__restrict__ cdist, int nx, int ny, int nw, int k,
-                                                   T maxdist, int cuts) {
+                                                   T maxdist, int cuts, const G g) {
     __shared__ uint64_t s_bw[WIDE_SLOTS][WIDE_WORDS];
     __shared__ T s_ta[WIDE_SPAN], s_tb[sizeof(T) == 8 ? WIDE_SPAN : 1];   // fp64: sin, cos of half the folded longitude; fp32: the folded longitude
     __shared__ T s_sp2[WIDE_ROWS][WIDE_SLOTS], s_cosp[WIDE_SLOTS], s_cost[WIDE_ROWS];
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 256 + tx;
-    const int x0 = blockIdx.x * 256, y0 = blockIdx.y * WIDE_ROWS;
+    const int x0 = blockIdx.x * 256, y0 = g.t0() + blockIdx.y * WIDE_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
-    const bool active = xx < nx && yy < ny;                      // (every thread stays for the barriers)
+    const bool active = xx < nx && yy < g.t1(ny);                // (every thread stays for the barriers)
     const int span = 256 + 2 * k, nws = (span + 63) >> 6;
     int c0 = (x0 - k) % nx;                                      // first column in reach, circular
     if (c0 < 0) c0 += nx;
@@ -521,7 +554,7 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
     // One distance per cell, as in k_dist_bits.
     const T m = sb_dist_finish_wave(a_early, a_late, maxdist);
     if (!active) return;
-    const size_t o = (size_t)yy * nx + xx;
+    const size_t o = g.at(xx, yy, nx);
     sb_dist_write(cdist + o, m, mask + o);
 }
 
@@ -534,39 +567,70 @@ hipError_t sb_launch_edges(const T *lsm, const T *ci, T *coast, int nx, int ny, 
 }
 
 template <typename T>
-hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
-                          int nx, int ny, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st) {
+hipError_t sb_launch_edges_band(const T *lsm, const T *ci, T *coast, int nx, int ny, int h, int south, int north, int rule,
+                                hipStream_t st) {
+    const EdgesBand<T> p{nx, ny, h, nx + 2 * h, south, north, rule};
+    hipLaunchKernelGGL(k_edges_band<T>, dim3((nx + 255) / 256, (ny + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lsm, ci, coast, p);
+    return hipGetLastError();
+}
+
+// coast, mask, cdist: the cell of column 0 of source row 0, rows ld apart; ny source rows, of which g's are targets (nt
+// of them: only those are launched)
+template <typename T, typename G>
+static hipError_t sb_launch_dist_g(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl,
+                                   T *cdist, int nx, int ny, int nt, int ld, int k, T maxdist, uint64_t *bits, int cuts,
+                                   const G g, hipStream_t st) {
     if (k > SB_DIST_MAX_WINDOW || !bits) return hipErrorInvalidValue;    // (the C ABI holds k <= SB_DIST_MAX_WINDOW)
     const SbDistKernel kern = sb_dist_kernel(nx, k);
     const int nw = (nx + 63) / 64, nearest = cuts & SB_CUT_NEAREST;
-    if (kern != SbDistKernel::BYTES) sb_launch_coastbits<T>(coast, bits, nx, ny, nw, nx, 0, st);
-    const dim3 gr((nx + 255) / 256, (ny + DIST_ROWS - 1) / DIST_ROWS), bl(256, DIST_ROWS);
+    if (kern != SbDistKernel::BYTES) sb_launch_coastbits<T>(coast, bits, nx, ny, nw, ld, 0, st);
+    const dim3 gr((nx + 255) / 256, (nt + DIST_ROWS - 1) / DIST_ROWS), bl(256, DIST_ROWS);
     switch (kern) {
     case SbDistKernel::BYTES:
-        hipLaunchKernelGGL(k_dist<T>, dim3((nx + 63) / 64, (ny + SB_DIST_TY - 1) / SB_DIST_TY), dim3(256),
-                           (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k), st, coast, mask, phi, lamf, cdist, nx, ny, k, maxdist);
+        hipLaunchKernelGGL((k_dist<T, G>), dim3((nx + 63) / 64, (nt + SB_DIST_TY - 1) / SB_DIST_TY), dim3(256),
+                           (size_t)(64 + 2 * k) * (SB_DIST_TY + 2 * k), st, coast, mask, phi, lamf, cdist, nx, ny, k, maxdist, g);
         break;
     case SbDistKernel::BITS_SMALL:
-        hipLaunchKernelGGL(k_dist_bits_small<T>, dim3((nx + 255) / 256, ny), dim3(256), 0, st, bits, mask, phi, lamf, shl, chl, cdist,
-                           nx, ny, nw, k, maxdist, nearest);
+        hipLaunchKernelGGL((k_dist_bits_small<T, G>), dim3((nx + 255) / 256, nt), dim3(256), 0, st, bits, mask, phi, lamf, shl, chl, cdist,
+                           nx, ny, nw, k, maxdist, nearest, g);
         break;
     case SbDistKernel::BITS32:
-        hipLaunchKernelGGL((k_dist_bits<T, uint32_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
+        hipLaunchKernelGGL((k_dist_bits<T, uint32_t, G>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest, g);
         break;
     case SbDistKernel::BITS64:
-        hipLaunchKernelGGL((k_dist_bits<T, uint64_t>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest);
+        hipLaunchKernelGGL((k_dist_bits<T, uint64_t, G>), gr, bl, 0, st, bits, mask, phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, nearest, g);
         break;
     case SbDistKernel::WIDE:
-        hipLaunchKernelGGL(k_dist_wide<T>, dim3((nx + 255) / 256, (ny + WIDE_ROWS - 1) / WIDE_ROWS), dim3(256, WIDE_ROWS), 0, st, bits, mask,
-                           phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, cuts);
+        hipLaunchKernelGGL((k_dist_wide<T, G>), dim3((nx + 255) / 256, (nt + WIDE_ROWS - 1) / WIDE_ROWS), dim3(256, WIDE_ROWS), 0, st, bits, mask,
+                           phi, lamf, shl, chl, cdist, nx, ny, nw, k, maxdist, cuts, g);
         break;
     }
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
+                          int nx, int ny, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st) {
+    return sb_launch_dist_g<T, DistWhole>(coast, mask, phi, lamf, shl, chl, cdist, nx, ny, ny, nx, k, maxdist, bits, cuts, DistWhole{}, st);
+}
+
+template <typename T>
+hipError_t sb_launch_dist_band(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
+                               int nx, int nys, int r0, int r1, int ld, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st) {
+    if (r0 < 0 || r1 > nys || r1 <= r0 || ld < nx) return hipErrorInvalidValue;
+    return sb_launch_dist_g<T, DistBand>(coast, mask, phi, lamf, shl, chl, cdist, nx, nys, r1 - r0, ld, k, maxdist, bits, cuts,
+                                         DistBand{r0, r1, ld}, st);
+}
+
 template hipError_t sb_launch_edges<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edges_band<float>(const float *, const float *, float *, int, int, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edges_band<double>(const double *, const double *, double *, int, int, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_dist<float>(const float *, const float *, const float *, const float *, const float *, const float *,
                                           float *, int, int, int, float, uint64_t *, int, hipStream_t);
 template hipError_t sb_launch_dist<double>(const double *, const double *, const double *, const double *, const double *,
                                            const double *, double *, int, int, int, double, uint64_t *, int, hipStream_t);
+template hipError_t sb_launch_dist_band<float>(const float *, const float *, const float *, const float *, const float *, const float *,
+                                               float *, int, int, int, int, int, int, float, uint64_t *, int, hipStream_t);
+template hipError_t sb_launch_dist_band<double>(const double *, const double *, const double *, const double *, const double *,
+                                                const double *, double *, int, int, int, int, int, int, double, uint64_t *, int, hipStream_t);

@@ -85,3 +85,24 @@ inline SbDistKernel sb_dist_kernel(int nx, int k) {
     if (nx < 2 * k + 257) return SbDistKernel::BITS_SMALL;
     return k <= 15 ? SbDistKernel::BITS32 : SbDistKernel::BITS64;
 }
+
+// One latitude band of a multi-GPU run in its ghost-celled frame (sb_band_get_dist_*: ny own rows, halo ghost rows on each
+// side, frame row halo is the band's first): which frame rows may hold a SOURCE of a window of half-width k -- the band's
+// own rows and k ghost rows on each cut side; none beyond a pole, where the globe's source range ends too -- and which of
+// those source rows are the targets.  Rows are counted from the first source row on: the kernels, the bit plane, the
+// latitude table and sb_dist_traits see source rows 0 .. nys-1 (frame rows f0 .. f0+nys-1) and nothing else of the frame,
+// so ghost rows beyond a pole and their latitudes are never read.  The caller holds k <= halo wherever a side is a cut.
+struct SbBandRows {
+    int f0, nys;     // first source row in the frame, number of source rows
+    int r0, r1;      // the targets: source rows r0 .. r1-1
+};
+
+inline SbBandRows sb_band_rows(int ny, int halo, bool south, bool north, int k) {
+    SbBandRows b;
+    b.f0 = south ? halo : halo - k;
+    const int f1 = north ? halo + ny : halo + ny + k;
+    b.nys = f1 - b.f0;
+    b.r0 = halo - b.f0;
+    b.r1 = b.r0 + ny;
+    return b;
+}

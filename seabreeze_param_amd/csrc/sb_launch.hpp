@@ -147,6 +147,17 @@ hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *
                           int cuts,                           // SB_CUT_* (sb_dist_plan.hpp); the kernel: sb_dist_kernel(nx, k)
                           hipStream_t st);
 
+// One latitude band in the band step's frame (pitch nx + 2h, interior at (h, h); south / north: the band touches that
+// pole).  Edges: lsm, ci, coast are the frames; SB_BND_GLOBAL's rule, raw reads of the first ghost row at a cut side.
+template <typename T>
+hipError_t sb_launch_edges_band(const T *lsm, const T *ci, T *coast, int nx, int ny, int h, int south, int north, int rule,
+                                hipStream_t st);
+// Distance: coast, mask, cdist point at (column 0, source row 0) of fields of pitch ld; nys source rows (phi and bits
+// have as many), of which r0 .. r1-1 are the targets.
+template <typename T>
+hipError_t sb_launch_dist_band(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
+                               int nx, int nys, int r0, int r1, int ld, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st);
+
 // the UM vn10.7 copy's coast setup on the tdims_l layout (sb_um_coast_kernels.hip): lf, ci, coast are
 // (nx + 2hi) x (ny + 2hj) with hi, hj >= 1; coast's interior is written, its ghost cells are not
 template <typename T>

@@ -362,6 +362,47 @@ class Context:
         self._chk(rc, "sb_get_dist_um_win")
         return cdist
 
+    def band_get_edges(self, lsm_f, ci_f, halo, south, north, rule=1, out=None):
+        """get_edges(rule, SB_BND_GLOBAL) for one latitude band in the band step's frame: lsm_f, ci_f are
+        (ny + 2*halo, nx + 2*halo) with the ghost row next to the interior filled on every cut side (south / north False);
+        ghost rows on a pole side and the east-west ghost columns are never read.  Returns coast on that frame with 0/1 in
+        the interior, the whole-grid call's bits; the ghost cells are those of `out` (zeros without it)."""
+        lsm_f = np.ascontiguousarray(lsm_f)
+        dt = np.dtype(lsm_f.dtype)
+        ci_f = _host(ci_f, dt)
+        ny, nx = lsm_f.shape[0] - 2 * halo, lsm_f.shape[1] - 2 * halo
+        if ci_f.shape != lsm_f.shape:
+            raise ValueError("lsm_f and ci_f must have the same shape")
+        coast = np.zeros_like(lsm_f) if out is None else out
+        if coast.shape != lsm_f.shape or coast.dtype != dt or not coast.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of the input's shape and dtype")
+        rc = getattr(self.lib, f"sb_band_get_edges_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo),
+                                                               C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                                                               _p(lsm_f), _p(ci_f), C.c_int(rule), _p(coast))
+        self._chk(rc, "sb_band_get_edges")
+        return coast
+
+    def band_get_dist(self, coast_f, mask_f, lon, lat_f, halo, south, north, kwin, maxdist=180.0, out=None):
+        """get_dist(kwin) for one latitude band in the band step's frame: coast_f, mask_f (ny + 2*halo, nx + 2*halo), lon
+        (nx), lat_f (ny + 2*halo: one latitude per frame row).  kwin ghost rows of coast_f are read on every cut side
+        (kwin <= halo there), none on a pole side.  Returns the signed distance on the frame, the interior being the
+        whole-grid call's bits; the ghost cells are those of `out` (zeros without it)."""
+        coast_f = np.ascontiguousarray(coast_f)
+        dt = np.dtype(coast_f.dtype)
+        mask_f = _host(mask_f, dt); lon = _host(lon, dt); lat_f = _host(lat_f, dt)
+        ny, nx = coast_f.shape[0] - 2 * halo, coast_f.shape[1] - 2 * halo
+        if mask_f.shape != coast_f.shape or lon.shape != (nx,) or lat_f.shape != (ny + 2 * halo,):
+            raise ValueError("mask_f must have coast_f's shape, lon nx entries, lat_f ny + 2*halo")
+        cdist = np.zeros_like(coast_f) if out is None else out
+        if cdist.shape != coast_f.shape or cdist.dtype != dt or not cdist.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of coast_f's shape and dtype")
+        rc = getattr(self.lib, f"sb_band_get_dist_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo),
+                                                              C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                                                              _p(coast_f), _p(mask_f), _p(lon), _p(lat_f), _CT[dt](maxdist),
+                                                              C.c_int(kwin), _p(cdist))
+        self._chk(rc, "sb_band_get_dist")
+        return cdist
+
     # ------------------------------------------------------------------ device-pointer API
     def sigmoid_dev(self, dtype, nx, ny, ary, sm, stream=None):
         """sm = 1/(1+exp(-std*(ary-r))) on device arrays (raw addresses); enqueues without synchronising."""
@@ -393,6 +434,25 @@ class Context:
         fn = getattr(self.lib, f"sb_get_dist_{_SFX[dt]}_dev")
         self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), _p(coast), _p(mask), _p(lon), _p(lat), _CT[dt](maxdist),
                      C.c_int(kwin), _p(cdist), C.c_void_p(stream) if stream else None), "sb_get_dist_dev")
+
+    def band_get_edges_dev(self, dtype, nx, ny, halo, south, north, lsm_f, ci_f, coast_f, rule=1, stream=None):
+        """band_get_edges on device frames (raw addresses); enqueues without synchronising."""
+        fn = getattr(self.lib, f"sb_band_get_edges_{_SFX[np.dtype(dtype)]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                     _p(lsm_f), _p(ci_f), C.c_int(rule), _p(coast_f), C.c_void_p(stream) if stream else None),
+                  "sb_band_get_edges_dev")
+
+    def band_get_dist_dev(self, dtype, nx, ny, halo, south, north, coast_f, mask_f, lon, lat_f, cdist_f, kwin,
+                          maxdist=180.0, stream=None):
+        """band_get_dist on device frames (raw addresses); lon (nx) and lat_f (ny + 2*halo) are host vectors."""
+        dt = np.dtype(dtype)
+        lon = _host(lon, dt); lat_f = _host(lat_f, dt)
+        if lon.shape != (nx,) or lat_f.shape != (ny + 2 * halo,):
+            raise ValueError("lon must have nx entries, lat_f ny + 2*halo")
+        fn = getattr(self.lib, f"sb_band_get_dist_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                     _p(coast_f), _p(mask_f), _p(lon), _p(lat_f), _CT[dt](maxdist), C.c_int(kwin), _p(cdist_f),
+                     C.c_void_p(stream) if stream else None), "sb_band_get_dist_dev")
 
     def get_edges_um_dev(self, dtype, nx, ny, halo_i, halo_j, landfrac_l, icefrac_l, coast, stream=None):
         """UM-layout get_edges on device arrays (raw addresses); enqueues without synchronising."""
