@@ -22,7 +22,8 @@ module sb_context_mod
   private
   public :: sb_ctx, sb_ensure_ctx, sb_fail, sb_release_ctx
   public :: sb_comm_get_unique_id, sb_comm_init, sb_comm_finalize, sb_comm_active, sb_comm_rank
-  public :: sb_set_static_sigma, sb_set_table_contrast, sb_set_table_window_cache, sb_last_step_report
+  public :: sb_set_static_sigma, sb_set_table_contrast, sb_set_table_contrast_bands, sb_set_table_window_cache
+  public :: sb_last_step_report
   public :: sb_dev_alloc, sb_dev_free, sb_dev_upload, sb_dev_download, sb_device_synchronize
 
   type(c_ptr), save :: sb_ctx = c_null_ptr
@@ -65,6 +66,11 @@ module sb_context_mod
       integer(c_int), value :: on
     end function
     integer(c_int) function c_set_table_contrast(ctx, on) bind(C, name="sb_set_table_contrast")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function c_set_table_contrast_bands(ctx, on) bind(C, name="sb_set_table_contrast_bands")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
       integer(c_int), value :: on
@@ -215,6 +221,17 @@ contains
     rc = c_set_table_contrast(sb_ctx, merge(1_c_int, 0_c_int, on))
     if (rc /= 0) call sb_fail('sb_set_table_contrast', rc)
   end subroutine sb_set_table_contrast
+
+  !> Opt-in, with sb_set_table_contrast: band steps (sb_band_seabreeze_diag) and calls with gathered moments take the
+  !! table contrast too; the ghost width must be at least the largest radius.
+  !! include/seabreeze_hip.h: sb_set_table_contrast_bands.
+  subroutine sb_set_table_contrast_bands(on)
+    logical, intent(in) :: on
+    integer(c_int) :: rc
+    call sb_ensure_ctx()
+    rc = c_set_table_contrast_bands(sb_ctx, merge(1_c_int, 0_c_int, on))
+    if (rc /= 0) call sb_fail('sb_set_table_contrast_bands', rc)
+  end subroutine sb_set_table_contrast_bands
 
   !> Opt-in, with sb_set_table_contrast: a table call keeps every band cell's window (radius, land-side count) while the
   !! coast stands -- k_scan finds a changed mask by content -- and later calls neither build nor search the count table.

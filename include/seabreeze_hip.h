@@ -143,10 +143,34 @@ int  sb_set_static_sigma(sb_ctx *ctx, int on);
    Takes effect for WHOLE SINGLE-DOMAIN calls of the host-model flavour -- sb_seabreeze_diag_*[_dev],
    sb_seabreeze_diag_um_*[_dev] -- with SB_BND_GLOBAL or SB_BND_HALO: six launches (k_scan, k_prep, two table passes, the
    query, k_wind).  Silently ignored, i.e. exactly what runs without it, for the f2py flavour (sb_diag_*, sb_diag_stream_*),
-   for SB_BND_WRAPPER, for band steps (sb_band_seabreeze_diag_*) and while gathered moments are in use.  It is never
+   for SB_BND_WRAPPER, for band steps (sb_band_seabreeze_diag_*) and while gathered moments are in use -- those two have a
+   switch of their own beside this one, sb_set_table_contrast_bands.  It is never
    chosen automatically, whatever the radius hint.  sb_profile_end reports the row pass under [2] and the column pass
    and the query together under [3] for such calls.                                                                 */
 int  sb_set_table_contrast(sb_ctx *ctx, int on);
+/* Opt-in, off by default, beside the table contrast above: the tables for the calls of a multi-band run too.  Takes effect
+   only while sb_set_table_contrast is on, for the host-model flavour with SB_BND_HALO, and only for
+     - band steps, sb_band_seabreeze_diag_*[_dev].  Ahead of the join with the communication stream, as without it:
+       k_scan (publishes the band's moments), k_prep (every call: no stored plan is trusted), k_wind, which leaves its
+       winds in scratch planes.  Behind it: k_merge_moments (the scalars of the gathered moments; dropped where
+       sb_set_static_sigma lets them stand), the two table passes over the band's whole ghost-celled frame, and the
+       query, which applies thresholds and state update itself: 3 + 4 launches.  theta gets the whole swap_bounds on the
+       communication stream -- neighbour rows, pole replication, east-west wrap: one fill kernel -- as the tile kernel's
+       band step does;
+     - diag calls while gathered moments are in use (sb_use_gathered_moments: bands driven from outside, ghost cells
+       filled by the caller): the same seven kernels in one sequence.  sb_profile_end reports the row pass under [2],
+       the column pass and the query together under [3]; k_merge_moments is not timed.
+   With it off, or sb_set_table_contrast off, such calls enqueue exactly what they enqueue without it; whole
+   single-domain calls never depend on it.
+   Ghost cells: the tables know no wrap and no clamp, a window is answered from them while it lies within the frame.  The
+   caller's contract is halo >= the largest radius, with the ghost cells of mask, z and sigma filled as a band step
+   expects them anyway; a band cell whose window needs more than the ghost width takes the global-memory path, bounded
+   by the frame and counted as ever (sb_last_counters) -- where the frame shows one class only the result is NaN, as for
+   every contrast kernel of a band.
+   Ignored for these calls: sb_set_band_order (k_wind always runs ahead of the join) and sb_set_table_window_cache (no
+   window is kept; the stored windows of a whole call are dropped, as after any other call on the context).
+   Results are those of the whole-grid table call on the same cells.  It is never chosen automatically.               */
+int  sb_set_table_contrast_bands(sb_ctx *ctx, int on);
 /* Opt-in, off by default, for the table contrast above: keep every band cell's window while the coast stands.  The radius
    of a cell's window and the land-side cells in it follow from the land-side plane (mask >= 0) and the geometry alone, and
    mask -- the signed coast distance -- changes only when the host model's ice mask does.  A table call that searches

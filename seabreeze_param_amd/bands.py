@@ -98,17 +98,24 @@ class BandRunner:
     """Owns one rank's device-resident fields and runs seabreeze_diag steps on them."""
 
     def __init__(self, ctx: _hip.Context, torch, dist, rank: int, world: int, nx: int, ny: int, nz: int,
-                 halo: int, dtype=np.float64, comm: str = "torch", rows=None, static_sigma: bool = False):
+                 halo: int, dtype=np.float64, comm: str = "torch", rows=None, static_sigma: bool = False,
+                 table_contrast: bool = False):
         """comm="torch": ghost rows and moments travel through torch.distributed (`dist`, any backend);
         comm="native": through the library's own RCCL communicator (ctx.comm_init must have run):
         ncclSend/ncclRecv + ncclAllGather enqueued on the compute stream by two C-ABI calls.
         static_sigma=True (opt-in, sb_set_static_sigma): sigma's statistics are formed and gathered in the first
-        step only; later steps run without the moments pass, the all-gather and the merge."""
+        step only; later steps run without the moments pass, the all-gather and the merge.
+        table_contrast=True (opt-in, sb_set_table_contrast and sb_set_table_contrast_bands): every step takes the contrast
+        from device-wide summed-area tables over this band's frame, radii up to `halo` at a cost that does not depend on
+        the radius; `halo` must be at least the largest radius."""
         assert comm in ("torch", "native")
         self.static_sigma = bool(static_sigma)
         self._stats_done = False
         self._shared_runtime = None
         ctx.set_static_sigma(self.static_sigma)
+        if table_contrast:                              # (off: the context's switches stay as the caller left them)
+            ctx.set_table_contrast(True)
+            ctx.set_table_contrast_bands(True)
         self.comm = comm
         self.ctx, self.torch, self.dist = ctx, torch, dist
         self.rank, self.world = rank, world

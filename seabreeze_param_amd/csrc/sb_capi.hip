@@ -139,6 +139,7 @@ struct sb_ctx {
     int no_wind_pairs = 0;              // sb_set_wind_pairs(ctx, 0): k_wind walks one cell per lane everywhere
     int last_wind_pairs = 0;            // the last call's k_wind was the paired instance (sb_last_wind_pairs)
     int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
+    int table_bands = 0;                // sb_set_table_contrast_bands(ctx, 1): with it, band steps and calls with gathered moments too
     // sb_set_table_window_cache(ctx, 1): a table call keeps every band cell's window in W while the coast stands.  tabc: what
     // the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half (sb_table_cache_report)
     int table_cache = 0;
@@ -373,6 +374,8 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     in.plan_use = c->plan_use != 0; in.segs_built = c->segs_built;
     in.scan_wgs = sb_scan_workgroups((unsigned)g.nyh * (unsigned)g.nw, c->ncu);
     in.table = c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0;
+    // ... and the tables for a band phase or a call with gathered moments: a switch of its own beside that one, ghost cells only
+    in.band_table = in.table && c->table_bands != 0 && g.bnd == BND_HALO && (phases != 3 || c->gathered != nullptr);
     const SbDiagPlan plan = sb_plan_diag(in);
     if (plan.table) {
         // 20 bytes per frame cell, and the row pass' block sums: 20 bytes per column and block of SB_TAB_RB rows
@@ -534,7 +537,9 @@ int band_diag_dev(sb_ctx *c, T timestep_s, int tn, int nx, int ny, int nz, int h
     // arithmetic (Geo::band) -- no fill kernel on the communication stream, three launches per band step (round 3: four,
     // and the fill, running behind the caller's stream's kernels rather than beside them, held the join up).  The tile
     // kernel (double precision, radii beyond 16) reads every ghost cell as filled: the whole swap_bounds for it.
-    const bool folds = sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
+    // The table contrast (sb_set_table_contrast_bands) builds its tables over the whole frame: the whole swap_bounds too.
+    const bool tables = c->table_contrast != 0 && c->table_bands != 0;
+    const bool folds = !tables && sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
     const int band_geo = folds ? (GEO_BAND_EW | (c->rank == 0 ? GEO_BAND_SOUTH : 0) | (c->rank == c->nranks - 1 ? GEO_BAND_NORTH : 0)) : 0;
     rc = folds ? exchange_rows_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream)
                : swap_bounds_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream);
@@ -1983,6 +1988,12 @@ int sb_set_static_sigma(sb_ctx *c, int on) {
 int sb_set_table_contrast(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->table_contrast = on ? 1 : 0;
+    return SB_OK;
+}
+
+int sb_set_table_contrast_bands(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->table_bands = on ? 1 : 0;
     return SB_OK;
 }
 

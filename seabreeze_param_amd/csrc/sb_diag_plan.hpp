@@ -15,7 +15,7 @@ enum SbStatsSrc { SB_STATS_NONE, SB_STATS_PARTIALS, SB_STATS_GATHERED };
 inline int sb_pick_halo(int r) { return r <= 8 ? 8 : r <= 16 ? 16 : r <= 24 ? 24 : 32; }
 // A strip kernel that does k_prep's work merges k_scan's partial moments with one thread each.  k_scan runs at most one
 // workgroup per compute unit, so the bound cannot fire on any device; it is part of the one predicate (`folds`) all the same.
-enum { SB_FOLD_MAX_PARTS = 1024, SB_PLAN_MAX_STEPS = 6 };
+enum { SB_FOLD_MAX_PARTS = 1024, SB_PLAN_MAX_STEPS = 7 };
 
 // what sb_strip_shape, sb_strip32_shape and sb_thc_tile_shape answer for the domain (sb_contrast_shapes, sb_launch.hpp)
 struct SbShapes {
@@ -39,6 +39,8 @@ struct SbPlanIn {
     SbShapes shapes;
     bool table;                     // sb_set_table_contrast is on and the call is one it serves as far as the caller can tell: host-model
                                     // flavour, SB_BND_GLOBAL or SB_BND_HALO, Geo::band == 0 (whole call, no gathered moments: checked here)
+    bool band_table;                // sb_set_table_contrast_bands is on beside it and the call is one that switch serves as far as the caller
+                                    // can tell: host-model flavour, SB_BND_HALO, Geo::band == 0 (a band phase or gathered moments: checked here)
 };
 
 // the contrast kernel of the call and its block / tile grid
@@ -108,7 +110,12 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
     // k_wind ahead of the join with the communication stream and applies the update in the contrast kernel; its
     // single-domain order (sb_set_band_order) was measured and is slower.
     const bool whole = in.phases == 3 && !in.gathered;
-    const bool late_wind = in.band_late_wind && in.gathered && folds;
+    // Opt-in (sb_set_table_contrast): the contrast of every band cell from device-wide summed-area tables, whatever its
+    // radius -- whole single-domain host-model calls; with sb_set_table_contrast_bands beside it, band steps and calls with
+    // gathered moments of that flavour too (`table` alone never changes those)
+    const bool band_table = in.band_table && in.table && !whole && in.t0_fly;
+    p.table = (in.table && whole && in.t0_fly) || band_table;
+    const bool late_wind = in.band_late_wind && in.gathered && folds && !band_table;    // (sb_set_band_order: not for the tables)
     p.wind_scratch = !(whole || late_wind);
     SbStep *contrast = nullptr;
     auto add = [&p](SbKernel k, int prof, bool stats = false, int nparts = 0) -> SbStep & {
@@ -117,12 +124,28 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
         s.stats = stats ? SB_STATS_PARTIALS : SB_STATS_NONE; s.nparts = nparts;
         return s;
     };
-    // Opt-in (sb_set_table_contrast), whole single-domain host-model calls only: the contrast of every band cell from
-    // device-wide summed-area tables, whatever its radius.  k_prep merges the moments, publishes the scalars the row pass
-    // forms t0 with and compacts the segment lists the query takes its band cells from.  A profiled call times the row
-    // pass in k_t0's pair (the host-model flavour has no k_t0), the column pass and the query together in the contrast's.
-    p.table = in.table && whole && in.t0_fly;
-    if (p.table) {
+    // A whole table call: k_prep merges the moments, publishes the scalars the row pass forms t0 with and compacts the
+    // segment lists the query takes its band cells from.  A profiled call times the row pass in k_t0's pair (the host-model
+    // flavour has no k_t0), the column pass and the query together in the contrast's.
+    if (band_table) {
+        // A band step / a call with gathered moments on the tables.  Ahead of the join, as without them: k_scan (publishes
+        // the band's moments), k_prep (every call: no stored plan is trusted), k_wind to the scratch planes.  Behind it:
+        // k_merge_moments leaves the scalars the row pass reads (dropped when they stand), the two passes over the whole
+        // ghost-celled frame, and the query, which applies thresholds and state update itself.
+        if (ph1) {
+            const bool own = (!in.gathered || in.moments_out) && !reuse, publishes = own && in.gathered;
+            add(SB_K_SCAN, SB_PROF_SCAN, own).publish = publishes;
+            add(SB_K_PREP, SB_PROF_PREP, own && !publishes, own && !publishes ? in.scan_wgs : 0);
+            add(SB_K_WIND, SB_PROF_WIND);
+        }
+        if (ph2) {
+            if (in.gathered && !reuse) add(SB_K_MERGE, SB_PROF_NONE).stats = SB_STATS_GATHERED;
+            add(SB_K_TABLE_ROWS, SB_PROF_T0);
+            add(SB_K_TABLE_COLS, SB_PROF_THC);
+            contrast = &add(SB_K_CONTRAST, SB_PROF_THC);
+            contrast->table = true;
+        }
+    } else if (p.table) {
         add(SB_K_SCAN, SB_PROF_SCAN, !reuse);
         add(SB_K_PREP, SB_PROF_PREP, !reuse, reuse ? 0 : in.scan_wgs);
         add(SB_K_TABLE_ROWS, SB_PROF_T0);

@@ -13,7 +13,11 @@
 //                  rows would leave nxh threads alive; a march of whole column strips a few hundred waves.)
 //   k_table_query  one wave per listed 64-cell segment (k_prep's lists, as k_wind), band lanes active: the smallest radius
 //                  whose square holds both classes by galloping and bisection on the count table alone, then the two
-//                  window sums, the means, thc.  Cells the tables cannot answer take contrast_global, here.
+//                  window sums, the means, thc.  Cells the tables cannot answer take contrast_global, here.  Two
+//                  instances: where k_wind follows with the update (a whole call) the query leaves thc; where k_wind ran
+//                  ahead and left its winds in the scratch planes (a band step, gathered moments:
+//                  sb_set_table_contrast_bands) it applies thresholds and state update to every band cell itself, the
+//                  four state loads issued ahead of the count probes.
 // The sums are wrapping unsigned adds: a window sum is the exact sum of once-rounded values, whatever the launch geometry.
 //
 // sb_set_table_window_cache: the radius of a band cell's window and the land-side cells in it follow from the land-side
@@ -213,7 +217,7 @@ __device__ __forceinline__ V tab_sum(const V *t, const Geo &g, const TabWin &w) 
     return s;
 }
 
-template <typename T>
+template <typename T, bool UPD>                          // UPD: the query applies the update (!job.wind_final)
 __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, SbTables tb) {
     const Geo g = job.g;
     const int lane = threadIdx.x & 63;
@@ -241,6 +245,9 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
         bool stored = false;                                 // this lane's cell is answered from its stored window
         if ((cur.word >> lane) & 1ull) {                     // band bits are set for interior cells of processed rows only
             const unsigned o = (unsigned)y * (unsigned)g.nx + (unsigned)x;
+            // this call's winds (k_wind left them) and the carried state travel under the gallop and the bisection
+            SbCellState<T> cst{};
+            if constexpr (UPD) cst = sb_trigger_load<T>(job, (size_t)o);
             // the largest radius the tables answer for this cell: the reach of the format; the frame (no wrap, no clamp:
             // strip_frame_reach) or the circle (2 nn + 1 <= nx)
             const int cap = min(SB_TAB_REACH, limited ? strip_frame_reach(g, x, y) : (g.nx - 1) / 2);
@@ -275,7 +282,9 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
                 auto to_f64 = [](long long v) { return __builtin_fma((double)(int)(v >> 32), 0x1p32, (double)(unsigned)v); };
                 const double dnl = (double)nl, dns = (double)((2 * hi + 1) * (2 * hi + 1) - nl);
                 const double ml = to_f64(TL) * sb_inv(dnl), ms = to_f64(TS) * sb_inv(dns);
-                job.thc[o] = mul * (T)((ml - ms) * (1.0 / (double)(1ll << SB_TAB_FB)));          // ref :216; k_wind applies :235-266
+                const T n_thc = mul * (T)((ml - ms) * (1.0 / (double)(1ll << SB_TAB_FB)));        // ref :216
+                if constexpr (UPD) sb_trigger_update<T>(job, (size_t)o, n_thc, cst);               // ref :235-266
+                else job.thc[o] = n_thc;                                                           // (k_wind applies them)
                 nnmax = hi;
             } else {
                 // beyond the reach, wider than the circle, or one class as far as the search may go: the global-memory
@@ -286,7 +295,8 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
                 const T cg = contrast_global(job, x, y, capg, sd, rr, nnmax, one_class);
                 atomicAdd(&job.counters[0], 1);
                 if (one_class) atomicAdd(&job.counters[1], 1);
-                job.thc[o] = mul * cg;
+                if constexpr (UPD) sb_trigger_update<T>(job, (size_t)o, mul * cg, cst);
+                else job.thc[o] = mul * cg;
             }
             flag = (x >> job.thc_txs) * job.tile_sx + (y / job.thc_ty) * job.tile_sy + job.tile_off;
         }
@@ -324,9 +334,11 @@ hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st
 }
 template <typename T>
 hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st) {
-    if (!job.wind_final) return hipErrorInvalidValue;   // (the update is k_wind's: the plan sees to it)
     static_assert(4 * (TAB_QUERY_NT / SB_WAVE) == SB_TAB_QUERY_WAVES_PER_CU, "the report has a slot per wave");
-    hipLaunchKernelGGL(k_table_query<T>, dim3(ncu * 4), dim3(TAB_QUERY_NT), 0, st, job, tb);
+    // (the plan decides whose the update is: k_wind's behind the query, or the query's from the winds k_wind left)
+    if (job.wind_final) hipLaunchKernelGGL((k_table_query<T, false>), dim3(ncu * 4), dim3(TAB_QUERY_NT), 0, st, job, tb);
+    else if (job.nws && job.nwd) hipLaunchKernelGGL((k_table_query<T, true>), dim3(ncu * 4), dim3(TAB_QUERY_NT), 0, st, job, tb);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 template hipError_t sb_launch_table_rows<float>(const DiagJob<float> &, const SbTables &, hipStream_t);

@@ -168,6 +168,11 @@ class Context:
         to 127 at a cost that does not depend on the radius (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_table_contrast(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast")
 
+    def set_table_contrast_bands(self, on: bool):
+        """Opt-in, with set_table_contrast: band steps and diag calls with gathered moments take the table contrast too;
+        the ghost width must cover the largest radius (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_table_contrast_bands(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast_bands")
+
     def set_table_window_cache(self, on: bool):
         """Opt-in, with set_table_contrast: a table call keeps every band cell's window while the coast stands; the same
         bits, less work per call (include/seabreeze_hip.h)."""
