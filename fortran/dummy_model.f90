@@ -35,6 +35,12 @@
 !                                routines, then, in this process, of three bands in frames cut here
 !                                (band_get_edges, band_get_dist); stops at the first cell that differs, prints
 !                                "bandsetup ok" otherwise.  No steps are run, output.bin holds cdist only
+!     radius                     search_radius: the window radius of every band cell of the grid (the whole-grid routine,
+!                                periodic and clamped), then of three bands in frames of halo_size ghost cells cut here
+!                                (band_search_radius): a band's cell must have the grid's radius where that is within
+!                                reach of its ghost rows, -1 where it is not; stops at the first cell that violates
+!                                this, prints "radius ok" otherwise.  No steps are run; output.bin holds cdist, then
+!                                the grid's radius plane (nx,ny) as 32-bit integers
 ! The tests write input.bin with numpy and compare output.bin with the CPU oracle.
 !
 ! Two deliberate differences from the outline, both documented in INTEGRATION.md:
@@ -65,7 +71,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | bandsetup | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -114,6 +120,8 @@ program dummy_model
     call check_status()
   case ('bandsetup')
     call run_band_setup()
+  case ('radius')
+    call run_radius()
   case default
     error stop 'unknown mode'
   end select
@@ -197,6 +205,58 @@ contains
     end do
     print '(a)', 'bandsetup ok'
   end subroutine run_band_setup
+
+  !---------------------------------------------------------------------------
+  ! The window radii of the grid and of three bands of it (the cuts of run_band_setup), each band in a frame of
+  ! halo_size ghost cells whose rows on a cut side are the neighbours' rows of the distance field (what swap_bounds
+  ! delivers); ghost rows beyond a pole and the east-west ghost columns are NaN: they are never read.  A band's window
+  ! may use its ghost rows and no more: reach = halo_size + the distance to the nearest cut side.
+  !---------------------------------------------------------------------------
+  subroutine run_radius()
+    use, intrinsic :: ieee_arithmetic, only : ieee_value, ieee_quiet_nan
+    use sea_breeze_diag_mod, only : get_edges, get_dist, search_radius, band_search_radius
+    integer :: h, b, r0, r1, nyl, i, j, lo, hi, cuts(4), reach, want
+    integer(c_int), allocatable :: rad(:,:), rb(:,:)
+    integer(c_long_long) :: summ(4), sb(4)
+    real :: nan
+    real, allocatable :: mf(:,:)
+    h = halo_size
+    nan = ieee_value(nan, ieee_quiet_nan)
+    call get_edges(mask, ice_frac, land_frac, h)
+    call get_dist(mask, land_frac, lon, lat, 180, cdist, h)
+    write (uout) cdist
+    allocate(rad(nx, ny))
+    call search_radius(cdist, 180., rad, summ, 0)
+    if (summ(1) /= count(rad /= 0) .or. summ(2) /= count(rad > 0) .or. summ(3) /= count(rad == -1) .or. &
+        summ(4) /= max(maxval(rad), 0)) error stop 'radius: summary does not describe the plane'
+    cuts = [0, ny/3 - 1, 2*(ny/3) + 2, ny]
+    if (cuts(2) < 1 .or. cuts(3) <= cuts(2) .or. cuts(3) >= ny) error stop 'radius: grid too small for three bands'
+    do b = 1, 3
+      r0 = cuts(b); r1 = cuts(b+1); nyl = r1 - r0                ! rows r0+1 .. r1 (1-based) of the grid
+      allocate(mf(nx+2*h, nyl+2*h), rb(nx, nyl))
+      mf = nan
+      lo = max(r0 - h, 0); hi = min(r1 + h, ny)                  ! the grid rows lo+1 .. hi lie in the frame
+      mf(1+h:nx+h, lo-r0+h+1:hi-r0+h) = cdist(:, lo+1:hi)
+      call band_search_radius(mf, 180., rb, sb, h, b == 1, b == 3)
+      do j = 1, nyl
+        reach = huge(reach)
+        if (b /= 1) reach = min(reach, j - 1 + h)
+        if (b /= 3) reach = min(reach, nyl - j + h)
+        do i = 1, nx
+          want = rad(i, r0+j)
+          if (want > reach) want = -1
+          if (rb(i, j) /= want) then
+            print '(a,i0,a,i0,a,i0,a,i0,a,i0)', 'radius: band ', b, ' differs at ', i, ',', r0 + j, ': ', rb(i, j), ' /= ', want
+            error stop 'radius: band_search_radius violates the band property'
+          end if
+        end do
+      end do
+      if (sb(1) /= count(rb /= 0) .or. sb(3) /= count(rb == -1)) error stop 'radius: band summary does not describe the plane'
+      deallocate(mf, rb)
+    end do
+    print '(a)', 'radius ok'
+    write (uout) rad
+  end subroutine run_radius
 
   !---------------------------------------------------------------------------
   ! fields resident on the device: static ones go up once, per step theta, u, v

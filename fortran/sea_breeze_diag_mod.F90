@@ -43,6 +43,7 @@ module sea_breeze_diag_mod
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
   public :: get_edges_um, get_dist_um, get_dist_um_win
   public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
+  public :: search_radius, band_search_radius
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
 #ifdef SB_REAL8
@@ -62,6 +63,8 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f64"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f64_dev"
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f64_dev"
+#define SB_SEARCH_RADIUS      "sb_search_radius_f64"
+#define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f64"
 #else
   integer, parameter :: rk = c_float
 #define SB_SEABREEZE_DIAG "sb_seabreeze_diag_f32"
@@ -79,6 +82,8 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f32"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f32_dev"
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f32_dev"
+#define SB_SEARCH_RADIUS      "sb_search_radius_f32"
+#define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f32"
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
@@ -214,6 +219,26 @@ module sea_breeze_diag_mod
       integer(c_int), value :: nx, ny, halo, south, north, kwin
       real(rk), value :: maxdist
       real(rk), intent(in) :: lon(*), lat(*)
+    end function
+    integer(c_int) function c_search_radius(ctx, nx, ny, halo, bnd, mask, maxdist, radius, summary, hist, nhist) &
+        bind(C, name=SB_SEARCH_RADIUS)
+      import :: c_ptr, c_int, c_long_long, rk
+      type(c_ptr), value :: ctx, hist
+      integer(c_int), value :: nx, ny, halo, bnd, nhist
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: mask(*)
+      integer(c_int), intent(inout) :: radius(*)
+      integer(c_long_long), intent(inout) :: summary(4)
+    end function
+    integer(c_int) function c_band_search_radius(ctx, nx, ny, halo, south, north, mask, maxdist, radius, summary, hist, nhist) &
+        bind(C, name=SB_BAND_SEARCH_RADIUS)
+      import :: c_ptr, c_int, c_long_long, rk
+      type(c_ptr), value :: ctx, hist
+      integer(c_int), value :: nx, ny, halo, south, north, nhist
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: mask(*)
+      integer(c_int), intent(inout) :: radius(*)
+      integer(c_long_long), intent(inout) :: summary(4)
     end function
   end interface
 
@@ -492,6 +517,50 @@ contains
     real, intent(inout), contiguous :: cdist(:,:)
     call band_get_dist_r(coast, landfrac, lon, lat, real(maxdist), cdist, halo_size, south, north, kwin)
   end subroutine band_get_dist_i
+
+  !---------------------------------------------------------------------------
+  ! search_radius: the radius of every band cell's expanding window (ref: generic/sea_breeze_diag.f90:188-214) from the
+  ! signed coast distance alone, before any seabreeze_diag call -- call it after get_dist, and again when the ice mask
+  ! changes.  mask is (nx+2*halo_size, ny+2*halo_size): halo_size = 0 is the whole globe (longitude periodic, latitude
+  ! clamped), halo_size > 0 a ghost-celled frame whose windows end at the frame.  radius (nx, ny): 0 off the band, the
+  ! radius, or -1 where no window up to seabreeze_diag's own limit holds both classes (it returns NaN there).  summary:
+  ! band cells, those with a radius, those with -1, the largest radius.  band_search_radius: one latitude band in the
+  ! band step's frame (south / north: the band touches that pole); the ghost rows of mask on a cut side are read as
+  ! swap_bounds left them, and with halo_size >= the whole grid's summary(4) the interior equals the whole grid's rows.
+  !---------------------------------------------------------------------------
+  subroutine search_radius(mask, maxdist, radius, summary, halo_size)
+    real, intent(in), contiguous :: mask(:,:)
+    real, intent(in) :: maxdist
+    integer(c_int), intent(inout), contiguous :: radius(:,:)
+    integer(c_long_long), intent(out) :: summary(4)
+    integer, intent(in) :: halo_size
+    integer(c_int) :: nx, ny, rc, bnd
+    nx = size(mask, 1) - 2*halo_size; ny = size(mask, 2) - 2*halo_size
+    if (halo_size < 0 .or. nx < 1 .or. ny < 1 .or. any(shape(radius) /= [nx, ny])) &
+      call fail('search_radius: mask must be (nx+2*halo_size, ny+2*halo_size), radius (nx, ny)', 1_c_int)
+    bnd = SB_BND_GLOBAL
+    if (halo_size > 0) bnd = SB_BND_HALO
+    call ensure_ctx()
+    rc = c_search_radius(ctx, nx, ny, int(halo_size, c_int), bnd, mask, real(maxdist, rk), radius, summary, c_null_ptr, 0_c_int)
+    if (rc /= 0) call fail('search_radius', rc)
+  end subroutine search_radius
+
+  subroutine band_search_radius(mask, maxdist, radius, summary, halo_size, south, north)
+    real, intent(in), contiguous :: mask(:,:)
+    real, intent(in) :: maxdist
+    integer(c_int), intent(inout), contiguous :: radius(:,:)
+    integer(c_long_long), intent(out) :: summary(4)
+    integer, intent(in) :: halo_size
+    logical, intent(in) :: south, north
+    integer(c_int) :: nx, ny, rc
+    nx = size(mask, 1) - 2*halo_size; ny = size(mask, 2) - 2*halo_size
+    if (halo_size < 0 .or. nx < 1 .or. ny < 1 .or. any(shape(radius) /= [nx, ny])) &
+      call fail('band_search_radius: mask must be (nx+2*halo_size, ny+2*halo_size), radius (nx, ny)', 1_c_int)
+    call ensure_ctx()
+    rc = c_band_search_radius(ctx, nx, ny, int(halo_size, c_int), merge(1_c_int, 0_c_int, south), &
+                              merge(1_c_int, 0_c_int, north), mask, real(maxdist, rk), radius, summary, c_null_ptr, 0_c_int)
+    if (rc /= 0) call fail('band_search_radius', rc)
+  end subroutine band_search_radius
 
   ! Device-resident forms: the fields are device pointers (sb_context_mod::sb_dev_alloc) in the same frames, lon and lat
   ! host arrays; the calls only enqueue on the context's stream.

@@ -493,6 +493,64 @@ int sb_band_get_dist_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, i
                          float maxdist, int kwin, float *cdist, void *stream);
 
 /* -------------------------------------------------------------------------------- */
+/* search_radius -- every band cell's window radius, from mask alone                  */
+/* no counterpart in the reference: the radius is the final nn of its expanding       */
+/*           window, ref: generic/sea_breeze_diag.f90:188-214                         */
+/* A setup product like get_dist: it changes when mask does (the ice mask), not per   */
+/* step.  It tells, before any diag call, what sb_last_counters [0], [2], [3] would   */
+/* say after one -- and that per cell: the ghost width a band run needs, which        */
+/* contrast kernel the radii call for, where a window never finds a second class.     */
+/* mask: (nx+2*halo, ny+2*halo), interior at (halo, halo); halo must be 0 unless      */
+/* bnd == SB_BND_HALO.  Cells are classified as a diag call classifies them, in the   */
+/* working precision: a band cell is one with !(|mask| > maxdist) (NaN: a band cell), */
+/* land side is mask >= 0 (-0.0: land, NaN: sea side); with SB_BND_WRAPPER the last   */
+/* row holds no band cell.  radius (nx, ny) int32, interior layout, may be NULL:      */
+/*   0   not a band cell;                                                             */
+/*   nn  the smallest nn >= 1 for which the cells (x+dx, y+dy), |dx|, |dy| <= nn,      */
+/*       that exist under the boundary rule hold both classes (longitude periodic,    */
+/*       latitude clamped; SB_BND_WRAPPER: offsets -1 and nx-1 both read column 0,    */
+/*       the centre of a cell in the last column included; SB_BND_HALO: the frame);   */
+/*   -1  no such nn up to the diag call's own cap -- nx+ny, and for SB_BND_HALO the    */
+/*       frame's reach (ghost width plus distance to the nearest interior edge) if     */
+/*       smaller: the cells a diag call returns NaN for and counts as one-class.       */
+/* summary[4], may be NULL: [0] band cells, [1] those with a radius, [2] those with   */
+/* -1, [3] the largest radius (0: none).  hist, optional (NULL or nhist == 0, else     */
+/* nhist >= 2): hist[0] the -1 cells, hist[k] band cells of radius k for               */
+/* 1 <= k < nhist-1, hist[nhist-1] those of radius >= nhist-1.                         */
+/* The band forms take the band step's frame (sb_band_seabreeze_diag_*,               */
+/* sb_band_get_dist_*): south / north as in sb_fill_ghosts_*; on cut sides the ghost  */
+/* rows of mask are read as the caller filled them and bound the reach; ghost rows    */
+/* beyond a pole and the east-west ghost columns are never read (clamp; periodic by   */
+/* index).  With halo >= the whole grid's summary[3] a band's interior equals its     */
+/* rows of the whole-grid SB_BND_GLOBAL plane.                                        */
+/* No side effects on diag state: the call has a grow-only workspace of its own and   */
+/* leaves planes, plans, lists, stored windows, counters and reports of the context   */
+/* alone; a diag call after it enqueues and returns what it would have without it.    */
+/* Host forms stage, synchronise and return the results.  The _dev forms take device  */
+/* pointers for mask, radius, summary and hist, zero summary and hist themselves on   */
+/* the stream, enqueue three kernels there and do not synchronise.                    */
+/* SB_ERR_ARG: NULL mask; radius, summary and hist all NULL; bad sizes (rows wider     */
+/* than 65535 cells included); halo != 0 with another rule than SB_BND_HALO;           */
+/* nhist == 1.                                                                        */
+/* -------------------------------------------------------------------------------- */
+int sb_search_radius_f64(sb_ctx *ctx, int nx, int ny, int halo, int bnd, const double *mask, double maxdist,
+                         int *radius, long long summary[4], long long *hist, int nhist);
+int sb_search_radius_f32(sb_ctx *ctx, int nx, int ny, int halo, int bnd, const float *mask, float maxdist,
+                         int *radius, long long summary[4], long long *hist, int nhist);
+int sb_search_radius_f64_dev(sb_ctx *ctx, int nx, int ny, int halo, int bnd, const double *mask, double maxdist,
+                         int *radius, long long summary[4], long long *hist, int nhist, void *stream);
+int sb_search_radius_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int bnd, const float *mask, float maxdist,
+                         int *radius, long long summary[4], long long *hist, int nhist, void *stream);
+int sb_band_search_radius_f64(sb_ctx *ctx, int nx, int ny, int halo, int south, int north, const double *mask,
+                         double maxdist, int *radius, long long summary[4], long long *hist, int nhist);
+int sb_band_search_radius_f32(sb_ctx *ctx, int nx, int ny, int halo, int south, int north, const float *mask,
+                         float maxdist, int *radius, long long summary[4], long long *hist, int nhist);
+int sb_band_search_radius_f64_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north, const double *mask,
+                         double maxdist, int *radius, long long summary[4], long long *hist, int nhist, void *stream);
+int sb_band_search_radius_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, int north, const float *mask,
+                         float maxdist, int *radius, long long summary[4], long long *hist, int nhist, void *stream);
+
+/* -------------------------------------------------------------------------------- */
 /* get_edges -- UM vn10.7 layout (tdims_l), for curvilinear / rotated-pole grids      */
 /* replaces: get_edges(mask, icefrac, landfrac)                                      */
 /*           ref: UM/vn10.7/sea_breeze_diag.F90:328-446 (get_edges)                  */

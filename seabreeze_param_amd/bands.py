@@ -107,7 +107,9 @@ class BandRunner:
         step only; later steps run without the moments pass, the all-gather and the merge.
         table_contrast=True (opt-in, sb_set_table_contrast and sb_set_table_contrast_bands): every step takes the contrast
         from device-wide summed-area tables over this band's frame, radii up to `halo` at a cost that does not depend on
-        the radius; `halo` must be at least the largest radius."""
+        the radius; `halo` must be at least the largest radius -- the whole-grid Context.search_radius call's
+        summary["max_radius"] for this mask and maxdist, or, without any rank holding the globe, the ghost width at which
+        check_halo() reports zero band cells without a window on every rank."""
         assert comm in ("torch", "native")
         self.static_sigma = bool(static_sigma)
         self._stats_done = False
@@ -232,6 +234,24 @@ class BandRunner:
             self._fill_ghosts(a)
         self.torch.cuda.synchronize()                  # (torch wrote them; the library reads them on streams of its own)
         self.ctx.synchronize()
+
+    def check_halo(self, maxdist: float = 180.0):
+        """After setup_mask / upload_static: this rank's (largest radius, band cells without a window) from self.mask
+        alone (band_search_radius on the band's frame; the whole-grid call where one rank owns the globe).  The ghost
+        width is enough for this band when the second number is zero -- or is what it would be on the whole grid, where
+        the mask itself holds one class only.  Raises nothing and changes nothing: no diag state, no field."""
+        t = self.torch
+        summary = t.zeros(4, dtype=t.int64, device=self.dev)
+        stream = self._stream()
+        if self.world == 1:
+            self.ctx.search_radius_dev(self.dtype, self.nx, self.nyl, 0, _hip.SB_BND_GLOBAL, self.mask.data_ptr(), None,
+                                       summary.data_ptr(), maxdist=maxdist, stream=stream)
+        else:
+            self.ctx.band_search_radius_dev(self.dtype, self.nx, self.nyl, self.h, self.rank == 0, self.rank == self.world - 1,
+                                            self.mask.data_ptr(), None, summary.data_ptr(), maxdist=maxdist, stream=stream)
+        self.synchronize()
+        s = summary.cpu().tolist()
+        return int(s[3]), int(s[2])
 
     def upload_step_inputs(self, p, u, v, theta, local3d=False):
         """p, u, v: the full (nz, ny, nx) fields, or with local3d=True only this band's rows

@@ -158,6 +158,9 @@ struct sb_ctx {
     DevBuf umbits;                      // the coast bit plane of sb_get_dist_um_*
     DevBuf tabA, tabL, tabC, tabS;      // the device-wide summed-area tables (SbTables), allocated by the first call that builds them
     DevBuf tabW, tabRep;                // the stored windows and the report's device words, allocated with them while the cache is on
+    // search_radius: its planes, flags and row distances; the host forms' copies of mask and of the results.  No diag call
+    // reads or writes them, and search_radius touches nothing else of the context.
+    DevBuf rad_ws, rad_mask, rad_out;
     // the strip kernel's plan (sb_strip_kernel.hip): [64 bytes: number of the last call whose band plane changed |
     // ncu x SB_PLAN_STRIDE]; plan_key: the geometry it was made for; call_seq numbers the diag calls
     int plan_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1201,6 +1204,68 @@ int band_get_dist_host(sb_ctx *c, int nx, int ny, int halo, int south, int north
     return s.finish();
 }
 
+// ---- search_radius: every band cell's window radius from mask alone (sb_radius_kernels.hip) ----
+// band < 0: the whole-grid form under rule bnd; else the band step's frame (SB_BND_HALO) with GEO_BAND_* = band.
+template <typename T>
+int check_search_radius(sb_ctx *c, int nx, int ny, int halo, int bnd, const T *mask, const int *radius, const long long *summary,
+                        const long long *hist, int nhist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (nx < 1 || ny < 1 || halo < 0 || !mask) return fail(c, SB_ERR_ARG, "bad search_radius arguments");
+    if (bnd != BND_WRAPPER && bnd != BND_GLOBAL && bnd != BND_HALO) return fail(c, SB_ERR_ARG, "unknown boundary rule");
+    if (bnd != BND_HALO && halo != 0) return fail(c, SB_ERR_ARG, "halo must be 0 unless bnd == SB_BND_HALO");
+    if (hist && nhist != 0 && nhist < 2) return fail(c, SB_ERR_ARG, "search_radius: nhist must be 0 or at least 2");
+    if (nhist < 0) return fail(c, SB_ERR_ARG, "search_radius: negative nhist");
+    if (!radius && !summary && !(hist && nhist)) return fail(c, SB_ERR_ARG, "search_radius: no result asked for");
+    const long long nxh = (long long)nx + 2LL * halo, nyh = (long long)ny + 2LL * halo;
+    if (nxh > SB_RADIUS_MAX_W)
+        return fail(c, SB_ERR_ARG, "search_radius: rows wider than " + std::to_string(SB_RADIUS_MAX_W) + " cells are not served");
+    // the kernels count 64-cell segments of the frame in 32 bits
+    if (nyh * ((nxh + 63) / 64) > SB_RADIUS_MAX_SEGS)
+        return fail(c, SB_ERR_ARG, "search_radius: a frame of more than " + std::to_string(SB_RADIUS_MAX_SEGS) +
+                                       " 64-cell segments (rows x words per row) is not served");
+    return SB_OK;
+}
+
+template <typename T>
+int search_radius_dev(sb_ctx *c, int nx, int ny, int halo, int bnd, int band, const T *mask, T maxdist, int *radius,
+                      long long *summary, long long *hist, int nhist, void *stream) {
+    int rc = check_search_radius<T>(c, nx, ny, halo, bnd, mask, radius, summary, hist, nhist);
+    if (rc) return rc;
+    if (!hist || nhist == 0) { hist = nullptr; nhist = 0; }
+    const SbRadiusGeo g = sb_radius_geo(nx, ny, halo, bnd, band);
+    if ((rc = ensure(c, c->rad_ws, sb_radius_ws_bytes(g)))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    HIPCHK(c, sb_launch_search_radius<T>(mask, maxdist, g, c->rad_ws.p, radius, summary, hist, nhist, st));
+    return SB_OK;
+}
+
+template <typename T>
+int search_radius_host(sb_ctx *c, int nx, int ny, int halo, int bnd, int band, const T *mask, T maxdist, int *radius,
+                       long long *summary, long long *hist, int nhist) {
+    int rc = check_search_radius<T>(c, nx, ny, halo, bnd, mask, radius, summary, hist, nhist);
+    if (rc) return rc;
+    if (!hist || nhist == 0) { hist = nullptr; nhist = 0; }
+    // (buffers of its own, not the Stager's: a staged diag call forgets sigma's statistics, this call forgets nothing)
+    const size_t nm = (size_t)(nx + 2 * halo) * (ny + 2 * halo) * sizeof(T), n2 = (size_t)nx * ny;
+    const size_t o_sum = (n2 * sizeof(int) + 7) & ~(size_t)7, o_hist = o_sum + 4 * sizeof(long long);
+    if ((rc = ensure(c, c->rad_mask, nm))) return rc;
+    if ((rc = ensure(c, c->rad_out, o_hist + (size_t)nhist * sizeof(long long)))) return rc;
+    char *out = (char *)c->rad_out.p;
+    HIPCHK(c, hipMemcpyAsync(c->rad_mask.p, mask, nm, hipMemcpyHostToDevice, c->stream));
+    rc = search_radius_dev<T>(c, nx, ny, halo, bnd, band, (const T *)c->rad_mask.p, maxdist, radius ? (int *)out : nullptr,
+                              (long long *)(out + o_sum), hist ? (long long *)(out + o_hist) : nullptr, nhist, nullptr);
+    if (rc) return rc;
+    if (radius) HIPCHK(c, hipMemcpyAsync(radius, out, n2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (summary) HIPCHK(c, hipMemcpyAsync(summary, out + o_sum, 4 * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    if (hist) HIPCHK(c, hipMemcpyAsync(hist, out + o_hist, (size_t)nhist * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SB_OK;
+}
+
+inline int band_geo_of(int south, int north) {
+    return GEO_BAND_EW | (south ? GEO_BAND_SOUTH : 0) | (north ? GEO_BAND_NORTH : 0);
+}
+
 // UM vn10.7 coast setup on the tdims_l layout (ref: UM/vn10.7/sea_breeze_diag.F90:328-601): fields with ghost cells are
 // (nx + 2*hi) x (ny + 2*hj); the ghost cells of the outputs are left to the caller's swap_bounds
 template <typename T>
@@ -1382,7 +1447,7 @@ int sb_destroy(sb_ctx *c) {
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
                       &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS, &c->tabW,
-                      &c->tabRep})
+                      &c->tabRep, &c->rad_ws, &c->rad_mask, &c->rad_out})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -1572,6 +1637,25 @@ int sb_last_counters(sb_ctx *c, long long counters[4]) {
                                      void *stream) {                                                                \
         return band_get_dist_dev<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, cdist,     \
                                     stream);                                                                        \
+    }                                                                                                              \
+    int sb_search_radius_##SFX(sb_ctx *c, int nx, int ny, int halo, int bnd, const T *mask, T maxdist, int *radius,\
+                               long long *summary, long long *hist, int nhist) {                                   \
+        return search_radius_host<T>(c, nx, ny, halo, bnd, 0, mask, maxdist, radius, summary, hist, nhist);        \
+    }                                                                                                              \
+    int sb_search_radius_##SFX##_dev(sb_ctx *c, int nx, int ny, int halo, int bnd, const T *mask, T maxdist,       \
+                                     int *radius, long long *summary, long long *hist, int nhist, void *stream) {  \
+        return search_radius_dev<T>(c, nx, ny, halo, bnd, 0, mask, maxdist, radius, summary, hist, nhist, stream); \
+    }                                                                                                              \
+    int sb_band_search_radius_##SFX(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *mask,      \
+                                    T maxdist, int *radius, long long *summary, long long *hist, int nhist) {      \
+        return search_radius_host<T>(c, nx, ny, halo, BND_HALO, band_geo_of(south, north), mask, maxdist, radius,  \
+                                     summary, hist, nhist);                                                        \
+    }                                                                                                              \
+    int sb_band_search_radius_##SFX##_dev(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *mask,\
+                                          T maxdist, int *radius, long long *summary, long long *hist, int nhist,  \
+                                          void *stream) {                                                          \
+        return search_radius_dev<T>(c, nx, ny, halo, BND_HALO, band_geo_of(south, north), mask, maxdist, radius,   \
+                                    summary, hist, nhist, stream);                                                 \
     }                                                                                                              \
     int sb_get_edges_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, const T *lf, const T *ci, T *coast) {       \
         return get_edges_um_host<T>(c, nx, ny, hi, hj, lf, ci, coast);                                              \

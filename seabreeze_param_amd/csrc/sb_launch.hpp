@@ -169,6 +169,46 @@ template <typename T>
 hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                                  int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st);
 
+// search_radius (sb_radius_kernels.hip): the radius of every band cell's window from mask alone.  The kernels work in
+// WINDOW coordinates: a row as the windows see it has W cells -- the nx cells of the circle (SB_BND_GLOBAL, a band;
+// SB_BND_WRAPPER with column nx-1 standing for column 0, the rule's quirk), or the nx + 2h cells of a plain
+// SB_BND_HALO frame, which does not wrap.
+struct SbRadiusGeo {
+    int nx, ny, h, ld;      // interior cells, ghost width, row pitch of mask (nx + 2h)
+    int bnd, band, rows;    // BND_*, GEO_BAND_* (0: no band), band rows (ny, or ny - 1 for the wrapper rule)
+    int W, nw;              // cells and 64-bit words of a row in window coordinates
+    int coff, ioff;         // frame column of window column 0; window column of interior column 0
+    int periodic;           // window columns wrap round the row
+    int Y0, Y1;             // frame rows a window may read: [Y0, Y1) (not the ghost rows beyond a pole)
+};
+inline SbRadiusGeo sb_radius_geo(int nx, int ny, int h, int bnd, int band) {
+    SbRadiusGeo g;
+    g.nx = nx; g.ny = ny; g.h = h; g.ld = nx + 2 * h;
+    g.bnd = bnd; g.band = bnd == BND_HALO ? band : 0; g.rows = bnd == BND_WRAPPER ? ny - 1 : ny;
+    const bool plain = bnd == BND_HALO && !(g.band & GEO_BAND_EW);
+    g.W = plain ? nx + 2 * h : nx; g.nw = (g.W + 63) / 64;
+    g.coff = plain ? 0 : h; g.ioff = plain ? h : 0;
+    g.periodic = plain ? 0 : 1;
+    g.Y0 = (g.band & GEO_BAND_SOUTH) ? h : 0;
+    g.Y1 = (g.band & GEO_BAND_NORTH) ? h + ny : ny + 2 * h;
+    return g;
+}
+// the workspace: [64 bytes: "a land-side cell exists", "a sea-side cell exists" | per row, which words of the land-side plane
+// hold a land-side cell, which a sea-side cell | land-side plane | band plane | one 16-bit distance per cell], all over the
+// ny + 2h frame rows in window coordinates
+#define SB_RADIUS_WS_HDR 64
+#define SB_RADIUS_MAX_W 65535        // a row distance is kept in 16 bits and 65535 stands for "none": wider rows are refused
+#define SB_RADIUS_MAX_SEGS 0x7fffffffLL    // the passes number the frame's segments (rows x words per row) in 32 bits
+inline size_t sb_radius_ws_bytes(const SbRadiusGeo &g) {
+    const size_t nyh = (size_t)g.ny + 2 * (size_t)g.h, plane = nyh * g.nw * sizeof(uint64_t);
+    const size_t sums = nyh * ((g.nw + 63) / 64) * sizeof(uint64_t);
+    return SB_RADIUS_WS_HDR + 2 * sums + 2 * plane + ((nyh * g.W * sizeof(uint16_t) + 7) & ~(size_t)7);
+}
+// zeroes summary / hist (device pointers, any of them and radius may be null) on the stream and enqueues the three passes
+template <typename T>
+hipError_t sb_launch_search_radius(const T *mask, T maxdist, const SbRadiusGeo &g, void *ws, int *radius, long long *summary,
+                                   long long *hist, int nhist, hipStream_t st);
+
 // local part of swap_bounds: E-W periodic ghost columns, pole-side ghost rows replicate the edge row
 template <typename T>
 hipError_t sb_launch_fill_ghosts(T *field, int nx, int ny, int h, int south, int north, hipStream_t st);

@@ -408,7 +408,56 @@ class Context:
         self._chk(rc, "sb_band_get_dist")
         return cdist
 
+    def _search_radius(self, fn_name, mask, maxdist, halo, nhist, lead):
+        mask = np.ascontiguousarray(mask)
+        dt = np.dtype(mask.dtype)
+        if dt not in _SFX or mask.ndim != 2:
+            raise ValueError("mask must be a 2-D float32 or float64 array")
+        ny, nx = mask.shape[0] - 2 * halo, mask.shape[1] - 2 * halo
+        radius = np.empty((max(ny, 0), max(nx, 0)), dtype=np.int32)
+        summary = (C.c_longlong * 4)()
+        hist = np.zeros(nhist, dtype=np.int64) if nhist else None
+        rc = getattr(self.lib, f"{fn_name}_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), *lead, _p(mask),
+                                                       _CT[dt](maxdist), _p(radius), summary, _p(hist), C.c_int(nhist))
+        self._chk(rc, fn_name)
+        return radius, dict(band_cells=summary[0], with_radius=summary[1], without_window=summary[2],
+                            max_radius=summary[3]), hist
+
+    def search_radius(self, mask, maxdist=180.0, halo=0, bnd=SB_BND_GLOBAL, nhist=0):
+        """Every band cell's window radius from mask alone, before any diag call: mask is (ny + 2*halo, nx + 2*halo), halo 0
+        unless bnd is SB_BND_HALO.  Returns (radius (ny, nx) int32: 0 off the band, nn >= 1, -1 where the window never holds
+        both classes within the diag call's cap; summary: band_cells, with_radius, without_window, max_radius -- what
+        last_counters() would say after a diag call; hist (nhist bins: [0] the -1 cells, [k] radius k, the last bin radius
+        >= nhist - 1) or None).  No effect on what a later diag call enqueues or returns."""
+        return self._search_radius("sb_search_radius", mask, maxdist, halo, nhist, (C.c_int(bnd),))
+
+    def band_search_radius(self, mask_f, halo, south, north, maxdist=180.0, nhist=0):
+        """search_radius for one latitude band in the band step's frame: mask_f (ny + 2*halo, nx + 2*halo) with its ghost
+        rows filled on every cut side (south / north False); ghost rows on a pole side and the east-west ghost columns are
+        never read.  A window may use the ghost rows and no more: with halo >= the whole grid's max_radius the interior is
+        the whole-grid SB_BND_GLOBAL plane's rows, with less the cells that need more come back -1."""
+        return self._search_radius("sb_band_search_radius", mask_f, maxdist, halo, nhist,
+                                   (C.c_int(1 if south else 0), C.c_int(1 if north else 0)))
+
     # ------------------------------------------------------------------ device-pointer API
+    def search_radius_dev(self, dtype, nx, ny, halo, bnd, mask, radius, summary, hist=None, nhist=0, maxdist=180.0,
+                          stream=None):
+        """search_radius on device arrays (raw addresses): radius (ny, nx) int32, summary 4 int64, hist nhist int64, any of
+        the three None; zeroes summary and hist on the stream and enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        fn = getattr(self.lib, f"sb_search_radius_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), C.c_int(bnd), _p(mask), _CT[dt](maxdist), _p(radius),
+                     _p(summary), _p(hist), C.c_int(nhist), C.c_void_p(stream) if stream else None), "sb_search_radius_dev")
+
+    def band_search_radius_dev(self, dtype, nx, ny, halo, south, north, mask_f, radius, summary, hist=None, nhist=0,
+                               maxdist=180.0, stream=None):
+        """band_search_radius on a device frame (raw addresses); enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        fn = getattr(self.lib, f"sb_band_search_radius_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                     _p(mask_f), _CT[dt](maxdist), _p(radius), _p(summary), _p(hist), C.c_int(nhist),
+                     C.c_void_p(stream) if stream else None), "sb_band_search_radius_dev")
+
     def sigmoid_dev(self, dtype, nx, ny, ary, sm, stream=None):
         """sm = 1/(1+exp(-std*(ary-r))) on device arrays (raw addresses); enqueues without synchronising."""
         fn = getattr(self.lib, f"sb_sigmoid_{_SFX[np.dtype(dtype)]}_dev")
@@ -553,6 +602,17 @@ def dist_window(lon, lat, maxdist=180.0) -> int:
     if rc != 0:
         raise SeabreezeHipError(f"sb_dist_window failed ({rc}): {lib.sb_last_error(None).decode()}")
     return k.value
+
+
+def contrast_regimes(hist):
+    """Band cells per contrast regime from a search_radius histogram of nhist >= 129 bins: radius <= 16 (the strip
+    kernel), 17..32 (the wide strip / tile kernels), 33..127 (in reach of the table contrast), beyond 127 (the global path
+    whatever is switched on), and without a window.  Counts only: which switches to set is the caller's decision."""
+    h = np.asarray(hist)
+    if h.ndim != 1 or h.size < 129:
+        raise ValueError("contrast_regimes needs a histogram of at least 129 bins (radii up to 127 told apart)")
+    return dict(strip=int(h[1:17].sum()), wide=int(h[17:33].sum()), table=int(h[33:128].sum()), beyond=int(h[128:].sum()),
+                none=int(h[0]))
 
 
 def get_threads() -> int:
