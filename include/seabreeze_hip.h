@@ -142,9 +142,9 @@ int  sb_set_static_sigma(sb_ctx *ctx, int on);
    the tests hold against the reference; the fixed-point rounding moves sb_con by 2.1e-10 at the most).
    Takes effect for WHOLE SINGLE-DOMAIN calls of the host-model flavour -- sb_seabreeze_diag_*[_dev],
    sb_seabreeze_diag_um_*[_dev] -- with SB_BND_GLOBAL or SB_BND_HALO: six launches (k_scan, k_prep, two table passes, the
-   query, k_wind).  Silently ignored, i.e. exactly what runs without it, for the f2py flavour (sb_diag_*, sb_diag_stream_*),
-   for SB_BND_WRAPPER, for band steps (sb_band_seabreeze_diag_*) and while gathered moments are in use -- those two have a
-   switch of their own beside this one, sb_set_table_contrast_bands.  It is never
+   query, k_wind).  Alone it changes nothing -- exactly what runs without it -- for the f2py flavour (sb_diag_*,
+   sb_diag_stream_*; SB_BND_WRAPPER), for band steps (sb_band_seabreeze_diag_*) and while gathered moments are in use: the
+   first has a switch of its own beside this one, sb_set_table_contrast_f2py, the other two sb_set_table_contrast_bands.  It is never
    chosen automatically, whatever the radius hint.  sb_profile_end reports the row pass under [2] and the column pass
    and the query together under [3] for such calls.                                                                 */
 int  sb_set_table_contrast(sb_ctx *ctx, int on);
@@ -171,6 +171,22 @@ int  sb_set_table_contrast(sb_ctx *ctx, int on);
    window is kept; the stored windows of a whole call are dropped, as after any other call on the context).
    Results are those of the whole-grid table call on the same cells.  It is never chosen automatically.               */
 int  sb_set_table_contrast_bands(sb_ctx *ctx, int on);
+/* Opt-in, off by default, beside the table contrast above: the tables for the f2py flavour too.  Takes effect only while
+   sb_set_table_contrast is on, for WHOLE calls of that flavour -- sb_diag_*[_dev] and every sb_diag_stream_step_* -- which
+   run under SB_BND_WRAPPER without ghost cells: six launches (k_scan, k_prep, the row pass, the column pass, the query,
+   k_wind) where the flavour runs five.  The row pass forms t0 itself and writes the t0 plane of `output` (rows
+   1 .. nlats - 1, the same bits as k_t0 writes; row nlats stays untouched), so no k_t0 is launched; sb_profile_end
+   reports the row pass under [2], the column pass and the query together under [3].
+   The wrapper's index rule -- latitude clamped, column max(1, modulo(jj, nlons)) -- never reads the last column: an
+   offset that lands there, the centre of a last-column cell included, reads column 1.  The tables are therefore built
+   over the EFFECTIVE row, whose last column holds column 1's value and land-side bit, and a window is a truly periodic
+   one over that row: radii up to 127 while 2 r + 1 <= nlons.  Cells beyond the reach, cells whose window is wider than
+   the circle and one-class cells take the global-memory path, which knows the rule, and are counted as ever
+   (sb_last_counters).  Results agree with the default path of the flavour as the host-model table call agrees with its.
+   sb_set_table_window_cache takes effect for these calls wherever this switch does (a streamed run on a standing mask).
+   With it off, or sb_set_table_contrast off, the f2py flavour enqueues exactly what it enqueues without it.  Ignored:
+   by the host-model flavour, by band steps and while gathered moments are in use.  It is never chosen automatically.   */
+int  sb_set_table_contrast_f2py(sb_ctx *ctx, int on);
 /* Opt-in, off by default, for the table contrast above: keep every band cell's window while the coast stands.  The radius
    of a cell's window and the land-side cells in it follow from the land-side plane (mask >= 0) and the geometry alone, and
    mask -- the signed coast distance -- changes only when the host model's ice mask does.  A table call that searches
@@ -182,12 +198,14 @@ int  sb_set_table_contrast_bands(sb_ctx *ctx, int on);
    what the call before left, and the first difference makes this call search again; nothing is stated by the caller, and
    the host-pointer entry points are served like the device-pointer ones.  And by the host whenever the planes k_scan
    compared with are not those of the stored windows: after any other diag call or band step on this context (the f2py
-   flavour, sb_diag_stream_*, a band step, a call with this switch or the table contrast off, another grid, boundary rule
-   or ghost width), after a failed launch, a reallocated workspace, and when this switch is set.  No synchronisation, no
+   flavour and sb_diag_stream_* unless they run as table calls themselves -- sb_set_table_contrast_f2py --, a band step, a
+   call with this switch or the table contrast off, another grid, boundary rule or ghost width), after a failed launch,
+   a reallocated workspace, and when this switch is set.  No synchronisation, no
    further launch: six launches, as without it.
    Results are those of the table path bit for bit, counters included, whether a call fills or not.
    Workspace: 4 bytes per interior cell, grow-only, allocated with the tables while the switch is on.
-   Takes effect exactly where sb_set_table_contrast does; silently ignored wherever that is ignored and while it is off.
+   Takes effect exactly where sb_set_table_contrast does, and for the f2py flavour where sb_set_table_contrast_f2py does;
+   silently ignored wherever those are ignored and while they are off.
    It is never chosen automatically.                                                                                  */
 int  sb_set_table_window_cache(sb_ctx *ctx, int on);
 /* [0] band cells of the last diag call that were answered from a stored window, [1] band cells of that call whose window

@@ -5,7 +5,8 @@
 The counterpart of the reference's `test_run.py` (ref: python_wrapper/test_run.py:8-57): read the configuration, the
 static fields and the list of daily or monthly input files; for each file read the winds, temperature and sea ice,
 run `seabreezediag.diag` with the state (timestep counter, wind speed, wind direction, heating contrast) carried from
-file to file, and write `<prefix>sb_<stamp>.nc` beside the inputs.  `run.conf.example` shows the entries.
+file to file, and write `<prefix>sb_<stamp>.nc` beside the inputs.  `run.conf.example` shows the entries; the
+optional `table_contrast` and `keep_windows` are handed to `seabreezediag.diag` (grids of a few km).
 """
 from __future__ import annotations
 
@@ -24,6 +25,8 @@ def main(config, verbose=True):
     shape = (len(meta.lat), len(meta.lon))
     thc, windspeed, winddir = (np.zeros(shape) for _ in range(3))
     tt = 1
+    # optional entries: the contrast from device-wide tables, and the windows kept while the coast stands
+    table = {k: bool(cfg.get(k, False)) for k in ("table_contrast", "keep_windows")}
     written = []
     result = None                   # one (ntime, lat, lon) result array for all files of equal length (diag's out=)
     for stamp in meta.dates:
@@ -38,7 +41,8 @@ def main(config, verbose=True):
             if result is None or result.shape[0] != nt:
                 result = np.empty((nt,) + shape)
             tt, sb_con, thc, windspeed, winddir = sbd.diag(tt, meta.landfrac, meta.z, meta.std, meta.lon, meta.lat,
-                                                           data.pres, meta=data, ws=windspeed, wd=winddir, thc=thc, out=result)
+                                                           data.pres, meta=data, ws=windspeed, wd=winddir, thc=thc, out=result,
+                                                           **table)
             meta.create_nc(sb_con, f_sb, "sb_con", data.time)
         finally:
             for f in data.nc.values():

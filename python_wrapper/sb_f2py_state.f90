@@ -71,6 +71,26 @@ module sb_f2py_state
       integer(c_long), intent(out) :: steps
       real(c_double), intent(out) :: seconds(3)
     end function
+    integer(c_int) function sb_set_table_contrast(ctx, on) bind(C, name="sb_set_table_contrast")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function sb_set_table_contrast_f2py(ctx, on) bind(C, name="sb_set_table_contrast_f2py")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function sb_set_table_window_cache(ctx, on) bind(C, name="sb_set_table_window_cache")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function sb_last_step_report(ctx, report) bind(C, name="sb_last_step_report")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), intent(out) :: report(4)
+    end function
     integer(c_int) function sb_sigmoid_f32(ctx, nx, ny, ary, sm) bind(C, name="sb_sigmoid_f32")
       import :: c_ptr, c_int, c_float
       type(c_ptr), value :: ctx

@@ -131,6 +131,13 @@ end subroutine get_threads
 !        u, v plane p selects, and hands back the sb_con plane of the step BEFORE it (double precision, written
 !        in place into the caller's array), so that staging step i+1 overlaps the device work of step i.
 !        Results are those of diag called step by step.
+!   set_table_contrast(on, keep_windows)
+!        opt-in: diag and the streamed steps take the land-sea contrast from device-wide summed-area tables, radii up
+!        to 127 at a cost that does not depend on the radius (km-scale grids; include/seabreeze_hip.h:
+!        sb_set_table_contrast with sb_set_table_contrast_f2py); keep_windows: sb_set_table_window_cache beside them.
+!        on = 0 switches all three off.
+!   n = last_launches()
+!        kernels the last diag call or streamed step enqueued (sb_last_step_report): 5, or 6 on the tables.
 !===============================================================================
 subroutine last_status(rc)
   use sb_f2py_state
@@ -237,3 +244,34 @@ subroutine stream_stats(steps, seconds)
   rc = sb_diag_stream_stats(ctx, n, seconds)
   steps = int(n)
 end subroutine stream_stats
+
+subroutine set_table_contrast(on, keep_windows)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer :: on, keep_windows
+  integer(c_int) :: rc, flag
+  !f2py integer, intent(in) :: on
+  !f2py integer optional, intent(in) :: keep_windows = 0
+  call sb_ok()
+  call sb_ensure()
+  if (.not. c_associated(ctx)) return
+  flag = merge(1_c_int, 0_c_int, on /= 0)
+  rc = sb_set_table_contrast(ctx, flag)
+  if (rc == 0) rc = sb_set_table_contrast_f2py(ctx, flag)
+  if (rc == 0) rc = sb_set_table_window_cache(ctx, merge(1_c_int, 0_c_int, on /= 0 .and. keep_windows /= 0))
+  if (rc /= 0) call sb_fail('set_table_contrast', rc)
+end subroutine set_table_contrast
+
+subroutine last_launches(n)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer :: n
+  integer(c_int) :: rc, rep(4)
+  !f2py integer, intent(out) :: n
+  n = 0
+  if (.not. c_associated(ctx)) return
+  rc = sb_last_step_report(ctx, rep)
+  if (rc == 0) n = rep(1)
+end subroutine last_launches

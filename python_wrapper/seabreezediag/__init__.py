@@ -111,6 +111,14 @@ def _coast_distance(lsm, ice, lon, lat, static_known_same=False):
     return _dist_cache["dist"]
 
 
+def _set_table_contrast(on, keep_windows=False):
+    """The extension's table switches (seabreeze_f2py.f90: set_table_contrast) on the module's device context."""
+    if not hasattr(_ext, "set_table_contrast"):
+        raise RuntimeError("table_contrast=True: this build of the `seabreeze` extension has no set_table_contrast")
+    _ext.set_table_contrast(1 if on else 0, 1 if (on and keep_windows) else 0)
+    _check("set_table_contrast")
+
+
 def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     """Potential sea-breeze convergence strength in the coastal band
     (Bergemann et al. 2017, doi:10.1002/2017MS001048).
@@ -122,9 +130,27 @@ def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     every plane is overwritten); plus the kernel
     tunables ``target_plev`` [hPa], ``thresh_wind``, ``thresh_winddir``, ``thresh_windch``,
     ``thresh_thc``, ``target_time`` [h], ``maxdist`` [km], ``timestep`` [min].
+    ``table_contrast=True`` (not in the reference; off by default): every step of this call takes the land-sea
+    contrast from device-wide summed-area tables, at a cost per band cell that does not depend on the radius of its
+    window -- for grids of a few km, whose band cells lie further than 32 cells from the other class (radii up to 127;
+    include/seabreeze_hip.h: ``sb_set_table_contrast`` with ``sb_set_table_contrast_f2py``).  ``keep_windows=True``
+    beside it keeps every band cell's window while the coast stands (``sb_set_table_window_cache``): the same
+    numbers, less work per step.  Both are switched on before the first step and off again when the call returns.
 
     Returns ``(tt, sb_con, thc, ws, wd)``; ``sb_con`` is float64 ``(ntime, lat, lon)``.
     """
+    table = bool(_pop(kwargs, "table_contrast", False))
+    keep = bool(_pop(kwargs, "keep_windows", False))
+    if not table:
+        return _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs)
+    _set_table_contrast(True, keep)
+    try:
+        return _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs)
+    finally:
+        _set_table_contrast(False)
+
+
+def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     ws, wd, thc = (_pop(kwargs, k) for k in ("ws", "wd", "thc"))
     meta = _pop(kwargs, "meta")
     out_arr = _pop(kwargs, "out")

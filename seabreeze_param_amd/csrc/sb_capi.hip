@@ -140,6 +140,7 @@ struct sb_ctx {
     int last_wind_pairs = 0;            // the last call's k_wind was the paired instance (sb_last_wind_pairs)
     int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
     int table_bands = 0;                // sb_set_table_contrast_bands(ctx, 1): with it, band steps and calls with gathered moments too
+    int table_f2py = 0;                 // sb_set_table_contrast_f2py(ctx, 1): with it, whole calls of the f2py flavour (sb_diag_*, stream steps) too
     // sb_set_table_window_cache(ctx, 1): a table call keeps every band cell's window in W while the coast stands.  tabc: what
     // the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half (sb_table_cache_report)
     int table_cache = 0;
@@ -326,8 +327,10 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     job.self = (DiagJob<T> *)c->jobcopy.p;
     // a table call that keeps its windows (sb_set_table_window_cache): as sb_plan_diag decides `table`, and the switch.  Its
     // k_scan watches the planes whatever the contrast kernel of the domain would be: the header of the plan alone then
-    const bool cache = c->table_cache != 0 && c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC &&
-                       (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0 && phases == 3 && c->gathered == nullptr;
+    // the f2py flavour on the tables: a switch of its own beside sb_set_table_contrast, the wrapper's boundary rule alone
+    const bool f2py_table = c->table_contrast != 0 && c->table_f2py != 0 && job.flavour == SB_FLAVOUR_WRAPPER && g.bnd == BND_WRAPPER && g.h == 0;
+    const bool cache = c->table_cache != 0 && c->table_contrast != 0 && phases == 3 && c->gathered == nullptr &&
+                       ((job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0) || f2py_table);
     if (strip || cache) {
         const size_t need = 64 + (strip ? (size_t)c->ncu * SB_PLAN_STRIDE : (size_t)0);
         if (c->plan.cap < need) {
@@ -376,7 +379,9 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     in.reuse_stats = reuse_stats<T>(c, job.sigma, g.nx, g.ny, g.h);
     in.plan_use = c->plan_use != 0; in.segs_built = c->segs_built;
     in.scan_wgs = sb_scan_workgroups((unsigned)g.nyh * (unsigned)g.nw, c->ncu);
-    in.table = c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0;
+    in.table = (c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0) ||
+               f2py_table;
+    in.f2py_table = f2py_table;
     // ... and the tables for a band phase or a call with gathered moments: a switch of its own beside that one, ghost cells only
     in.band_table = in.table && c->table_bands != 0 && g.bnd == BND_HALO && (phases != 3 || c->gathered != nullptr);
     const SbDiagPlan plan = sb_plan_diag(in);
@@ -2078,6 +2083,12 @@ int sb_set_table_contrast(sb_ctx *c, int on) {
 int sb_set_table_contrast_bands(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->table_bands = on ? 1 : 0;
+    return SB_OK;
+}
+
+int sb_set_table_contrast_f2py(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->table_f2py = on ? 1 : 0;
     return SB_OK;
 }
 

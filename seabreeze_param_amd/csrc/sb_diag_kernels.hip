@@ -13,7 +13,8 @@
 //            merged into the sigmoid scalars, the tile flags compacted into the list of active tiles
 //            (for k_thc3), the band plane into the lists of 64-cell segments that hold band cells
 //            (for k_wind)                                                      [tiny]
-//   k_t0     f2py flavour only: the t0 plane is an output there               [HBM stream]
+//   k_t0     f2py flavour only: the t0 plane is an output there (on the tables -- sb_set_table_contrast_f2py -- the
+//            row pass writes it, sb_table_kernels.hip)                         [HBM stream]
 //   k_strip  (sb_strip_kernel.hip; radii up to 16) t0 and its summed-area tables marched through a
 //            ring in LDS, strip by strip -> thc; k_thc3 (sb_thc_kernel.hip) per tile for radii
 //            up to 32                                                          [VALU + LDS]

@@ -41,6 +41,8 @@ struct SbPlanIn {
                                     // flavour, SB_BND_GLOBAL or SB_BND_HALO, Geo::band == 0 (whole call, no gathered moments: checked here)
     bool band_table;                // sb_set_table_contrast_bands is on beside it and the call is one that switch serves as far as the caller
                                     // can tell: host-model flavour, SB_BND_HALO, Geo::band == 0 (a band phase or gathered moments: checked here)
+    bool f2py_table;                // sb_set_table_contrast_f2py is on beside sb_set_table_contrast and the call is of the f2py flavour
+                                    // with SB_BND_WRAPPER; the caller sets `table` with it (whole call, no gathered moments: checked here)
 };
 
 // the contrast kernel of the call and its block / tile grid
@@ -114,7 +116,10 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
     // radius -- whole single-domain host-model calls; with sb_set_table_contrast_bands beside it, band steps and calls with
     // gathered moments of that flavour too (`table` alone never changes those)
     const bool band_table = in.band_table && in.table && !whole && in.t0_fly;
-    p.table = (in.table && whole && in.t0_fly) || band_table;
+    // ... and with sb_set_table_contrast_f2py beside it, whole calls of the f2py flavour: the row pass forms t0 and writes
+    // the plane that flavour returns, so the six launches of the host-model table call stand where five ran, without k_t0
+    const bool f2py_table = in.f2py_table && in.table && whole && !in.t0_fly;
+    p.table = (in.table && whole && in.t0_fly) || band_table || f2py_table;
     const bool late_wind = in.band_late_wind && in.gathered && folds && !band_table;    // (sb_set_band_order: not for the tables)
     p.wind_scratch = !(whole || late_wind);
     SbStep *contrast = nullptr;

@@ -58,8 +58,8 @@ inline void sb_tab_cache_filled(SbTabCache &s, const SbTabKey &key, int seq) {
     s = SbTabCache{};
     s.have_key = true; s.key = key; s.seq = seq;
 }
-// every other diag call or band step that runs k_scan: the f2py flavour, a stream step, a band step, a call with either
-// switch off or with gathered moments in use
+// every other diag call or band step that runs k_scan: the f2py flavour and a stream step unless they run as table calls
+// themselves (sb_set_table_contrast_f2py), a band step, a call with either switch off or with gathered moments in use
 inline void sb_tab_cache_other_call(SbTabCache &s) { s.have_key = false; s.other = true; }
 inline void sb_tab_cache_launch_failed(SbTabCache &s) { s.have_key = false; s.failed = true; }
 inline void sb_tab_cache_toggled(SbTabCache &s) { s.have_key = false; s.toggled = true; }

@@ -7,6 +7,8 @@
 //                  -> inclusive prefix along longitude of {all, land side, land-side count} by DPP scans with a carry
 //                  between the 64-cell segments of the row.  The SB_TAB_RB waves of a workgroup add their prefixed rows
 //                  up per column (LDS atomics, 1024 columns at a time): S, the block sums the column pass starts from.
+//                  A second form for the f2py flavour (sb_set_table_contrast_f2py): the tables over the wrapper rule's
+//                  effective row, and the t0 plane written here (no k_t0 in such a call).
 //   k_table_cols   prefix along latitude, in place, BLOCKED: a workgroup takes 256 columns x 64 rows, starts from the sum of
 //                  the blocks of S above it (independent loads, a few dozen) and walks its rows with eight rows of loads
 //                  in flight.  Lanes run along longitude: every access is a whole line.  (One chain per column over all
@@ -50,7 +52,14 @@ __device__ __forceinline__ u64 tab_readlane63(u64 v) {
 }
 
 // ---- the row pass
-template <typename T, bool WC>                           // WC: with the count table
+// WR, the f2py flavour's form (sb_set_table_contrast_f2py; SB_BND_WRAPPER, no ghost cells): the wrapper's column rule
+// max(1, modulo(jj, nlons)) never reads its last column -- an offset that lands there, the centre of a last-column cell
+// included, reads column 0 (sb_map_cell) -- so a window is a truly periodic one over the EFFECTIVE row, whose last column
+// holds column 0's value and land-side bit: those enter the three sums at frame column nx - 1 (one more load of theta, z,
+// sigma per row, the same address in every lane), and tab_window's periodic branch serves the rule unchanged.  t0 is an
+// output of this flavour: the pass forms it itself (the one sequence, sb_t0) and writes the plane k_t0 would -- the whole
+// frame for contrast_global, rows 1 .. nlats - 1 of `output`, the REAL value at column nx - 1 -- so such a call launches no k_t0.
+template <typename T, bool WC, bool WR>                  // WC: with the count table
 __device__ __forceinline__ void tab_rows_body(const DiagJob<T> &job, const SbTables &tb, u64 *sA, u64 *sL, unsigned *sC) {
     const Geo g = job.g;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -61,11 +70,18 @@ __device__ __forceinline__ void tab_rows_body(const DiagJob<T> &job, const SbTab
     const T sd = job.stats[0], rr = job.stats[1];
     u64 carA = 0, carL = 0;
     unsigned carC = 0;
+    // (WR) what the effective row holds in its last column: column 0's value and bit
+    u64 eff_a = 0;
+    bool eff_land = false;
+    if constexpr (WR) {
+        eff_a = tab_fixed((double)sb_t0<T>(job.theta[row], job.z[row], job.sigma[row], sd, rr));
+        eff_land = (cls[0] & 1ull) != 0ull;
+    }
     struct In { T th, zz, sg; uint64_t word; };
     auto issue = [&](int w) {                            // every load unconditional, from a clamped address
         const int X = min(w * 64 + lane, g.nxh - 1);
         In r;
-        r.th = job.t0_fly ? job.theta[row + X] : job.t0[row + X];
+        r.th = (WR || job.t0_fly) ? job.theta[row + X] : job.t0[row + X];
         r.zz = job.z[row + X]; r.sg = job.sigma[row + X];
         r.word = cls[min(w, g.nw - 1)];
         return r;
@@ -73,9 +89,17 @@ __device__ __forceinline__ void tab_rows_body(const DiagJob<T> &job, const SbTab
     auto segment = [&](int w, const In &r) {
         const int X = w * 64 + lane;
         const bool in = X < g.nxh;
-        const T t0v = job.t0_fly ? sb_t0<T>(r.th, r.zz, r.sg, sd, rr) : r.th;
-        const bool land = ((r.word >> lane) & 1ull) != 0ull;          // (no bits beyond the frame: k_scan)
-        u64 a = in ? tab_fixed((double)t0v) : 0ull, l = land ? a : 0ull;
+        const T t0v = (WR || job.t0_fly) ? sb_t0<T>(r.th, r.zz, r.sg, sd, rr) : r.th;
+        bool land = ((r.word >> lane) & 1ull) != 0ull;                // (no bits beyond the frame: k_scan)
+        u64 a = in ? tab_fixed((double)t0v) : 0ull;
+        if constexpr (WR) {
+            if (in) {                                                 // (k_t0's two stores: no ghost cells, g.nxh == g.nx)
+                job.t0[row + X] = t0v;
+                if (job.out && Y < g.rows) job.out[(size_t)g.nx * g.ny + row + X] = t0v;
+            }
+            if (X == g.nx - 1) { a = eff_a; land = eff_land; }
+        }
+        u64 l = land ? a : 0ull;
         int c = land ? 1 : 0;
         sb_scan2_u64(a, l);                              // (all 64 lanes)
         if (WC) c = sb_wave_scan_add(c);
@@ -114,15 +138,15 @@ __device__ __forceinline__ void tab_rows_body(const DiagJob<T> &job, const SbTab
         }
     }
 }
-template <typename T>
+template <typename T, bool WR>                           // (the host picks the form: the host-model instances are the code as it was)
 __global__ __launch_bounds__(TAB_ROWS_NT) void k_table_rows(DiagJob<T> job, SbTables tb) {
     __shared__ u64 sA[TAB_ROWS_NT], sL[TAB_ROWS_NT];
     __shared__ unsigned sC[TAB_ROWS_NT];
     const bool fill = sb_tab_fill(tb);                   // (k_scan of this call has finished: uniform over the launch)
     // sb_table_cache_report [2]: calls that searched
     if (tb.W && blockIdx.x == 0 && threadIdx.x == 0) tb.rep[0] = (tb.rep_reset ? 0u : tb.rep[0]) + (fill ? 1u : 0u);
-    if (fill) tab_rows_body<T, true>(job, tb, sA, sL, sC);
-    else tab_rows_body<T, false>(job, tb, sA, sL, sC);
+    if (fill) tab_rows_body<T, true, WR>(job, tb, sA, sL, sC);
+    else tab_rows_body<T, false, WR>(job, tb, sA, sL, sC);
 }
 
 // ---- the column pass
@@ -177,6 +201,9 @@ __global__ __launch_bounds__(TAB_COLS_NT) void k_table_cols(int nxh, int nyh, in
 // modes the tables serve.  SB_BND_HALO (Geo::band == 0): no wrap, no clamp, the caller keeps nn within the frame reach.
 // SB_BND_GLOBAL: longitude periodic, at most two column ranges while 2 nn + 1 <= nx; latitude clamped, a row beyond a
 // pole is the edge row again, once per repetition: the rows in range plus `below` times row 0 plus `above` times row ny - 1.
+// SB_BND_WRAPPER (the f2py flavour's form of the row pass) takes the periodic branch as it stands: the tables hold the
+// effective row, the cap (nx - 1) / 2 keeps a window narrower than the circle, and g.ny - 1 is the real last row nlats --
+// read with multiplicity by the clamp, never processed (band bits exist for rows 1 .. nlats - 1 only: k_scan).
 struct TabWin { int xa0, xb0, xa1, xb1, ya, yb, below, above; };      // (xa1 > xb1: one column range)
 __device__ __forceinline__ TabWin tab_window(const Geo &g, int x, int y, int nn) {
     TabWin w;
@@ -324,7 +351,11 @@ __global__ __launch_bounds__(TAB_QUERY_NT) void k_table_query(DiagJob<T> job, Sb
 template <typename T>
 hipError_t sb_launch_table_rows(const DiagJob<T> &job, const SbTables &tb, hipStream_t st) {
     const int nblk = (job.g.nyh + SB_TAB_RB - 1) / SB_TAB_RB;
-    hipLaunchKernelGGL(k_table_rows<T>, dim3(nblk), dim3(TAB_ROWS_NT), 0, st, job, tb);
+    if (job.flavour == SB_FLAVOUR_WRAPPER) {
+        // the f2py flavour's form writes the t0 plane and knows the wrapper's frame alone
+        if (job.g.bnd != BND_WRAPPER || job.g.h != 0 || !job.t0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_table_rows<T, true>), dim3(nblk), dim3(TAB_ROWS_NT), 0, st, job, tb);
+    } else hipLaunchKernelGGL((k_table_rows<T, false>), dim3(nblk), dim3(TAB_ROWS_NT), 0, st, job, tb);
     return hipGetLastError();
 }
 hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st) {

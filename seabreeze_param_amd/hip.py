@@ -173,6 +173,11 @@ class Context:
         the ghost width must cover the largest radius (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_table_contrast_bands(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast_bands")
 
+    def set_table_contrast_f2py(self, on: bool):
+        """Opt-in, with set_table_contrast: whole calls of the f2py flavour (diag, stream steps) take the table contrast
+        too -- six launches, the wrapper's column rule by tables over the effective row (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_table_contrast_f2py(self.h, C.c_int(1 if on else 0)), "sb_set_table_contrast_f2py")
+
     def set_table_window_cache(self, on: bool):
         """Opt-in, with set_table_contrast: a table call keeps every band cell's window while the coast stands; the same
         bits, less work per call (include/seabreeze_hip.h)."""
@@ -473,6 +478,20 @@ class Context:
                 _p(thc), _p(sb_con), C.byref(tunables) if tunables is not None else None,
                 C.c_void_p(stream) if stream else None)
         self._chk(rc, "sb_seabreeze_diag_dev")
+
+    def diag_dev(self, dtype, tn, nps, nx, ny, p, z, std, theta, v, u, cdist, ws, wd, thc, output, stream=None,
+                 target_plev=700.0, thresh_wind=11.0, thresh_winddir=90.0, thresh_windch=5.0,
+                 thresh_thc=0.75, target_time=6.0, maxdist=180.0, timestep=24.0):
+        """The f2py flavour (sb_diag_*_dev) on device arrays (raw addresses); output is (4, ny, nx), of which the kernels
+        write rows 1 .. ny - 1 of every plane; enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        ct = _CT[dt]
+        fn = getattr(self.lib, f"sb_diag_{_SFX[dt]}_dev")
+        rc = fn(self.h, C.c_int(tn), _p(p), _p(z), _p(std), _p(theta), _p(v), _p(u), _p(cdist), _p(ws), _p(wd), _p(thc),
+                ct(target_plev), ct(thresh_wind), ct(thresh_winddir), ct(thresh_windch), ct(thresh_thc), ct(target_time),
+                ct(maxdist), ct(timestep), C.c_int(nps), C.c_int(nx), C.c_int(ny), _p(output),
+                C.c_void_p(stream) if stream else None)
+        self._chk(rc, "sb_diag_dev")
 
 
     def get_edges_dev(self, dtype, nx, ny, lsm, ci, coast, rule=0, bnd=SB_BND_WRAPPER, stream=None):
