@@ -214,6 +214,38 @@ int  sb_set_table_window_cache(sb_ctx *ctx, int on);
    A call that failed counts as a call without the cache.  Synchronises the device, as sb_last_counters does (a diag
    call may have been enqueued on a stream of the caller's).                                                         */
 int  sb_table_cache_report(sb_ctx *ctx, long long rep[4]);
+/* Opt-in guard for missing and non-finite temperatures.  Every contrast kernel but the global-memory search assumes
+   |t0| < 2048 K (64-bit fixed point in the strip kernels and the tables, fp64 prefix sums about a per-tile offset in the
+   tile kernel): a NaN, an Inf or the 2.0e20 missing value in theta or z leaves a finite, wrong thc in the windows that hold
+   the cell, where the reference lets it flow into the window means (generic/sea_breeze_diag.f90:198-216: NaN, +-Inf or
+   about 2e20 / n in thc, NaN or 0 in sb_con).  With the guard on, a call
+     - marks every cell of the ghost-celled frame with !(|theta| + 0.0060956 |z| < 2048) as bad, ahead of its first kernel
+       (one pass over theta and z: two reads per frame cell);
+     - behind the contrast kernel dilates the bad cells by that kernel's reach -- 16 cells (k_strip), 31 (k_strip32), 127
+       (the tables), under the call's boundary rule; for the tile kernel, whose floating-point sums do not cancel, every
+       tile whose staged rectangle holds a bad cell -- and computes the band cells so tainted again as the reference
+       does: plain sums of t0 per class in double precision over the window the global-memory search finds;
+     - then runs k_wind as ever.  Band cells that are not tainted keep the bits the contrast kernel left: their windows do
+       not hold the cell, and the wrapped fixed-point sums cancel whatever bits it turned into.
+   Four launches more (sb_last_step_report[0] counts them), all unconditional, no host synchronisation; without a bad cell
+   three of them leave at once.  Radii, counters, marks, stored plans and stored windows follow from mask alone: the
+   fields of sb_last_counters, sb_last_step_report[1..3] and sb_profile_end mean what they mean without the guard (its
+   launches lie outside every timed pair).  Workspace: two bit planes of the frame, grow-only, allocated while the switch is on.
+   Takes effect for WHOLE calls in which the contrast kernel runs ahead of a final k_wind: sb_seabreeze_diag_*[_dev] and
+   sb_seabreeze_diag_um_*[_dev] (fold on or off; strip, 96-column strip or tile kernel; with sb_set_table_contrast, with
+   or without sb_set_table_window_cache) and the f2py flavour, sb_diag_*[_dev] and sb_diag_stream_step_* (with or without
+   sb_set_table_contrast_f2py).  Silently IGNORED where the contrast kernel applies the update itself -- a band step
+   (sb_band_seabreeze_diag_*) and a call with gathered moments in use: those enqueue exactly what they enqueue without it.
+   Off by default; with the switch off a call enqueues exactly what it enqueued before the guard existed.
+   Cost, measured on one MI355X at 2560 x 1920 x 56 in double precision: 54 us per call without a bad cell
+   (165 against 111 us), about 0.5 ms more as soon as one cell has to be computed again (one thread per cell: latency).
+   NOT covered: a non-finite sigma.  It poisons the statistics of the whole field, and the reference then returns NaN
+   everywhere; nothing here looks at sigma.                                                                             */
+int  sb_set_nonfinite_guard(sb_ctx *ctx, int on);
+/* [0] bad cells of the ghost-celled frame the last diag call found, [1] band cells that call computed again, [2] calls
+   that found a bad cell, [3] calls that ran with the guard in effect, both since sb_set_nonfinite_guard was last called.
+   All four are 0 after a call the guard did not serve.  Synchronises the device, as sb_last_counters does.            */
+int  sb_guard_report(sb_ctx *ctx, long long rep[4]);
 /* What the last diag call or band step enqueued on this rank: [0] kernel launches, [1] RCCL operations (sends,
    receives, all-gathers), [2] RCCL groups, [3] device-to-device copies.  No synchronisation.               */
 int  sb_last_step_report(sb_ctx *ctx, int report[4]);

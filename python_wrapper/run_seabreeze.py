@@ -6,7 +6,8 @@ The counterpart of the reference's `test_run.py` (ref: python_wrapper/test_run.p
 static fields and the list of daily or monthly input files; for each file read the winds, temperature and sea ice,
 run `seabreezediag.diag` with the state (timestep counter, wind speed, wind direction, heating contrast) carried from
 file to file, and write `<prefix>sb_<stamp>.nc` beside the inputs.  `run.conf.example` shows the entries; the
-optional `table_contrast` and `keep_windows` are handed to `seabreezediag.diag` (grids of a few km).
+optional `table_contrast` and `keep_windows` (grids of a few km) and `guard_nonfinite` (inputs with missing values) are
+handed to `seabreezediag.diag`.
 """
 from __future__ import annotations
 
@@ -25,8 +26,9 @@ def main(config, verbose=True):
     shape = (len(meta.lat), len(meta.lon))
     thc, windspeed, winddir = (np.zeros(shape) for _ in range(3))
     tt = 1
-    # optional entries: the contrast from device-wide tables, and the windows kept while the coast stands
-    table = {k: bool(cfg.get(k, False)) for k in ("table_contrast", "keep_windows")}
+    # optional entries: the contrast from device-wide tables, the windows kept while the coast stands, and the guard for
+    # missing and non-finite temperatures
+    table = {k: bool(cfg.get(k, False)) for k in ("table_contrast", "keep_windows", "guard_nonfinite")}
     written = []
     result = None                   # one (ntime, lat, lon) result array for all files of equal length (diag's out=)
     for stamp in meta.dates:

@@ -86,6 +86,11 @@ module sb_f2py_state
       type(c_ptr), value :: ctx
       integer(c_int), value :: on
     end function
+    integer(c_int) function sb_set_nonfinite_guard(ctx, on) bind(C, name="sb_set_nonfinite_guard")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
     integer(c_int) function sb_last_step_report(ctx, report) bind(C, name="sb_last_step_report")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx

@@ -137,7 +137,11 @@ end subroutine get_threads
 !        sb_set_table_contrast with sb_set_table_contrast_f2py); keep_windows: sb_set_table_window_cache beside them.
 !        on = 0 switches all three off.
 !   n = last_launches()
-!        kernels the last diag call or streamed step enqueued (sb_last_step_report): 5, or 6 on the tables.
+!        kernels the last diag call or streamed step enqueued (sb_last_step_report): 5, or 6 on the tables; four more with
+!        the guard below.
+!   set_nonfinite_guard(on)
+!        opt-in: diag and the streamed steps find NaN, Inf and missing (2e20) temperatures and compute the band cells whose
+!        windows hold them again as the reference does (include/seabreeze_hip.h: sb_set_nonfinite_guard).
 !===============================================================================
 subroutine last_status(rc)
   use sb_f2py_state
@@ -262,6 +266,20 @@ subroutine set_table_contrast(on, keep_windows)
   if (rc == 0) rc = sb_set_table_window_cache(ctx, merge(1_c_int, 0_c_int, on /= 0 .and. keep_windows /= 0))
   if (rc /= 0) call sb_fail('set_table_contrast', rc)
 end subroutine set_table_contrast
+
+subroutine set_nonfinite_guard(on)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer :: on
+  integer(c_int) :: rc
+  !f2py integer, intent(in) :: on
+  call sb_ok()
+  call sb_ensure()
+  if (.not. c_associated(ctx)) return
+  rc = sb_set_nonfinite_guard(ctx, merge(1_c_int, 0_c_int, on /= 0))
+  if (rc /= 0) call sb_fail('set_nonfinite_guard', rc)
+end subroutine set_nonfinite_guard
 
 subroutine last_launches(n)
   use iso_c_binding

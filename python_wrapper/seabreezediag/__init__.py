@@ -119,6 +119,14 @@ def _set_table_contrast(on, keep_windows=False):
     _check("set_table_contrast")
 
 
+def _set_nonfinite_guard(on):
+    """The extension's guard switch (seabreeze_f2py.f90: set_nonfinite_guard) on the module's device context."""
+    if not hasattr(_ext, "set_nonfinite_guard"):
+        raise RuntimeError("guard_nonfinite=True: this build of the `seabreeze` extension has no set_nonfinite_guard")
+    _ext.set_nonfinite_guard(1 if on else 0)
+    _check("set_nonfinite_guard")
+
+
 def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     """Potential sea-breeze convergence strength in the coastal band
     (Bergemann et al. 2017, doi:10.1002/2017MS001048).
@@ -136,18 +144,31 @@ def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     include/seabreeze_hip.h: ``sb_set_table_contrast`` with ``sb_set_table_contrast_f2py``).  ``keep_windows=True``
     beside it keeps every band cell's window while the coast stands (``sb_set_table_window_cache``): the same
     numbers, less work per step.  Both are switched on before the first step and off again when the call returns.
+    ``guard_nonfinite=True`` (not in the reference; off by default): NaN, Inf and missing values (2e20) in ``t`` -- what
+    reanalysis files carry -- reach ``thc`` and ``sb_con`` as they do in the reference: every step finds such cells and
+    computes the band cells whose windows hold them again, the reference's way (``sb_set_nonfinite_guard``; without it
+    those cells hold finite, wrong numbers).  Switched on before the first step and off again when the call returns.
 
     Returns ``(tt, sb_con, thc, ws, wd)``; ``sb_con`` is float64 ``(ntime, lat, lon)``.
     """
     table = bool(_pop(kwargs, "table_contrast", False))
     keep = bool(_pop(kwargs, "keep_windows", False))
-    if not table:
+    guard = bool(_pop(kwargs, "guard_nonfinite", False))
+    if not table and not guard:
         return _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs)
-    _set_table_contrast(True, keep)
+    if guard:
+        _set_nonfinite_guard(True)
     try:
+        if table:
+            _set_table_contrast(True, keep)
         return _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs)
     finally:
-        _set_table_contrast(False)
+        try:
+            if table:
+                _set_table_contrast(False)
+        finally:
+            if guard:
+                _set_nonfinite_guard(False)
 
 
 def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):

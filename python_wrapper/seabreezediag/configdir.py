@@ -51,7 +51,8 @@ class Config(dict):
     (`skipwhitespace`), quotes and brackets are stripped; numbers, `true/false/none` and comma-separated tuples are
     converted; a value starting with `$NAME/` has the environment variable substituted
     (ref: configdir.py:236-345 for the accepted syntax).  Entries the file driver reads beyond the reference's:
-    `table_contrast`, `keep_windows` (true / false, optional: `seabreezediag.diag`'s keywords of those names)."""
+    `table_contrast`, `keep_windows`, `guard_nonfinite` (true / false, optional: `seabreezediag.diag`'s keywords of those
+    names)."""
 
     def __init__(self, filename, maketuple=True, skipwhitespace=True, split="="):
         super().__init__()

@@ -149,6 +149,12 @@ struct sb_ctx {
     bool tab_last = false;              // the last diag call ran with the cache in effect
     long long tab_calls = 0;            // such calls since the switch was turned on
     int tab_waves = 0;                  // waves of the last such call's query: the slots of the report it wrote
+    // sb_set_nonfinite_guard(ctx, 1): whole calls find missing / non-finite temperatures and compute the band cells they reach
+    // again as the reference does (sb_guard_kernels.hip); the report's host half (sb_guard_report)
+    int guard = 0;
+    bool guard_rep_reset = true;        // no call has run with the guard in effect since the switch was set
+    bool guard_last = false;            // the last diag call ran with the guard in effect
+    long long guard_calls = 0;          // such calls since the switch was set
     const void *stats_sigma = nullptr;
     int stats_dims[4] = {0, 0, 0, 0};   // nx, ny, halo, sizeof(T)
     int stats_ngathered = 0;            // bands whose moments the kept scalars were merged from (0: this domain's own)
@@ -159,6 +165,7 @@ struct sb_ctx {
     DevBuf umbits;                      // the coast bit plane of sb_get_dist_um_*
     DevBuf tabA, tabL, tabC, tabS;      // the device-wide summed-area tables (SbTables), allocated by the first call that builds them
     DevBuf tabW, tabRep;                // the stored windows and the report's device words, allocated with them while the cache is on
+    DevBuf guardA, guardB, guardRep;    // the guard's two bit planes and its device words (SbGuard), allocated while the switch is on
     // search_radius: its planes, flags and row distances; the host forms' copies of mask and of the results.  No diag call
     // reads or writes them, and search_radius touches nothing else of the context.
     DevBuf rad_ws, rad_mask, rad_out;
@@ -271,6 +278,7 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     const size_t nbits = (size_t)g.nyh * g.nw * sizeof(uint64_t);
     int rc;
     c->tab_last = false;                // (sb_table_cache_report: until this call has been enqueued with the cache in effect)
+    c->guard_last = false;              // (sb_guard_report likewise)
     if ((rc = ensure(c, c->bandbits, nbits))) return rc;
     if ((rc = ensure(c, c->clsbits, nbits))) return rc;
     SbPlanIn in = plan_input<T>(c, g.nx, g.rows);
@@ -385,6 +393,19 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     // ... and the tables for a band phase or a call with gathered moments: a switch of its own beside that one, ghost cells only
     in.band_table = in.table && c->table_bands != 0 && g.bnd == BND_HALO && (phases != 3 || c->gathered != nullptr);
     const SbDiagPlan plan = sb_plan_diag(in);
+    // the guard for missing and non-finite temperatures: a plan of its own beside that one, which it leaves as it is
+    in.guard = c->guard != 0 && g.band == 0;
+    lc.guard = sb_plan_guard(in, plan);
+    if (lc.guard.on) {
+        if ((rc = ensure(c, c->guardA, nbits))) return rc;
+        if ((rc = ensure(c, c->guardB, nbits))) return rc;
+        if (!c->guardRep.p) {
+            if ((rc = ensure(c, c->guardRep, SB_GUARD_REP_WORDS * sizeof(unsigned)))) return rc;
+            HIPCHK(c, hipMemsetAsync(c->guardRep.p, 0, SB_GUARD_REP_WORDS * sizeof(unsigned), st));   // (the ticket: zero between launches)
+        }
+        lc.guard_ws.bad = (uint64_t *)c->guardA.p; lc.guard_ws.taint = (uint64_t *)c->guardB.p; lc.guard_ws.rep = (unsigned *)c->guardRep.p;
+        lc.guard_ws.rep_reset = c->guard_rep_reset ? 1 : 0;
+    }
     if (plan.table) {
         // 20 bytes per frame cell, and the row pass' block sums: 20 bytes per column and block of SB_TAB_RB rows
         const size_t nsum = (size_t)((g.nyh + SB_TAB_RB - 1) / SB_TAB_RB) * g.nxh;
@@ -426,7 +447,8 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         if (le == hipErrorInvalidValue) return fail(c, SB_ERR_ARG, "no contrast kernel instance for this halo / tile shape");
         if (le != hipSuccess) return hipfail(c, le, "sb_launch_diag");
     }
-    c->rep_launches += plan.nsteps;
+    c->rep_launches += plan.nsteps + (lc.guard.on ? lc.guard.nlaunch : 0);
+    if (lc.guard.on) { c->guard_last = true; c->guard_rep_reset = false; ++c->guard_calls; }
     // W belongs to the planes of the last call that ran with the cache in effect: any other call that ran k_scan on them
     // (or a part of a band step) drops the key
     if (lc.tables.W) {
@@ -1452,7 +1474,7 @@ int sb_destroy(sb_ctx *c) {
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
                       &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS, &c->tabW,
-                      &c->tabRep, &c->rad_ws, &c->rad_mask, &c->rad_out})
+                      &c->tabRep, &c->rad_ws, &c->rad_mask, &c->rad_out, &c->guardA, &c->guardB, &c->guardRep})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -2111,6 +2133,25 @@ int sb_table_cache_report(sb_ctx *c, long long rep[4]) {
     if (c->tab_last)
         for (int w = 0; w < c->tab_waves; ++w) { rep[0] += d[SB_TAB_REP_HDR + 2 * w]; rep[1] += d[SB_TAB_REP_HDR + 2 * w + 1]; }
     rep[2] = d[0]; rep[3] = c->tab_calls;
+    return SB_OK;
+}
+
+int sb_set_nonfinite_guard(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->guard = on ? 1 : 0;
+    c->guard_rep_reset = true; c->guard_calls = 0; c->guard_last = false;
+    return SB_OK;
+}
+
+int sb_guard_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null pointer");
+    rep[0] = rep[1] = rep[2] = rep[3] = 0;
+    if (!c->guard_last || !c->guardRep.p) return SB_OK;      // (the last diag call was not one the guard served)
+    HIPCHK(c, hipDeviceSynchronize());
+    unsigned d[3];
+    HIPCHK(c, hipMemcpy(d, c->guardRep.p, sizeof(d), hipMemcpyDeviceToHost));
+    rep[0] = d[0]; rep[1] = d[1]; rep[2] = d[2]; rep[3] = c->guard_calls;
     return SB_OK;
 }
 

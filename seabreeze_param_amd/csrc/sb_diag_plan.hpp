@@ -43,6 +43,8 @@ struct SbPlanIn {
                                     // can tell: host-model flavour, SB_BND_HALO, Geo::band == 0 (a band phase or gathered moments: checked here)
     bool f2py_table;                // sb_set_table_contrast_f2py is on beside sb_set_table_contrast and the call is of the f2py flavour
                                     // with SB_BND_WRAPPER; the caller sets `table` with it (whole call, no gathered moments: checked here)
+    bool guard;                     // sb_set_nonfinite_guard is on and the frame is one the guard serves as far as the caller can tell
+                                    // (Geo::band == 0); sb_plan_diag does not read it: the guard has a plan of its own, sb_plan_guard
 };
 
 // the contrast kernel of the call and its block / tile grid
@@ -202,4 +204,37 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
     }
     p.segs_built = contrast && contrast->fold;
     return p;
+}
+
+// ---- the opt-in guard for missing and non-finite temperatures (sb_set_nonfinite_guard; sb_guard_kernels.hip).  Purely
+// additive: the main plan above is the same with the switch on and off, and the guard's launches go between its steps.
+//   k_guard_bits    ahead of step `bits_before` (the first): the bad-bit plane of the frame and the number of bad cells
+//   k_guard_taint   behind step `after` (the CONTRAST step), two launches: the bad plane dilated along longitude, then along
+//                   latitude, by the reach of the contrast kernel that ran -- or, for the tile kernel, whose floating-point
+//                   prefix sums let one bad cell poison a whole tile, by the staged rectangle of every tile ("by tile")
+//   k_guard_repair  behind it and ahead of the final WIND: the tainted band cells again, the way the reference sums them
+// Only whole calls in which CONTRAST runs ahead of a final WIND: where the contrast kernel applies the update itself (band
+// phases, calls with gathered moments) thc is consumed before a repair could run, and the guard is ignored.
+enum { SB_GUARD_BY_TILE = -1, SB_GUARD_REACH_STRIP = 16, SB_GUARD_REACH_STRIP32 = 31, SB_GUARD_REACH_TABLE = 127, SB_GUARD_LAUNCHES = 4 };
+struct SbGuardPlan {
+    bool on;                        // the guard runs in this call
+    int reach;                      // cells a bad cell taints round itself, or SB_GUARD_BY_TILE
+    int tile_w, tile_rows, halo;    // by tile: the tiles' owned columns and rows and their LDS halo (SbContrast)
+    int bits_before, after;         // steps of the main plan: k_guard_bits goes ahead of the one, taint and repair behind the other
+    int nlaunch;                    // launches the guard adds (sb_last_step_report[0] counts them)
+};
+inline SbGuardPlan sb_plan_guard(const SbPlanIn &in, const SbDiagPlan &p) {
+    SbGuardPlan gp{};
+    gp.bits_before = gp.after = -1;
+    if (!in.guard || in.phases != 3 || in.gathered || p.nsteps < 2) return gp;
+    const int ci = p.nsteps - 2;
+    const SbStep &c = p.steps[ci], &w = p.steps[ci + 1];
+    if (c.kernel != SB_K_CONTRAST || c.strip_update || w.kernel != SB_K_WIND || !w.wind_final || p.wind_scratch) return gp;
+    gp.on = true;
+    gp.bits_before = 0; gp.after = ci; gp.nlaunch = SB_GUARD_LAUNCHES;
+    if (c.table) gp.reach = SB_GUARD_REACH_TABLE;
+    else if (p.contrast.strip == 1) gp.reach = SB_GUARD_REACH_STRIP;
+    else if (p.contrast.strip == 2) gp.reach = SB_GUARD_REACH_STRIP32;
+    else { gp.reach = SB_GUARD_BY_TILE; gp.tile_w = p.contrast.txw; gp.tile_rows = p.contrast.tyrows; gp.halo = p.contrast.Hk; }
+    return gp;
 }

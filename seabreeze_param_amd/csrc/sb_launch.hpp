@@ -59,6 +59,20 @@ struct SbTables {
 };
 __device__ __forceinline__ bool sb_tab_fill(const SbTables &tb) { return !tb.W || tb.force || *tb.gen == tb.call_id; }
 
+// The guard for missing and non-finite temperatures (sb_set_nonfinite_guard; sb_guard_kernels.hip, SbGuardPlan): two bit
+// planes of the (nxh, nyh) frame in the layout of bandbits -- bad cells, later the tainted band cells; the longitude pass'
+// result -- and the device words of sb_guard_report: [0] bad frame cells of this call, [1] band cells it computed again,
+// [2] calls that found a bad cell since the switch was set; the workgroups' ticket and their partial counts.
+#define SB_GUARD_MAX_WGS 2048
+#define SB_GUARD_REP_TICKET 4
+#define SB_GUARD_REP_PART 8
+#define SB_GUARD_REP_WORDS (SB_GUARD_REP_PART + SB_GUARD_MAX_WGS)
+struct SbGuard {
+    uint64_t *bad, *taint;
+    unsigned *rep;
+    int rep_reset;                  // the first such call since the switch was set: rep[2] starts over
+};
+
 // Everything of the context a diag launch needs besides the job itself.
 struct SbLaunchCtx {
     hipStream_t stream;             // every kernel of the call is enqueued here
@@ -75,6 +89,8 @@ struct SbLaunchCtx {
     int wind_pairs;                 // sb_set_wind_pairs: k_wind may take its paired walk where the call is eligible
     int *wind_pairs_ran;            // ... and launch_wind notes here whether it did (host memory), or nullptr
     SbTables tables;                // a call whose plan builds the device-wide tables (SbDiagPlan::table)
+    SbGuardPlan guard;              // where the guard's launches go between the plan's steps (on == false: nowhere) ...
+    SbGuard guard_ws;               // ... and their workspace
 };
 
 template <typename T>
@@ -131,6 +147,13 @@ hipError_t sb_launch_table_rows(const DiagJob<T> &job, const SbTables &tb, hipSt
 hipError_t sb_launch_table_cols(const Geo &g, const SbTables &tb, hipStream_t st);
 template <typename T>
 hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st);
+
+// the guard (sb_guard_kernels.hip): the bad-bit plane and the count, ahead of the call's first kernel; behind the contrast
+// kernel the two taint passes and the repair of the tainted band cells in job.thc (three launches)
+template <typename T>
+hipError_t sb_launch_guard_bits(const DiagJob<T> &job, const SbGuard &gd, int ncu, hipStream_t st);
+template <typename T>
+hipError_t sb_launch_guard_repair(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st);
 
 // theta <- theta - (gmma*z)*sigmoid(sigma) over n cells, with the scalars the last diag call left in `stats`
 template <typename T>

@@ -190,6 +190,18 @@ class Context:
         self._chk(self.lib.sb_table_cache_report(self.h, arr), "sb_table_cache_report")
         return dict(stored_cells=arr[0], searched_cells=arr[1], fills=arr[2], calls=arr[3])
 
+    def set_nonfinite_guard(self, on: bool):
+        """Opt-in: whole diag calls find NaN, Inf and missing (2e20) temperatures and compute the band cells whose windows
+        hold them again as the reference does, between the contrast kernel and k_wind (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_nonfinite_guard(self.h, C.c_int(1 if on else 0)), "sb_set_nonfinite_guard")
+
+    def guard_report(self):
+        """Bad frame cells the last diag call found / band cells it computed again; calls that found a bad cell / ran with
+        the guard in effect since the switch was last set.  All 0 after a call the guard did not serve."""
+        arr = (C.c_longlong * 4)()
+        self._chk(self.lib.sb_guard_report(self.h, arr), "sb_guard_report")
+        return dict(bad_cells=arr[0], repaired_cells=arr[1], calls_with_bad=arr[2], calls=arr[3])
+
     def last_step_report(self):
         """What the last diag call / band step enqueued on this rank."""
         arr = (C.c_int * 4)()
