@@ -23,7 +23,7 @@ module sb_context_mod
   public :: sb_ctx, sb_ensure_ctx, sb_fail, sb_release_ctx
   public :: sb_comm_get_unique_id, sb_comm_init, sb_comm_finalize, sb_comm_active, sb_comm_rank
   public :: sb_set_static_sigma, sb_set_table_contrast, sb_set_table_contrast_bands, sb_set_table_window_cache
-  public :: sb_set_nonfinite_guard
+  public :: sb_set_nonfinite_guard, sb_set_nonfinite_guard_bands
   public :: sb_last_step_report
   public :: sb_dev_alloc, sb_dev_free, sb_dev_upload, sb_dev_download, sb_device_synchronize
 
@@ -72,6 +72,11 @@ module sb_context_mod
       integer(c_int), value :: on
     end function
     integer(c_int) function c_set_nonfinite_guard(ctx, on) bind(C, name="sb_set_nonfinite_guard")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function c_set_nonfinite_guard_bands(ctx, on) bind(C, name="sb_set_nonfinite_guard_bands")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
       integer(c_int), value :: on
@@ -229,7 +234,8 @@ contains
   end subroutine sb_set_table_contrast
 
   !> Opt-in: whole calls (sb_seabreeze_diag, the UM-layout form) find NaN, Inf and missing (2e20) temperatures and compute
-  !! the band cells whose windows hold them again as the reference does; a band step (sb_band_seabreeze_diag) ignores it.
+  !! the band cells whose windows hold them again as the reference does; a band step (sb_band_seabreeze_diag) ignores it
+  !! unless sb_set_nonfinite_guard_bands is on beside it.
   !! include/seabreeze_hip.h: sb_set_nonfinite_guard.
   subroutine sb_set_nonfinite_guard(on)
     logical, intent(in) :: on
@@ -238,6 +244,17 @@ contains
     rc = c_set_nonfinite_guard(sb_ctx, merge(1_c_int, 0_c_int, on))
     if (rc /= 0) call sb_fail('sb_set_nonfinite_guard', rc)
   end subroutine sb_set_nonfinite_guard
+
+  !> Opt-in, with sb_set_nonfinite_guard: band steps (sb_band_seabreeze_diag) and calls with gathered moments are guarded
+  !! too; theta gets the whole swap_bounds in a band step (one fill launch more on a strip kernel).
+  !! include/seabreeze_hip.h: sb_set_nonfinite_guard_bands.
+  subroutine sb_set_nonfinite_guard_bands(on)
+    logical, intent(in) :: on
+    integer(c_int) :: rc
+    call sb_ensure_ctx()
+    rc = c_set_nonfinite_guard_bands(sb_ctx, merge(1_c_int, 0_c_int, on))
+    if (rc /= 0) call sb_fail('sb_set_nonfinite_guard_bands', rc)
+  end subroutine sb_set_nonfinite_guard_bands
 
   !> Opt-in, with sb_set_table_contrast: band steps (sb_band_seabreeze_diag) and calls with gathered moments take the
   !! table contrast too; the ghost width must be at least the largest radius.

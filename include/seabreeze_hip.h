@@ -235,13 +235,42 @@ int  sb_table_cache_report(sb_ctx *ctx, long long rep[4]);
    sb_seabreeze_diag_um_*[_dev] (fold on or off; strip, 96-column strip or tile kernel; with sb_set_table_contrast, with
    or without sb_set_table_window_cache) and the f2py flavour, sb_diag_*[_dev] and sb_diag_stream_step_* (with or without
    sb_set_table_contrast_f2py).  Silently IGNORED where the contrast kernel applies the update itself -- a band step
-   (sb_band_seabreeze_diag_*) and a call with gathered moments in use: those enqueue exactly what they enqueue without it.
+   (sb_band_seabreeze_diag_*) and a call with gathered moments in use: those enqueue exactly what they enqueue without it,
+   unless sb_set_nonfinite_guard_bands (below), a switch of its own, is on beside this one.
    Off by default; with the switch off a call enqueues exactly what it enqueued before the guard existed.
    Cost, measured on one MI355X at 2560 x 1920 x 56 in double precision: 54 us per call without a bad cell
    (165 against 111 us), about 0.5 ms more as soon as one cell has to be computed again (one thread per cell: latency).
    NOT covered: a non-finite sigma.  It poisons the statistics of the whole field, and the reference then returns NaN
    everywhere; nothing here looks at sigma.                                                                             */
 int  sb_set_nonfinite_guard(sb_ctx *ctx, int on);
+/* Opt-in, off by default, beside the guard above: the guard for the calls of a multi-band run too.  Takes effect only
+   while sb_set_nonfinite_guard is on, for the host-model flavour, and only for
+     - band steps, sb_band_seabreeze_diag_*[_dev], on every contrast kernel a band step can get (k_strip, k_strip32, the
+       tile kernel, the tables under sb_set_table_contrast_bands);
+     - sb_seabreeze_diag_*[_dev] and sb_seabreeze_diag_um_*[_dev] while gathered moments are in use
+       (sb_use_gathered_moments), under any boundary rule, with sb_set_band_order 0 or 1.
+   In those calls the contrast kernel applies thresholds and state update itself and writes over ws / wd, the state of the
+   step before, so nothing behind it could form sb_con again.  The taint follows from theta, z, the band plane and the
+   kernel's reach alone: k_guard_bits and the two taint passes therefore run directly AHEAD of the contrast kernel (for the
+   tables between the column pass and the query), the latitude pass puts ws / wd of every tainted band cell aside, and
+   the repair directly behind the contrast kernel computes those cells again and applies the update again from what was
+   put aside: thc and sb_con are written over, ws / wd come out as the contrast kernel left them.  Under
+   sb_set_band_order(ctx, 1) -- the contrast ahead of a final k_wind -- the guard runs as in a whole call.  Four launches
+   more, as there; the reaches are the whole call's (16 / 31 / 127 / by tile).
+   Ghost cells of theta: the guard reads the whole frame.  A band step on a strip kernel with nx > 98 otherwise exchanges
+   the neighbour rows only and leaves theta's east-west ghost columns and polar ghost rows unfilled; while this switch
+   is in effect theta gets the whole swap_bounds on the communication stream, as the tile kernel's and the tables' band
+   steps get it anyway -- ONE FILL LAUNCH MORE for those steps (sb_last_step_report[0] counts it).  A call with gathered
+   moments has its ghost cells filled by the caller.
+   sb_guard_report and sb_last_step_report[0] mean for a served band step what they mean for a whole call; a band step
+   counts once in [3].  Setting this switch resets [2] and [3], as setting the other does, and drops the strip kernel's
+   stored plan (the next step plans its march afresh).  A profiled call with gathered moments times the three passes ahead
+   of the tables' query within pair [3].
+   Workspace: two planes of (nx, ny) elements beside the guard's bit planes, grow-only, allocated while the switch is on.
+   With either switch off such calls enqueue exactly what they enqueue without it; whole single-domain calls never depend
+   on it.  IGNORED: by the f2py flavour with gathered moments (sb_diag_* while sb_use_gathered_moments is in use), which
+   enqueues what it enqueues without it.  Cost: DESIGN.md 2.4e.  It is never chosen automatically.                       */
+int  sb_set_nonfinite_guard_bands(sb_ctx *ctx, int on);
 /* [0] bad cells of the ghost-celled frame the last diag call found, [1] band cells that call computed again, [2] calls
    that found a bad cell, [3] calls that ran with the guard in effect, both since sb_set_nonfinite_guard was last called.
    All four are 0 after a call the guard did not serve.  Synchronises the device, as sb_last_counters does.            */

@@ -99,7 +99,7 @@ class BandRunner:
 
     def __init__(self, ctx: _hip.Context, torch, dist, rank: int, world: int, nx: int, ny: int, nz: int,
                  halo: int, dtype=np.float64, comm: str = "torch", rows=None, static_sigma: bool = False,
-                 table_contrast: bool = False):
+                 table_contrast: bool = False, guard_nonfinite: bool = False):
         """comm="torch": ghost rows and moments travel through torch.distributed (`dist`, any backend);
         comm="native": through the library's own RCCL communicator (ctx.comm_init must have run):
         ncclSend/ncclRecv + ncclAllGather enqueued on the compute stream by two C-ABI calls.
@@ -109,7 +109,10 @@ class BandRunner:
         from device-wide summed-area tables over this band's frame, radii up to `halo` at a cost that does not depend on
         the radius; `halo` must be at least the largest radius -- the whole-grid Context.search_radius call's
         summary["max_radius"] for this mask and maxdist, or, without any rank holding the globe, the ghost width at which
-        check_halo() reports zero band cells without a window on every rank."""
+        check_halo() reports zero band cells without a window on every rank.
+        guard_nonfinite=True (opt-in, sb_set_nonfinite_guard and sb_set_nonfinite_guard_bands): every step finds NaN, Inf and
+        missing (2e20) temperatures in this band's frame -- ghost rows from the neighbours included -- and computes the band
+        cells whose windows hold them again as the reference does; guard_report() of the context counts this rank's frame."""
         assert comm in ("torch", "native")
         self.static_sigma = bool(static_sigma)
         self._stats_done = False
@@ -118,6 +121,9 @@ class BandRunner:
         if table_contrast:                              # (off: the context's switches stay as the caller left them)
             ctx.set_table_contrast(True)
             ctx.set_table_contrast_bands(True)
+        if guard_nonfinite:                             # (likewise)
+            ctx.set_nonfinite_guard(True)
+            ctx.set_nonfinite_guard_bands(True)
         self.comm = comm
         self.ctx, self.torch, self.dist = ctx, torch, dist
         self.rank, self.world = rank, world

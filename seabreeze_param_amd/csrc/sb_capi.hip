@@ -152,6 +152,7 @@ struct sb_ctx {
     // sb_set_nonfinite_guard(ctx, 1): whole calls find missing / non-finite temperatures and compute the band cells they reach
     // again as the reference does (sb_guard_kernels.hip); the report's host half (sb_guard_report)
     int guard = 0;
+    int guard_bands = 0;                // sb_set_nonfinite_guard_bands(ctx, 1): with it, band steps and calls with gathered moments too
     bool guard_rep_reset = true;        // no call has run with the guard in effect since the switch was set
     bool guard_last = false;            // the last diag call ran with the guard in effect
     long long guard_calls = 0;          // such calls since the switch was set
@@ -166,6 +167,7 @@ struct sb_ctx {
     DevBuf tabA, tabL, tabC, tabS;      // the device-wide summed-area tables (SbTables), allocated by the first call that builds them
     DevBuf tabW, tabRep;                // the stored windows and the report's device words, allocated with them while the cache is on
     DevBuf guardA, guardB, guardRep;    // the guard's two bit planes and its device words (SbGuard), allocated while the switch is on
+    DevBuf guardWs, guardWd;            // sb_set_nonfinite_guard_bands: ws / wd of the tainted band cells ahead of the contrast kernel's update
     // search_radius: its planes, flags and row distances; the host forms' copies of mask and of the results.  No diag call
     // reads or writes them, and search_radius touches nothing else of the context.
     DevBuf rad_ws, rad_mask, rad_out;
@@ -395,6 +397,7 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     const SbDiagPlan plan = sb_plan_diag(in);
     // the guard for missing and non-finite temperatures: a plan of its own beside that one, which it leaves as it is
     in.guard = c->guard != 0 && g.band == 0;
+    in.guard_bands = c->guard_bands != 0;
     lc.guard = sb_plan_guard(in, plan);
     if (lc.guard.on) {
         if ((rc = ensure(c, c->guardA, nbits))) return rc;
@@ -405,6 +408,11 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
         }
         lc.guard_ws.bad = (uint64_t *)c->guardA.p; lc.guard_ws.taint = (uint64_t *)c->guardB.p; lc.guard_ws.rep = (unsigned *)c->guardRep.p;
         lc.guard_ws.rep_reset = c->guard_rep_reset ? 1 : 0;
+        if (lc.guard.taint_before >= 0) {                // the contrast kernel applies the update: ws / wd of the tainted cells are put aside
+            if ((rc = ensure(c, c->guardWs, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
+            if ((rc = ensure(c, c->guardWd, (size_t)g.nx * g.ny * sizeof(T)))) return rc;
+            lc.guard_ws.stash_ws = c->guardWs.p; lc.guard_ws.stash_wd = c->guardWd.p;
+        }
     }
     if (plan.table) {
         // 20 bytes per frame cell, and the row pass' block sums: 20 bytes per column and block of SB_TAB_RB rows
@@ -568,8 +576,11 @@ int band_diag_dev(sb_ctx *c, T timestep_s, int tn, int nx, int ny, int nz, int h
     // and the fill, running behind the caller's stream's kernels rather than beside them, held the join up).  The tile
     // kernel (double precision, radii beyond 16) reads every ghost cell as filled: the whole swap_bounds for it.
     // The table contrast (sb_set_table_contrast_bands) builds its tables over the whole frame: the whole swap_bounds too.
+    // The guard for band steps (sb_set_nonfinite_guard_bands) reads the whole frame: the whole swap_bounds again, and its
+    // kernels see plain SB_BND_HALO geometry (Geo::band == 0) -- the one fill launch is what the switch costs a strip kernel here.
     const bool tables = c->table_contrast != 0 && c->table_bands != 0;
-    const bool folds = !tables && sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
+    const bool guard_frame = c->guard != 0 && c->guard_bands != 0;
+    const bool folds = !tables && !guard_frame && sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
     const int band_geo = folds ? (GEO_BAND_EW | (c->rank == 0 ? GEO_BAND_SOUTH : 0) | (c->rank == c->nranks - 1 ? GEO_BAND_NORTH : 0)) : 0;
     rc = folds ? exchange_rows_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream)
                : swap_bounds_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream);
@@ -1474,7 +1485,7 @@ int sb_destroy(sb_ctx *c) {
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     for (DevBuf *b : {&c->t0, &c->bandbits, &c->clsbits, &c->tiles, &c->vecs, &c->nws, &c->nwd, &c->coastbits, &c->tile_list,
                       &c->seg_list, &c->stamps, &c->jobcopy, &c->plan, &c->umbits, &c->tabA, &c->tabL, &c->tabC, &c->tabS, &c->tabW,
-                      &c->tabRep, &c->rad_ws, &c->rad_mask, &c->rad_out, &c->guardA, &c->guardB, &c->guardRep})
+                      &c->tabRep, &c->rad_ws, &c->rad_mask, &c->rad_out, &c->guardA, &c->guardB, &c->guardRep, &c->guardWs, &c->guardWd})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->stage)
         if (b.p) (void)hipFree(b.p);
@@ -2140,6 +2151,16 @@ int sb_set_nonfinite_guard(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     c->guard = on ? 1 : 0;
     c->guard_rep_reset = true; c->guard_calls = 0; c->guard_last = false;
+    return SB_OK;
+}
+
+int sb_set_nonfinite_guard_bands(sb_ctx *c, int on) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    c->guard_bands = on ? 1 : 0;
+    c->guard_rep_reset = true; c->guard_calls = 0; c->guard_last = false;
+    // later band steps on the same planes get another Geo::band (the whole swap_bounds against neighbour rows only), which
+    // the key of the strip kernel's stored plan does not hold: the next call plans afresh
+    c->plan_bits = nullptr;
     return SB_OK;
 }
 

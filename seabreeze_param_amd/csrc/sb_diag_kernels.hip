@@ -717,6 +717,7 @@ hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const S
     for (int i = 0; i < plan.nsteps; ++i) {
         const SbStep &s = plan.steps[i];
         if (gp.on && i == gp.bits_before && (e = sb_launch_guard_bits<T>(job, lc.guard_ws, lc.ncu, st)) != hipSuccess) return e;
+        if (gp.on && i == gp.taint_before && (e = sb_launch_guard_taint<T>(job, gp, lc.guard_ws, lc.ncu, st)) != hipSuccess) return e;
         hipEvent_t *ev = s.prof == SB_PROF_NONE ? nullptr : lc.prof;
         DiagJob<T> j = job;
         j.wind_final = s.wind_final; j.strip_update = s.strip_update; j.lists_stand = s.lists_stand; j.seg_trust = s.seg_trust; j.fold = s.fold;
@@ -746,7 +747,10 @@ hipError_t sb_launch_diag(const DiagJob<T> &job, const SbDiagPlan &plan, const S
         }
         if (ev_close) SB_EV_END(s.prof);
         if (s.publish && lc.moments_event && (e = hipEventRecord(lc.moments_event, st)) != hipSuccess) return e;
-        if (gp.on && i == gp.after && (e = sb_launch_guard_repair<T>(job, gp, lc.guard_ws, lc.ncu, st)) != hipSuccess) return e;
+        if (gp.on && i == gp.after) {
+            if (gp.taint_before < 0 && (e = sb_launch_guard_taint<T>(job, gp, lc.guard_ws, lc.ncu, st)) != hipSuccess) return e;
+            if ((e = sb_launch_guard_repair<T>(job, gp, lc.guard_ws, lc.ncu, st)) != hipSuccess) return e;
+        }
     }
     return hipGetLastError();
 }

@@ -45,6 +45,8 @@ struct SbPlanIn {
                                     // with SB_BND_WRAPPER; the caller sets `table` with it (whole call, no gathered moments: checked here)
     bool guard;                     // sb_set_nonfinite_guard is on and the frame is one the guard serves as far as the caller can tell
                                     // (Geo::band == 0); sb_plan_diag does not read it: the guard has a plan of its own, sb_plan_guard
+    bool guard_bands;               // sb_set_nonfinite_guard_bands is on beside it: band phases and calls with gathered moments of the
+                                    // host-model flavour too (checked in sb_plan_guard; sb_plan_diag does not read it either)
 };
 
 // the contrast kernel of the call and its block / tile grid
@@ -213,8 +215,16 @@ inline SbDiagPlan sb_plan_diag(const SbPlanIn &in) {
 //                   latitude, by the reach of the contrast kernel that ran -- or, for the tile kernel, whose floating-point
 //                   prefix sums let one bad cell poison a whole tile, by the staged rectangle of every tile ("by tile")
 //   k_guard_repair  behind it and ahead of the final WIND: the tainted band cells again, the way the reference sums them
-// Only whole calls in which CONTRAST runs ahead of a final WIND: where the contrast kernel applies the update itself (band
-// phases, calls with gathered moments) thc is consumed before a repair could run, and the guard is ignored.
+// Whole calls in which CONTRAST runs ahead of a final WIND.  Where the contrast kernel applies the update itself (phase 2 of
+// a band step, a one-sequence call with gathered moments) thc is consumed, and ws / wd -- the state of the step before,
+// which the trigger rule needs -- are overwritten, before a repair could run: the guard is ignored there unless
+// sb_set_nonfinite_guard_bands is on beside it (`guard_bands`; host-model flavour only).  The taint follows from theta, z,
+// the band plane and the reach alone, so then
+//   k_guard_bits and both taint passes go directly AHEAD of the CONTRAST step (`taint_before`), the latitude pass puts ws / wd
+//                   of every tainted band cell aside in two stash planes;
+//   k_guard_repair  directly behind it computes those cells again and applies the update again from the stash (`update`).
+// A call with gathered moments in the single-domain order (sb_set_band_order: CONTRAST, then a final WIND) runs as a whole
+// call does.  A phase-1 plan gets nothing.
 enum { SB_GUARD_BY_TILE = -1, SB_GUARD_REACH_STRIP = 16, SB_GUARD_REACH_STRIP32 = 31, SB_GUARD_REACH_TABLE = 127, SB_GUARD_LAUNCHES = 4 };
 struct SbGuardPlan {
     bool on;                        // the guard runs in this call
@@ -222,16 +232,32 @@ struct SbGuardPlan {
     int tile_w, tile_rows, halo;    // by tile: the tiles' owned columns and rows and their LDS halo (SbContrast)
     int bits_before, after;         // steps of the main plan: k_guard_bits goes ahead of the one, taint and repair behind the other
     int nlaunch;                    // launches the guard adds (sb_last_step_report[0] counts them)
+    int taint_before;               // the two taint passes go ahead of this step and stash ws / wd; -1: behind `after`, no stash
+    bool update;                    // the repair applies thresholds and state update from the stash (the CONTRAST step applied them)
 };
 inline SbGuardPlan sb_plan_guard(const SbPlanIn &in, const SbDiagPlan &p) {
     SbGuardPlan gp{};
-    gp.bits_before = gp.after = -1;
-    if (!in.guard || in.phases != 3 || in.gathered || p.nsteps < 2) return gp;
-    const int ci = p.nsteps - 2;
-    const SbStep &c = p.steps[ci], &w = p.steps[ci + 1];
-    if (c.kernel != SB_K_CONTRAST || c.strip_update || w.kernel != SB_K_WIND || !w.wind_final || p.wind_scratch) return gp;
+    gp.bits_before = gp.after = gp.taint_before = -1;
+    if (!in.guard || !(in.phases & 2) || p.nsteps < 1) return gp;
+    const bool whole = in.phases == 3 && !in.gathered;
+    if (!whole && !(in.guard_bands && in.t0_fly)) return gp;
+    int ci = p.nsteps - 1;
+    if (p.steps[ci].kernel == SB_K_WIND) --ci;
+    if (ci < 0 || p.steps[ci].kernel != SB_K_CONTRAST) return gp;
+    const SbStep &c = p.steps[ci];
+    const bool wind_behind = ci + 1 < p.nsteps;
+    if (wind_behind) {
+        // CONTRAST ahead of a final WIND: a whole call, or gathered moments in the single-domain order (phase 2 of a band
+        // step in that order: CONTRAST is its step 0)
+        if (c.strip_update || !p.steps[ci + 1].wind_final || p.wind_scratch) return gp;
+        gp.bits_before = 0;
+    } else {
+        // the CONTRAST step applies the update
+        if (whole || !(c.strip_update || p.wind_scratch)) return gp;
+        gp.bits_before = gp.taint_before = ci; gp.update = true;
+    }
     gp.on = true;
-    gp.bits_before = 0; gp.after = ci; gp.nlaunch = SB_GUARD_LAUNCHES;
+    gp.after = ci; gp.nlaunch = SB_GUARD_LAUNCHES;
     if (c.table) gp.reach = SB_GUARD_REACH_TABLE;
     else if (p.contrast.strip == 1) gp.reach = SB_GUARD_REACH_STRIP;
     else if (p.contrast.strip == 2) gp.reach = SB_GUARD_REACH_STRIP32;

@@ -24,7 +24,16 @@
 //                   has one, and per cell searches nn as contrast_global does (same cap, same geometry), sums plain t0 per
 //                   class in double -- NOT about the centre cell: with a centre of +Inf every term of contrast_global's sum
 //                   is NaN where the reference gives +-Inf -- and writes mul (T)(sl/nl - ss/ns) to thc.
+//
+// sb_set_nonfinite_guard_bands beside it: the calls in which the contrast kernel applies thresholds and state update itself
+// (phase 2 of a band step, a call with gathered moments).  That update overwrites ws / wd, the state of the step before, so
+// nothing behind it can form sb_con again from what is left.  The taint needs theta, z, the band plane and the reach only:
+// there the three passes above run AHEAD of the contrast kernel, the latitude pass in a second instance (STASH) that copies
+// ws / wd of every tainted band cell into two stash planes, and k_guard_repair<T, true> behind the contrast kernel hands the
+// contrast of a cell to sb_trigger_update with the stashed state and the winds k_wind left in the scratch planes: thc and
+// sb_con are written over, ws / wd come out as the contrast kernel left them (they do not depend on thc).
 #include "sb_thc_common.hpp"
+#include <type_traits>
 
 static_assert(SB_GUARD_REACH_TABLE == SB_TAB_REACH, "the guard dilates by the tables' reach");
 
@@ -119,9 +128,19 @@ __device__ __forceinline__ void guard_span(int c, int R, int tile, int &lo, int 
 
 // PASS 0: bad -> out, along longitude, one wave per frame row.  PASS 1: hd (pass 0's result) -> out, along latitude, one wave
 // per segment, band cells only; counts them.  R: the reach; tile: the tiles' width (pass 0) or rows (pass 1), 1: by cell.
-template <int PASS>
-__global__ __launch_bounds__(GUARD_NT) void k_guard_taint(Geo g, const uint64_t *__restrict__ src, uint64_t *__restrict__ out,
-                                                         const uint64_t *__restrict__ bandbits, int R, int tile, unsigned *__restrict__ rep) {
+// STASH (pass 1 only): every lane whose bit is set puts ws / wd of its cell aside (T: the planes' type; void: no stash).
+template <typename T>
+struct GuardStash {
+    const T *ws, *wd;               // the carried state, (nx, ny)
+    T *sws, *swd;                   // the stash planes, (nx, ny)
+};
+template <>
+struct GuardStash<void> {};
+
+template <int PASS, typename T>
+__device__ __forceinline__ void guard_taint_body(const Geo &g, const uint64_t *__restrict__ src, uint64_t *__restrict__ out,
+                                                 const uint64_t *__restrict__ bandbits, int R, int tile, unsigned *__restrict__ rep,
+                                                 const GuardStash<T> &stash) {
     __shared__ unsigned s_red[GUARD_NT];
     if (rep[0] == 0) {                                   // no bad cell in the frame: nothing is read, nothing repaired
         if (PASS == 1 && blockIdx.x == 0 && threadIdx.x == 0) rep[1] = 0;
@@ -182,6 +201,13 @@ __global__ __launch_bounds__(GUARD_NT) void k_guard_taint(Geo g, const uint64_t 
                     acc |= ((uint64_t)hi32 << 32) | lo32;
                 }
                 acc &= band;
+                if constexpr (!std::is_void<T>::value) {
+                    if ((acc >> lane) & 1ull) {          // (band cells are interior cells)
+                        const size_t o = (size_t)(Y - g.h) * g.nx + (size_t)(w * 64 + lane - g.h);
+                        stash.sws[o] = stash.ws[o];
+                        stash.swd[o] = stash.wd[o];
+                    }
+                }
             }
             if (lane == 0) out[sg] = acc;
             cnt += (unsigned)__popcll(acc);
@@ -196,9 +222,22 @@ __global__ __launch_bounds__(GUARD_NT) void k_guard_taint(Geo g, const uint64_t 
     }
 }
 
-// one tainted band cell, the reference's way: generic/sea_breeze_diag.f90:188-216
+template <int PASS>
+__global__ __launch_bounds__(GUARD_NT) void k_guard_taint(Geo g, const uint64_t *__restrict__ src, uint64_t *__restrict__ out,
+                                                         const uint64_t *__restrict__ bandbits, int R, int tile, unsigned *__restrict__ rep) {
+    guard_taint_body<PASS, void>(g, src, out, bandbits, R, tile, rep, GuardStash<void>{});
+}
+// the latitude pass ahead of a contrast kernel that applies the update itself
 template <typename T>
-__device__ __forceinline__ void guard_repair_cell(const DiagJob<T> &job, int x, int y, T sd, T rr) {
+__global__ __launch_bounds__(GUARD_NT) void k_guard_taint_stash(Geo g, const uint64_t *__restrict__ src, uint64_t *__restrict__ out,
+                                                               const uint64_t *__restrict__ bandbits, int R, int tile,
+                                                               unsigned *__restrict__ rep, GuardStash<T> stash) {
+    guard_taint_body<1, T>(g, src, out, bandbits, R, tile, rep, stash);
+}
+
+// one tainted band cell, the reference's way: generic/sea_breeze_diag.f90:188-216.  -> its contrast
+template <typename T>
+__device__ __forceinline__ T guard_repair_cell(const DiagJob<T> &job, int x, int y, T sd, T rr) {
     const Geo &g = job.g;
     int cap = g.nx + g.ny;                               // (contrast_global's callers: strip_slow_cell, k_thc3, k_table_query)
     if (g.bnd == BND_HALO) cap = min(cap, min(min(x + g.h, g.nx - 1 - x + g.h), min(y + g.h, g.ny - 1 - y + g.h)));
@@ -229,11 +268,14 @@ __device__ __forceinline__ void guard_repair_cell(const DiagJob<T> &job, int x, 
             if (sb_bit(job.clsbits, g.nw, X, Y)) { sl += t; nl += 1.0; } else { ss += t; ns += 1.0; }
         }
     const T mul = sb_bit(job.clsbits, g.nw, x + g.h, y + g.h) ? T(1) : T(-1);
-    job.thc[(size_t)y * g.nx + x] = mul * (T)(sl / nl - ss / ns);      // 0/0 -> NaN when a class is missing
+    return mul * (T)(sl / nl - ss / ns);                 // 0/0 -> NaN when a class is missing
 }
 
-template <typename T>
-__global__ __launch_bounds__(GUARD_NT) void k_guard_repair(DiagJob<T> job, const uint64_t *__restrict__ taint, const unsigned *__restrict__ rep) {
+// UPD: the contrast kernel applied thresholds and state update (and wrote over ws / wd): apply them again with the state the
+// latitude pass put aside and this call's winds in the scratch planes -- ws / wd come out as they are, thc and sb_con anew
+template <typename T, bool UPD>
+__global__ __launch_bounds__(GUARD_NT) void k_guard_repair(DiagJob<T> job, const uint64_t *__restrict__ taint, const unsigned *__restrict__ rep,
+                                                          const T *__restrict__ sws, const T *__restrict__ swd) {
     if (rep[0] == 0) return;
     __shared__ int s_scan[GUARD_NT / SB_WAVE];
     __shared__ unsigned short s_list[GUARD_CHUNK * 64];
@@ -250,7 +292,11 @@ __global__ __launch_bounds__(GUARD_NT) void k_guard_repair(DiagJob<T> job, const
         for (int i = threadIdx.x; i < total; i += GUARD_NT) {
             const unsigned code = s_list[i], sg = sg0 + (code >> 6);
             const int Y = (int)(sg / (unsigned)g.nw), X = (int)(sg - (unsigned)Y * (unsigned)g.nw) * 64 + (int)(code & 63u);
-            guard_repair_cell<T>(job, X - g.h, Y - g.h, sd, rr);
+            const int x = X - g.h, y = Y - g.h;
+            const size_t o = (size_t)y * g.nx + x;
+            const T n_thc = guard_repair_cell<T>(job, x, y, sd, rr);
+            if constexpr (UPD) sb_trigger_update<T>(job, o, n_thc, SbCellState<T>{job.nws[o], job.nwd[o], sws[o], swd[o]});
+            else job.thc[o] = n_thc;
         }
         __syncthreads();                                 // (s_list is written again)
     }
@@ -270,23 +316,44 @@ hipError_t sb_launch_guard_bits(const DiagJob<T> &job, const SbGuard &gd, int nc
     return hipGetLastError();
 }
 
+// the two taint passes; gp.taint_before >= 0: ahead of the contrast kernel, with the stash
 template <typename T>
-hipError_t sb_launch_guard_repair(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st) {
+hipError_t sb_launch_guard_taint(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st) {
     const Geo &g = job.g;
     const bool by_tile = gp.reach == SB_GUARD_BY_TILE;
     const int R = by_tile ? gp.halo : gp.reach;
     const unsigned nseg = (unsigned)g.nyh * (unsigned)g.nw;
     hipLaunchKernelGGL(k_guard_taint<0>, dim3(guard_grid((unsigned)g.nyh, ncu)), dim3(GUARD_NT), 0, st, g, (const uint64_t *)gd.bad, gd.taint,
                        (const uint64_t *)job.bandbits, R, by_tile ? gp.tile_w : 1, gd.rep);
-    hipLaunchKernelGGL(k_guard_taint<1>, dim3(guard_grid(nseg, ncu)), dim3(GUARD_NT), 0, st, g, (const uint64_t *)gd.taint, gd.bad,
-                       (const uint64_t *)job.bandbits, R, by_tile ? gp.tile_rows : 1, gd.rep);
-    const unsigned nchunk = (nseg + GUARD_CHUNK - 1) / GUARD_CHUNK;
-    hipLaunchKernelGGL(k_guard_repair<T>, dim3((int)min(nchunk, (unsigned)(ncu * 4))), dim3(GUARD_NT), 0, st, job,
-                       (const uint64_t *)gd.bad, (const unsigned *)gd.rep);
+    if (gp.taint_before >= 0) {
+        if (!gd.stash_ws || !gd.stash_wd) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_guard_taint_stash<T>, dim3(guard_grid(nseg, ncu)), dim3(GUARD_NT), 0, st, g, (const uint64_t *)gd.taint, gd.bad,
+                           (const uint64_t *)job.bandbits, R, by_tile ? gp.tile_rows : 1, gd.rep,
+                           GuardStash<T>{job.ws, job.wd, (T *)gd.stash_ws, (T *)gd.stash_wd});
+    } else
+        hipLaunchKernelGGL(k_guard_taint<1>, dim3(guard_grid(nseg, ncu)), dim3(GUARD_NT), 0, st, g, (const uint64_t *)gd.taint, gd.bad,
+                           (const uint64_t *)job.bandbits, R, by_tile ? gp.tile_rows : 1, gd.rep);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t sb_launch_guard_repair(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st) {
+    const Geo &g = job.g;
+    const unsigned nseg = (unsigned)g.nyh * (unsigned)g.nw, nchunk = (nseg + GUARD_CHUNK - 1) / GUARD_CHUNK;
+    const dim3 grid((int)min(nchunk, (unsigned)(ncu * 4)));
+    if (gp.update) {
+        if (!gd.stash_ws || !gd.stash_wd || !job.nws || !job.nwd) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_guard_repair<T, true>), grid, dim3(GUARD_NT), 0, st, job, (const uint64_t *)gd.bad, (const unsigned *)gd.rep,
+                           (const T *)gd.stash_ws, (const T *)gd.stash_wd);
+    } else
+        hipLaunchKernelGGL((k_guard_repair<T, false>), grid, dim3(GUARD_NT), 0, st, job, (const uint64_t *)gd.bad, (const unsigned *)gd.rep,
+                           (const T *)nullptr, (const T *)nullptr);
     return hipGetLastError();
 }
 
 template hipError_t sb_launch_guard_bits<float>(const DiagJob<float> &, const SbGuard &, int, hipStream_t);
 template hipError_t sb_launch_guard_bits<double>(const DiagJob<double> &, const SbGuard &, int, hipStream_t);
+template hipError_t sb_launch_guard_taint<float>(const DiagJob<float> &, const SbGuardPlan &, const SbGuard &, int, hipStream_t);
+template hipError_t sb_launch_guard_taint<double>(const DiagJob<double> &, const SbGuardPlan &, const SbGuard &, int, hipStream_t);
 template hipError_t sb_launch_guard_repair<float>(const DiagJob<float> &, const SbGuardPlan &, const SbGuard &, int, hipStream_t);
 template hipError_t sb_launch_guard_repair<double>(const DiagJob<double> &, const SbGuardPlan &, const SbGuard &, int, hipStream_t);

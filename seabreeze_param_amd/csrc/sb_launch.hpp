@@ -71,6 +71,8 @@ struct SbGuard {
     uint64_t *bad, *taint;
     unsigned *rep;
     int rep_reset;                  // the first such call since the switch was set: rep[2] starts over
+    void *stash_ws, *stash_wd;      // sb_set_nonfinite_guard_bands: (nx, ny) of T, ws / wd of the tainted band cells as they were
+                                    // ahead of a contrast kernel that applies the update itself; else nullptr
 };
 
 // Everything of the context a diag launch needs besides the job itself.
@@ -149,9 +151,13 @@ template <typename T>
 hipError_t sb_launch_table_query(const DiagJob<T> &job, const SbTables &tb, int ncu, hipStream_t st);
 
 // the guard (sb_guard_kernels.hip): the bad-bit plane and the count, ahead of the call's first kernel; behind the contrast
-// kernel the two taint passes and the repair of the tainted band cells in job.thc (three launches)
+// kernel the two taint passes and the repair of the tainted band cells in job.thc (three launches).  Where the contrast
+// kernel applies the update itself (SbGuardPlan::taint_before, ::update) all but the repair run ahead of it, the latitude
+// pass stashes ws / wd, and the repair applies the update again (job.nws / job.nwd: this call's winds)
 template <typename T>
 hipError_t sb_launch_guard_bits(const DiagJob<T> &job, const SbGuard &gd, int ncu, hipStream_t st);
+template <typename T>
+hipError_t sb_launch_guard_taint(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st);
 template <typename T>
 hipError_t sb_launch_guard_repair(const DiagJob<T> &job, const SbGuardPlan &gp, const SbGuard &gd, int ncu, hipStream_t st);
 

@@ -195,6 +195,12 @@ class Context:
         hold them again as the reference does, between the contrast kernel and k_wind (include/seabreeze_hip.h)."""
         self._chk(self.lib.sb_set_nonfinite_guard(self.h, C.c_int(1 if on else 0)), "sb_set_nonfinite_guard")
 
+    def set_nonfinite_guard_bands(self, on: bool):
+        """Opt-in, with set_nonfinite_guard: band steps and host-model diag calls with gathered moments are guarded too --
+        the taint is found ahead of the contrast kernel, ws / wd of the tainted cells are put aside and the update is
+        applied again behind it; theta gets the whole swap_bounds in a band step (include/seabreeze_hip.h)."""
+        self._chk(self.lib.sb_set_nonfinite_guard_bands(self.h, C.c_int(1 if on else 0)), "sb_set_nonfinite_guard_bands")
+
     def guard_report(self):
         """Bad frame cells the last diag call found / band cells it computed again; calls that found a bad cell / ran with
         the guard in effect since the switch was last set.  All 0 after a call the guard did not serve."""
