@@ -17,7 +17,22 @@
  *     through device buffers it owns.  `_dev` entry points take DEVICE pointers and
  *     enqueue on `stream` (a hipStream_t passed as void*; NULL = the context's own
  *     stream) without synchronising -- this is what a GPU-resident host model and
- *     bench.py use.
+ *     bench.py use.  NULL is the context's own non-blocking stream, never the legacy
+ *     default stream: a caller that passes NULL orders its work against the calls
+ *     through the context (sb_device_upload / _download, sb_synchronize).
+ *     "Without synchronising" holds for the steady state, the second and later call
+ *     of one geometry and one set of switches on one context.  A call WAITS FOR THE
+ *     DEVICE where the grow-only workspace has to grow -- the first call of a
+ *     context, of a larger grid or ghost width, of an option that brings planes of
+ *     its own: the smaller buffer is freed, and hipFree waits --, and the first band
+ *     step of a context creates its second stream.  sb_get_dist_*_dev and
+ *     sb_band_get_dist_*_dev wait for the device when they are handed other
+ *     coordinates than the call before (the tables are made anew from a host vector
+ *     that may still be on its way), and once for the stream that uploaded the tables
+ *     when the same coordinates come back on ANOTHER stream.  Everything a call
+ *     enqueues -- kernels, the zeroing of its flag and plan buffers, copies -- is
+ *     ordered on `stream`; a band step's second stream forks from it and joins it
+ *     inside the call (tests/test_enqueue_only_gpu.py).
  *   - Every function returns SB_OK (0) or an sb_status; sb_last_error() gives text.
  *     The reference has no error reporting on this path (generic + wrapper) and an
  *     `error` out-argument in the UM copy (ref: UM/vn10.7/sea_breeze_diag.F90:102,

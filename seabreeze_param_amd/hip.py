@@ -575,6 +575,19 @@ class Context:
         self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), _p(sigma), _p(moments5),
                      C.c_void_p(stream) if stream else None), "sb_sigma_moments_dev")
 
+    def device_upload(self, dst, src):
+        """Host array -> device address `dst` on the context's own stream (sb_device_upload); synchronises that stream."""
+        src = np.ascontiguousarray(src)
+        self._chk(self.lib.sb_device_upload(self.h, _p(dst), _p(src), C.c_size_t(src.nbytes)), "sb_device_upload")
+
+    def device_download(self, dst, src):
+        """Device address `src` -> the C-contiguous host array `dst` on the context's own stream (sb_device_download);
+        synchronises that stream."""
+        if not isinstance(dst, np.ndarray) or not dst.flags.c_contiguous:
+            raise ValueError("dst must be a C-contiguous numpy array")
+        self._chk(self.lib.sb_device_download(self.h, _p(dst), _p(src), C.c_size_t(dst.nbytes)), "sb_device_download")
+        return dst
+
     def use_gathered_moments(self, gathered, nparts: int):
         """Following diag calls merge `nparts` gathered moments (device address) instead of scanning sigma."""
         self._chk(self.lib.sb_use_gathered_moments(self.h, _p(gathered) if gathered else None, C.c_int(nparts)),
