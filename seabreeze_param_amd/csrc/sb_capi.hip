@@ -138,21 +138,17 @@ struct sb_ctx {
     int band_late_wind = 0;             // sb_set_band_order(ctx, 1): a band step runs the contrast before k_wind (measurement)
     int no_wind_pairs = 0;              // sb_set_wind_pairs(ctx, 0): k_wind walks one cell per lane everywhere
     int last_wind_pairs = 0;            // the last call's k_wind was the paired instance (sb_last_wind_pairs)
-    int table_contrast = 0;             // sb_set_table_contrast(ctx, 1): whole host-model calls take the contrast from device-wide tables
-    int table_bands = 0;                // sb_set_table_contrast_bands(ctx, 1): with it, band steps and calls with gathered moments too
-    int table_f2py = 0;                 // sb_set_table_contrast_f2py(ctx, 1): with it, whole calls of the f2py flavour (sb_diag_*, stream steps) too
-    // sb_set_table_window_cache(ctx, 1): a table call keeps every band cell's window in W while the coast stands.  tabc: what
-    // the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half (sb_table_cache_report)
-    int table_cache = 0;
+    // the opt-in switches of the table contrast, its window cache and the guard (the six setters at the end of this file): which
+    // calls each of them serves is sb_apply_switches' to say (sb_diag_plan.hpp)
+    SbSwitches sw{};
+    // the window cache: what the host knows about whose planes W belongs to (sb_table_cache.hpp); the report's host half
+    // (sb_table_cache_report)
     SbTabCache tabc;
     bool tab_rep_reset = true;          // no call has run with the cache in effect since the switch was turned on
     bool tab_last = false;              // the last diag call ran with the cache in effect
     long long tab_calls = 0;            // such calls since the switch was turned on
     int tab_waves = 0;                  // waves of the last such call's query: the slots of the report it wrote
-    // sb_set_nonfinite_guard(ctx, 1): whole calls find missing / non-finite temperatures and compute the band cells they reach
-    // again as the reference does (sb_guard_kernels.hip); the report's host half (sb_guard_report)
-    int guard = 0;
-    int guard_bands = 0;                // sb_set_nonfinite_guard_bands(ctx, 1): with it, band steps and calls with gathered moments too
+    // the guard for missing / non-finite temperatures (sb_guard_kernels.hip): the report's host half (sb_guard_report)
     bool guard_rep_reset = true;        // no call has run with the guard in effect since the switch was set
     bool guard_last = false;            // the last diag call ran with the guard in effect
     long long guard_calls = 0;          // such calls since the switch was set
@@ -335,12 +331,12 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     }
     if ((rc = ensure(c, c->jobcopy, sizeof(DiagJob<double>)))) return rc;
     job.self = (DiagJob<T> *)c->jobcopy.p;
-    // a table call that keeps its windows (sb_set_table_window_cache): as sb_plan_diag decides `table`, and the switch.  Its
-    // k_scan watches the planes whatever the contrast kernel of the domain would be: the header of the plan alone then
-    // the f2py flavour on the tables: a switch of its own beside sb_set_table_contrast, the wrapper's boundary rule alone
-    const bool f2py_table = c->table_contrast != 0 && c->table_f2py != 0 && job.flavour == SB_FLAVOUR_WRAPPER && g.bnd == BND_WRAPPER && g.h == 0;
-    const bool cache = c->table_cache != 0 && c->table_contrast != 0 && phases == 3 && c->gathered == nullptr &&
-                       ((job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0) || f2py_table);
+    // which of the context's switches serve this call, and whether it is a table call that keeps its windows (its k_scan
+    // watches the planes whatever the contrast kernel: without a strip kernel the header of the plan alone is allocated)
+    static_assert((int)SB_CALL_BND_WRAPPER == (int)BND_WRAPPER && (int)SB_CALL_BND_GLOBAL == (int)BND_GLOBAL &&
+                  (int)SB_CALL_BND_HALO == (int)BND_HALO, "SbCallBnd names sb_device.hpp's boundary rules");
+    in.phases = phases;
+    const bool cache = sb_apply_switches(c->sw, SbCall{job.flavour == SB_FLAVOUR_GENERIC, g.bnd, g.h != 0, g.band != 0}, in);
     if (strip || cache) {
         const size_t need = 64 + (strip ? (size_t)c->ncu * SB_PLAN_STRIDE : (size_t)0);
         if (c->plan.cap < need) {
@@ -385,19 +381,12 @@ int run_diag(sb_ctx *c, DiagJob<T> &job, hipStream_t st, int phases = 3) {
     lc.moments_event = (phases == 1 && c->nranks > 1) ? c->ev_mom : nullptr;   // (one rank: nobody waits for them)
     lc.stats_ticket = (int *)c->ticket + 1;
     // every decision about the kernels of this call: the plan's (the job's mode fields are the executor's to set)
-    in.phases = phases; in.t0_fly = job.t0_fly != 0; in.moments_out = lc.moments_out != nullptr;
+    in.t0_fly = job.t0_fly != 0; in.moments_out = lc.moments_out != nullptr;
     in.reuse_stats = reuse_stats<T>(c, job.sigma, g.nx, g.ny, g.h);
     in.plan_use = c->plan_use != 0; in.segs_built = c->segs_built;
     in.scan_wgs = sb_scan_workgroups((unsigned)g.nyh * (unsigned)g.nw, c->ncu);
-    in.table = (c->table_contrast != 0 && job.flavour == SB_FLAVOUR_GENERIC && (g.bnd == BND_GLOBAL || g.bnd == BND_HALO) && g.band == 0) ||
-               f2py_table;
-    in.f2py_table = f2py_table;
-    // ... and the tables for a band phase or a call with gathered moments: a switch of its own beside that one, ghost cells only
-    in.band_table = in.table && c->table_bands != 0 && g.bnd == BND_HALO && (phases != 3 || c->gathered != nullptr);
     const SbDiagPlan plan = sb_plan_diag(in);
     // the guard for missing and non-finite temperatures: a plan of its own beside that one, which it leaves as it is
-    in.guard = c->guard != 0 && g.band == 0;
-    in.guard_bands = c->guard_bands != 0;
     lc.guard = sb_plan_guard(in, plan);
     if (lc.guard.on) {
         if ((rc = ensure(c, c->guardA, nbits))) return rc;
@@ -575,12 +564,10 @@ int band_diag_dev(sb_ctx *c, T timestep_s, int tn, int nx, int ny, int nz, int h
     // arithmetic (Geo::band) -- no fill kernel on the communication stream, three launches per band step (round 3: four,
     // and the fill, running behind the caller's stream's kernels rather than beside them, held the join up).  The tile
     // kernel (double precision, radii beyond 16) reads every ghost cell as filled: the whole swap_bounds for it.
-    // The table contrast (sb_set_table_contrast_bands) builds its tables over the whole frame: the whole swap_bounds too.
-    // The guard for band steps (sb_set_nonfinite_guard_bands) reads the whole frame: the whole swap_bounds again, and its
-    // kernels see plain SB_BND_HALO geometry (Geo::band == 0) -- the one fill launch is what the switch costs a strip kernel here.
-    const bool tables = c->table_contrast != 0 && c->table_bands != 0;
-    const bool guard_frame = c->guard != 0 && c->guard_bands != 0;
-    const bool folds = !tables && !guard_frame && sb_plan_contrast(plan_input<T>(c, nx, ny)).strip != 0 && nx > 96 + 2;
+    // The table contrast and the guard for band steps read the whole frame too, and their kernels see plain SB_BND_HALO
+    // geometry (Geo::band == 0) -- the one fill launch is what either switch costs a strip kernel here.  One predicate,
+    // beside the one that decides which switches serve the two phases below: sb_band_folds_frame, sb_diag_plan.hpp.
+    const bool folds = sb_band_folds_frame(c->sw, sb_plan_contrast(plan_input<T>(c, nx, ny)), nx);
     const int band_geo = folds ? (GEO_BAND_EW | (c->rank == 0 ? GEO_BAND_SOUTH : 0) | (c->rank == c->nranks - 1 ? GEO_BAND_NORTH : 0)) : 0;
     rc = folds ? exchange_rows_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream)
                : swap_bounds_dev<T>(c, theta, nx, ny, halo, (void *)c->aux_stream);
@@ -2109,25 +2096,25 @@ int sb_set_static_sigma(sb_ctx *c, int on) {
 
 int sb_set_table_contrast(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->table_contrast = on ? 1 : 0;
+    c->sw.table = on != 0;
     return SB_OK;
 }
 
 int sb_set_table_contrast_bands(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->table_bands = on ? 1 : 0;
+    c->sw.table_bands = on != 0;
     return SB_OK;
 }
 
 int sb_set_table_contrast_f2py(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->table_f2py = on ? 1 : 0;
+    c->sw.table_f2py = on != 0;
     return SB_OK;
 }
 
 int sb_set_table_window_cache(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->table_cache = on ? 1 : 0;
+    c->sw.table_cache = on != 0;
     sb_tab_cache_toggled(c->tabc);                   // (whatever W holds, the next call that uses it fills it)
     if (on) { c->tab_rep_reset = true; c->tab_calls = 0; }
     return SB_OK;
@@ -2149,14 +2136,14 @@ int sb_table_cache_report(sb_ctx *c, long long rep[4]) {
 
 int sb_set_nonfinite_guard(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->guard = on ? 1 : 0;
+    c->sw.guard = on != 0;
     c->guard_rep_reset = true; c->guard_calls = 0; c->guard_last = false;
     return SB_OK;
 }
 
 int sb_set_nonfinite_guard_bands(sb_ctx *c, int on) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
-    c->guard_bands = on ? 1 : 0;
+    c->sw.guard_bands = on != 0;
     c->guard_rep_reset = true; c->guard_calls = 0; c->guard_last = false;
     // later band steps on the same planes get another Geo::band (the whole swap_bounds against neighbour rows only), which
     // the key of the strip kernel's stored plan does not hold: the next call plans afresh

@@ -1,7 +1,8 @@
-// sb_diag_plan.hpp -- which kernels a diag call enqueues, in which order and in which mode: decided here, in one pure
-// function, and nowhere else.  run_diag (sb_capi.hip) sizes its workspace from the plan, sb_launch_diag (sb_diag_kernels.hip)
-// walks its steps, band_diag_dev asks it for the contrast kernel.  Plain C++17: no HIP, no pointers, no heap -- a host
-// compiler builds it alone (tests/diag_plan_dump.cpp).
+// sb_diag_plan.hpp -- which kernels a diag call enqueues, in which order and in which mode, and which of the context's opt-in
+// switches serve it: decided here, in pure functions, and nowhere else.  run_diag (sb_capi.hip) hands sb_apply_switches the
+// switches and what it knows of the call, sizes its workspace from the plan, sb_launch_diag (sb_diag_kernels.hip) walks its
+// steps, band_diag_dev asks sb_band_folds_frame which ghost cells of theta a band step fills.  Plain C++17: no HIP, no pointers,
+// no heap -- a host compiler builds it alone (tests/plan_dump.cpp).
 #pragma once
 
 // kernels of a diag call that sb_profile_begin / sb_profile_end time, each with its own pair of events
@@ -263,4 +264,50 @@ inline SbGuardPlan sb_plan_guard(const SbPlanIn &in, const SbDiagPlan &p) {
     else if (p.contrast.strip == 2) gp.reach = SB_GUARD_REACH_STRIP32;
     else { gp.reach = SB_GUARD_BY_TILE; gp.tile_w = p.contrast.txw; gp.tile_rows = p.contrast.tyrows; gp.halo = p.contrast.Hk; }
     return gp;
+}
+
+// ---- the opt-in switches of a context (sb_set_table_contrast, _bands, _f2py, sb_set_table_window_cache, sb_set_nonfinite_guard,
+// _bands) and the calls each of them serves.  Every predicate over a switch and a call stands here once; sb_plan_diag and
+// sb_plan_guard above check the halves that they can see (`whole`, `t0_fly`) for themselves, so they are valid for any input.
+struct SbSwitches { bool table, table_bands, table_f2py, table_cache, guard, guard_bands; };
+// what run_diag knows of a call before it plans
+enum SbCallBnd { SB_CALL_BND_WRAPPER = 0, SB_CALL_BND_GLOBAL = 1, SB_CALL_BND_HALO = 2 };    // BND_* (sb_device.hpp)
+struct SbCall {
+    bool host_model;                // the host-model flavour (seabreeze_diag*, band steps); false: the f2py flavour (sb_diag_*, stream steps)
+    int bnd;                        // the boundary rule, SbCallBnd
+    bool ghost;                     // the ghost width is not 0
+    bool band_geo;                  // Geo::band is not 0: a band step whose strip kernel takes ghost cells of theta from its interior
+};
+// the two pairs of switches that a band step's frame depends on  (static, here and below: the library's exported symbols stay as they are)
+static inline bool sb_band_tables_on(const SbSwitches &s) { return s.table && s.table_bands; }
+static inline bool sb_band_guard_on(const SbSwitches &s) { return s.guard && s.guard_bands; }
+
+// Fills the switches' fields of `in` (table, band_table, f2py_table, guard, guard_bands; phases and gathered are set already)
+// and answers whether the call is a table call that keeps its windows (sb_set_table_window_cache): as sb_plan_diag decides
+// `table` for a whole call, and the switch.  Its k_scan watches the planes whatever the contrast kernel of the domain would
+// be: where that is the tile kernel, run_diag allocates the header of the strip kernel's plan alone.
+static inline bool sb_apply_switches(const SbSwitches &s, const SbCall &c, SbPlanIn &in) {
+    const bool whole = in.phases == 3 && !in.gathered;
+    // the tables and the guard's kernels see plain geometry: every ghost cell of the frame as filled
+    const bool host_frame = c.host_model && (c.bnd == SB_CALL_BND_GLOBAL || c.bnd == SB_CALL_BND_HALO) && !c.band_geo;
+    // the f2py flavour on the tables: a switch of its own beside sb_set_table_contrast, the wrapper's boundary rule alone
+    in.f2py_table = s.table && s.table_f2py && !c.host_model && c.bnd == SB_CALL_BND_WRAPPER && !c.ghost;
+    in.table = (s.table && host_frame) || in.f2py_table;
+    // ... and the tables for a band phase or a call with gathered moments: a switch of its own beside that one, ghost cells only
+    in.band_table = sb_band_tables_on(s) && host_frame && c.bnd == SB_CALL_BND_HALO && !whole;
+    // the guard for missing and non-finite temperatures: a plan of its own (sb_plan_guard), whatever the flavour
+    in.guard = s.guard && !c.band_geo;
+    in.guard_bands = sb_band_guard_on(s) && !c.band_geo;
+    return s.table_cache && in.table && whole;
+}
+
+// A band step (band_diag_dev) on a strip kernel sends only the ghost rows of theta that come from a neighbour; the east-west
+// ghost columns and the rows beyond a pole follow from theta's interior, and the strip kernels take them from there by index
+// (Geo::band != 0) -- which needs a circle of latitude wider than any row they stage (sb_strip_common.hpp: one wrap of the index
+// then suffices).  Never where the band tables or the band guard may be served: they read the whole frame as filled, so theta
+// gets the whole swap_bounds and Geo::band stays 0, which is what sb_apply_switches asks of the two phases that follow.
+// `k`: sb_plan_contrast of the band.
+enum { SB_BAND_FOLD_NX_ABOVE = 96 + 2 };
+static inline bool sb_band_folds_frame(const SbSwitches &s, const SbContrast &k, int nx) {
+    return !sb_band_tables_on(s) && !sb_band_guard_on(s) && k.strip != 0 && nx > SB_BAND_FOLD_NX_ABOVE;
 }

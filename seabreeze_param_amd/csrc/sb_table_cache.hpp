@@ -4,7 +4,7 @@
 // under this call's number, so the table kernels evaluate  fill = host_force || *plan_gen == call_id.  The device sees a
 // coast that moved; only the host knows WHICH call left the planes k_scan compared with -- and W belongs to the planes of
 // the last table call that ran with the cache in effect.  Plain C++17: no HIP, no heap -- a host compiler builds it alone
-// (tests/table_cache_dump.cpp).
+// (tests/plan_dump.cpp).
 #pragma once
 
 #ifndef SB_TAB_REACH

@@ -3,48 +3,24 @@ sb_set_table_contrast): a band step of the host-model flavour becomes SCAN, PREP
 CONTRAST (the table query, which applies the update); a whole call with gathered moments the same seven steps in one sequence.
 Every other call -- and every call while `table` is off -- keeps the sequence it has without the switch.
 
-tests/band_table_plan_dump.cpp is tests/table_plan_dump.cpp with the one more input; it is built host-only, the way
-tests/test_table_plan.py builds its program.  The expectations are written out by hand from the table of launch sequences
-in DESIGN.md section 2.3.
+tests/plan_dump.cpp is built host-only (tests/plan_dump.py); `gathered`, `table` and `band_table` are 1 here unless a case
+says otherwise.  The expectations are written out by hand from the table of launch sequences in DESIGN.md section 2.3.
 """
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("phases", "esize", "t0_fly", "hint", "no_wide", "no_fold", "no_cache", "late", "gathered", "mout", "reuse",
-          "plan_use", "segs_built", "wgs", "fits", "table", "band_table")
-DEFAULT = dict(phases=3, esize=8, t0_fly=1, hint=6, no_wide=0, no_fold=0, no_cache=0, late=0, gathered=1, mout=0, reuse=0,
-               plan_use=0, segs_built=0, wgs=12, fits=1, table=1, band_table=1)
+import plan_dump as pd
 
 
 def _line(label, **kw):
-    c = dict(DEFAULT, **kw)
-    return label + " " + " ".join(str(c[f]) for f in FIELDS)
+    return pd.line(label, **dict(dict(gathered=1, table=1, band_table=1), **kw))
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/band_table_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "band_table_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "band_table_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: (contrast, [steps], kept)}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {}
-        for ln in out.splitlines():
-            label, contrast, steps, kept = (s.strip() for s in ln.split("|"))
-            res[label] = (contrast, steps.split(), kept)
-        assert len(res) == len(lines)
-        return res
-    return run
+    exe = pd.build(tmp_path_factory)
+    return lambda lines: pd.plans(exe, lines)       # -> {label: (contrast, [steps], kept, guard, guard tail)}
 
 
 # phase 1 of a band step (k_scan publishes the band's moments), phase 2, and the gathered call: no step is `final` -- k_wind
@@ -53,7 +29,7 @@ PH1 = ["SCAN:prof=scan,stats=partials*0,publish", "PREP:prof=prep,stats=none*0",
 PH1_REUSE = ["SCAN:prof=scan,stats=none*0", "PREP:prof=prep,stats=none*0", "WIND:prof=wind,stats=none*0"]
 MERGE = ["MERGE:prof=none,stats=gathered*0"]
 TABLES = ["TABLE_ROWS:prof=t0,stats=none*0", "TABLE_COLS:prof=thc,stats=none*0", "CONTRAST:prof=thc,stats=none*0,table"]
-KEPT = "segs_built=0 wind_scratch=1 scan_wgs=12 table=1"
+KEPT = lambda nsteps: pd.kept(0, 1, 1, nsteps)      # segs_built=0 wind_scratch=1 scan_wgs=12 table=1, and the step count
 
 GRID = list(itertools.product((8, 4), (6, 24, 31)))         # both precisions, the strip kernels' and the tile kernel's radius hints
 
@@ -70,7 +46,7 @@ def test_band_step_phases(dump):
             want["ph2/" + k] = TABLES if reuse else MERGE + TABLES
     got = dump(lines)
     for k, steps in want.items():
-        assert got[k][1] == steps and got[k][2] == KEPT, (k, got[k])
+        assert got[k][1] == steps and got[k][2] == KEPT(len(steps)), (k, got[k])
 
 
 def test_whole_call_with_gathered_moments(dump):
@@ -83,7 +59,7 @@ def test_whole_call_with_gathered_moments(dump):
             want[k] = PH1_REUSE + ([] if reuse else MERGE) + TABLES
     got = dump(lines)
     for k, steps in want.items():
-        assert got[k][1] == steps and got[k][2] == KEPT, (k, got[k])
+        assert got[k][1] == steps and got[k][2] == KEPT(len(steps)), (k, got[k])
     assert len(want["8/6/0"]) == 7
 
 
@@ -99,7 +75,7 @@ def test_knobs_of_the_other_kernels_do_not_matter(dump):
     for k in cases:
         assert got[k + "/ph1"][1] == PH1 and got[k + "/ph2"][1] == MERGE + TABLES, (k, got[k + "/ph1"], got[k + "/ph2"])
         assert got[k + "/whole"][1] == PH1_REUSE + MERGE + TABLES, (k, got[k + "/whole"])
-        assert all(got[f"{k}/{p}"][2] == KEPT for p in ("ph1", "ph2", "whole")), k
+        assert all(got[f"{k}/{p}"][2] == KEPT(n) for p, n in (("ph1", 3), ("ph2", 4), ("whole", 7))), k
 
 
 FLAGS = ("no_wide", "no_fold", "no_cache", "late", "mout", "reuse", "plan_use", "segs_built")
@@ -139,7 +115,7 @@ def test_nothing_changes_while_the_table_switch_is_off(dump):
     got, pairs = _pairs(dump, sels, dict(band_table=1, table=0), dict(band_table=0, table=0))
     for off, on in pairs:
         assert got[on] == got[off], (on, got[on], got[off])
-        assert got[on][2].endswith("table=0") and not any("TABLE" in s or s.endswith(",table") for s in got[on][1])
+        assert " table=0 " in got[on][2] and not any("TABLE" in s or s.endswith(",table") for s in got[on][1])
 
 
 def test_switch_off_is_the_plan_of_today(dump):
@@ -151,4 +127,4 @@ def test_switch_off_is_the_plan_of_today(dump):
     }
     got = dump([_line(k, band_table=0, **kw) for k, (kw, _) in want.items()])
     for k, (_, steps) in want.items():
-        assert got[k][1] == steps and got[k][2].endswith("table=0"), (k, got[k])
+        assert got[k][1] == steps and " table=0 " in got[k][2], (k, got[k])

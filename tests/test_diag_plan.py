@@ -1,47 +1,22 @@
 """The launch plan of a diag call (seabreeze_param_amd/csrc/sb_diag_plan.hpp): which kernels, in which order, in which mode.
 
-tests/diag_plan_dump.cpp is built host-only with the compiler that builds the library and prints the plan of every case
-it is given.  The expectations below are written out by hand from the table of launch sequences in DESIGN.md section 2.3;
-nothing here is produced by the planner.  The domain is 200 x 96 cells, k_scan runs 12 workgroups there.
+tests/plan_dump.cpp is built host-only with the compiler that builds the library and prints the plan of every case
+it is given (tests/plan_dump.py).  The expectations below are written out by hand from the table of launch sequences in
+DESIGN.md section 2.3; nothing here is produced by the planner.  The domain is 200 x 96 cells, k_scan runs 12 workgroups there.
 """
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("phases", "esize", "t0_fly", "hint", "no_wide", "no_fold", "no_cache", "late", "gathered", "mout", "reuse",
-          "plan_use", "segs_built", "wgs", "fits")
-DEFAULT = dict(phases=3, esize=8, t0_fly=1, hint=6, no_wide=0, no_fold=0, no_cache=0, late=0, gathered=0, mout=0, reuse=0,
-               plan_use=0, segs_built=0, wgs=12, fits=1)
+import plan_dump as pd
 
-
-def _line(label, **kw):
-    c = dict(DEFAULT, **kw)
-    return label + " " + " ".join(str(c[f]) for f in FIELDS)
+_line = pd.line
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/diag_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "diag_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "diag_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: (contrast, [steps], kept)}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {}
-        for ln in out.splitlines():
-            label, contrast, steps, kept = (s.strip() for s in ln.split("|"))
-            res[label] = (contrast, steps.split(), kept)
-        assert len(res) == len(lines)
-        return res
-    return run
+    exe = pd.build(tmp_path_factory)
+    return lambda lines: pd.plans(exe, lines)       # -> {label: (contrast, [steps], kept, guard, guard tail)}
 
 
 STRIP = "strip=1 Hk=16 tile=32x16 grid=7x6 vb=1 nflag=58"          # 7 strips x (6 + 2 virtual) blocks + 2 counters
@@ -127,7 +102,8 @@ def test_named_cases(dump):
             if contrast[esize] is None:
                 continue
             lines.append(_line(f"{name}/{esize}", esize=esize, **kw))
-            want[f"{name}/{esize}"] = (contrast[esize], steps, f"segs_built={built} wind_scratch={scratch} scan_wgs=12")
+            want[f"{name}/{esize}"] = (contrast[esize], steps, pd.kept(built, scratch, 0, len(steps)),
+                                       pd.GUARD_OFF, pd.TAIL_OFF)
     got = dump(lines)
     for label in want:
         assert got[label] == want[label], label
@@ -153,7 +129,7 @@ def test_invariants_over_the_input_space(dump):
             lines.append(_line(f"c{len(lines)}", phases=phases, esize=esize, hint=hint, wgs=wgs, **dict(zip(flags, bits))))
     got = dump(lines)
     assert len(got) == 3 * 2 * 3 * 2 * 1024
-    for label, (contrast, steps, kept) in got.items():
+    for label, (contrast, steps, kept, _, _) in got.items():
         names = [s.split(":")[0] for s in steps]
         assert 1 <= len(steps) <= 6, (label, steps)
         assert names.count("CONTRAST") <= 1 and names.count("WIND") <= 1, (label, steps)

@@ -4,54 +4,30 @@ writes the t0 plane), TABLE_COLS, CONTRAST (the table query), WIND -- six launch
 Every other call -- the host-model flavour, band phases, gathered moments, and every call while `table` is off -- keeps the
 plan it has without the input.
 
-tests/f2py_table_plan_dump.cpp is tests/band_table_plan_dump.cpp with the one more input, built host-only the way
-tests/test_band_table_plan.py builds its program; it also drives the host's half of the window cache
-(sb_table_cache.hpp) for the keys of wrapper calls.  The expectations are written out by hand from the table of launch
-sequences in DESIGN.md section 2.3.
+tests/plan_dump.cpp is built host-only (tests/plan_dump.py); here `t0_fly` is 0, `table` and `f2py_table` are 1 unless a case
+says otherwise.  The program also drives the host's half of the window cache (sb_table_cache.hpp) for the keys of wrapper
+calls.  The expectations are written out by hand from the table of launch sequences in DESIGN.md section 2.3.
 """
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("phases", "esize", "t0_fly", "hint", "no_wide", "no_fold", "no_cache", "late", "gathered", "mout", "reuse",
-          "plan_use", "segs_built", "wgs", "fits", "table", "band_table", "f2py_table")
-DEFAULT = dict(phases=3, esize=8, t0_fly=0, hint=6, no_wide=0, no_fold=0, no_cache=0, late=0, gathered=0, mout=0, reuse=0,
-               plan_use=0, segs_built=0, wgs=12, fits=1, table=1, band_table=0, f2py_table=1)
-BND_WRAPPER, BND_GLOBAL = 0, 1
+import plan_dump as pd
+from plan_dump import BND_GLOBAL, BND_WRAPPER
 
 
 def _line(label, **kw):
-    c = dict(DEFAULT, **kw)
-    return "plan " + label + " " + " ".join(str(c[f]) for f in FIELDS)
+    return pd.line(label, **dict(dict(t0_fly=0, table=1, f2py_table=1), **kw))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/f2py_table_plan_dump.cpp with")
-    out = str(tmp_path_factory.mktemp("plan") / "f2py_table_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "f2py_table_plan_dump.cpp"), "-o", out],
-                   check=True)
-    return out
+    return pd.build(tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def dump(exe):
-    def run(lines):
-        """-> {label: (contrast, [steps], kept)}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {}
-        for ln in out.splitlines():
-            label, contrast, steps, kept = (s.strip() for s in ln.split("|"))
-            res[label] = (contrast, steps.split(), kept)
-        assert len(res) == len(lines)
-        return res
-    return run
+    return lambda lines: pd.plans(exe, lines)       # -> {label: (contrast, [steps], kept, guard, guard tail)}
 
 
 SIX = ["SCAN:prof=scan,stats=partials*0,final", "PREP:prof=prep,stats=partials*12,final", "TABLE_ROWS:prof=t0,stats=none*0,final",
@@ -126,7 +102,7 @@ def test_input_changes_nothing_where_it_does_not_apply(dump):
 
 
 def _cache(exe, lines):
-    return subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split()
+    return pd.run(exe, lines)
 
 
 def test_window_cache_host_half_for_wrapper_calls(exe):

@@ -2,36 +2,24 @@
 sb_table_cache.hpp): when the host forces a table call to search every window again, and the word of plane W.
 
 The device's half -- k_scan reports a changed plane under the call's number -- sees a coast that moved, but only the host
-knows which call left the planes k_scan compared with.  tests/table_cache_dump.cpp drives the decision from standard
-input; it is built host-only, the way tests/test_table_plan.py builds its program.  Every forcing condition is run on its
-own from a steady state, and the call after it is steady again.
+knows which call left the planes k_scan compared with.  tests/plan_dump.cpp drives the decision from standard input
+(its `call`, `other`, `failed`, `toggled` and `word` commands); it is built host-only (tests/plan_dump.py).  Every forcing
+condition is run on its own from a steady state, and the call after it is steady again.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import plan_dump as pd
 import table_ref as tr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("nx", "ny", "h", "bnd", "rows", "band", "cls", "W", "C")
 KEY = dict(nx=160, ny=112, h=0, bnd=1, rows=112, band=4096, cls=8192, W=12288, C=16384)
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/table_cache_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("tabcache") / "table_cache_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "table_cache_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        return subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
-    return run
+    exe = pd.build(tmp_path_factory)
+    return lambda lines: pd.run(exe, lines)
 
 
 def _call(seq, **kw):

@@ -2,56 +2,33 @@
 flavour becomes SCAN, PREP, TABLE_ROWS, TABLE_COLS, CONTRAST (the table query), WIND -- six launches, the two table passes
 not fused; every other call keeps the sequence it has without the switch.
 
-tests/table_plan_dump.cpp is tests/diag_plan_dump.cpp with the one more input; it is built host-only, the way
-tests/test_diag_plan.py builds its program.  The expectations are written out by hand from the table of launch sequences
-in DESIGN.md section 2.3.  The boundary mode is not the planner's business: the caller sets `table` for SB_BND_GLOBAL and
-SB_BND_HALO alike (the GPU tests run both), and the plan of a table call does not depend on the contrast kernel the
-domain would otherwise get -- the cases run every radius hint and both precisions.
+tests/plan_dump.cpp is built host-only (tests/plan_dump.py); `table` is 1 here unless a case says otherwise.  The
+expectations are written out by hand from the table of launch sequences in DESIGN.md section 2.3.  The boundary mode is
+not the planner's business: the caller sets `table` for SB_BND_GLOBAL and SB_BND_HALO alike (the GPU tests run both), and
+the plan of a table call does not depend on the contrast kernel the domain would otherwise get -- the cases run every
+radius hint and both precisions.
 """
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("phases", "esize", "t0_fly", "hint", "no_wide", "no_fold", "no_cache", "late", "gathered", "mout", "reuse",
-          "plan_use", "segs_built", "wgs", "fits", "table")
-DEFAULT = dict(phases=3, esize=8, t0_fly=1, hint=6, no_wide=0, no_fold=0, no_cache=0, late=0, gathered=0, mout=0, reuse=0,
-               plan_use=0, segs_built=0, wgs=12, fits=1, table=1)
+import plan_dump as pd
 
 
 def _line(label, **kw):
-    c = dict(DEFAULT, **kw)
-    return label + " " + " ".join(str(c[f]) for f in FIELDS)
+    return pd.line(label, **dict(dict(table=1), **kw))
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/table_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "table_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "table_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: (contrast, [steps], kept)}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {}
-        for ln in out.splitlines():
-            label, contrast, steps, kept = (s.strip() for s in ln.split("|"))
-            res[label] = (contrast, steps.split(), kept)
-        assert len(res) == len(lines)
-        return res
-    return run
+    exe = pd.build(tmp_path_factory)
+    return lambda lines: pd.plans(exe, lines)       # -> {label: (contrast, [steps], kept, guard, guard tail)}
 
 
 TABLE_STEPS = ["SCAN:prof=scan,stats=partials*0,final", "PREP:prof=prep,stats=partials*12,final",
                "TABLE_ROWS:prof=t0,stats=none*0,final", "TABLE_COLS:prof=thc,stats=none*0,final",
                "CONTRAST:prof=thc,stats=none*0,final,table", "WIND:prof=wind,stats=none*0,final"]
-TABLE_KEPT = "segs_built=0 wind_scratch=0 scan_wgs=12 table=1"
+TABLE_KEPT = "segs_built=0 wind_scratch=0 scan_wgs=12 table=1 nsteps=6 max=7"
 
 
 def test_whole_host_model_call_takes_the_tables(dump):
@@ -89,7 +66,7 @@ def test_switch_is_ignored_where_it_does_not_apply(dump):
     for off, on in zip(labels[0::2], labels[1::2]):
         assert off.endswith("/0") and on.endswith("/1")
         assert got[on] == got[off], (on, got[on], got[off])
-        assert got[on][2].endswith("table=0") and not any("TABLE" in s or s.endswith(",table") for s in got[on][1])
+        assert " table=0 " in got[on][2] and not any("TABLE" in s or s.endswith(",table") for s in got[on][1])
 
 
 def test_named_sequences_with_the_switch_set(dump):
@@ -114,4 +91,4 @@ def test_switch_off_is_the_plan_of_today(dump):
     got = dump([_line("off", table=0)])
     assert got["off"][1] == ["SCAN:prof=scan,stats=partials*0,final", "CONTRAST:prof=thc,stats=partials*12,fold,final",
                              "WIND:prof=wind,stats=none*0,final"]
-    assert got["off"][2] == "segs_built=1 wind_scratch=0 scan_wgs=12 table=0"
+    assert got["off"][2] == "segs_built=1 wind_scratch=0 scan_wgs=12 table=0 nsteps=3 max=7"
