@@ -465,6 +465,55 @@ int sb_diag_stream_end_f64(sb_ctx *ctx, double *sb_con_last, double *output4, do
 int sb_diag_stream_stats(sb_ctx *ctx, long *steps, double seconds[3]);
 
 /* -------------------------------------------------------------------------------- */
+/* diag, streamed, with sea ice that moves: the coast follows on the device (opt-in)  */
+/* replaces: get_edges(lsm, ci[ts]) -> get_dist(coast, lsm, lon, lat) of every step of */
+/*           the reference's driver, ref: python_wrapper/seabreezediag/__init__.py:    */
+/*           222-245 (the ice plane is part of the land class, ref: sobel.f90:51).     */
+/* A stream that never calls these behaves and costs as before.                        */
+/* sb_diag_stream_coast: once, between sb_diag_stream_begin and the first step.  lsm   */
+/* (nlons,nlats), lon(nlons), lat(nlats) are host pointers; lsm is uploaded and kept,   */
+/* the window half-width k follows from maxdist_km as in sb_get_dist_* with kwin < 0   */
+/* (same refusals: k > SB_DIST_MAX_WINDOW, the latitude nearest 70 degrees in the last */
+/* row), and the search radius hint becomes k + 1.  The stream gets a coast bit plane  */
+/* of its own.  incremental = 0: every ice call computes the whole grid (k_edges and   */
+/* the whole-grid distance launch: the A/B and fallback path); grids narrower than the */
+/* window (2k + 1 > nlons, k <= 31) take that path whatever is asked.                  */
+/* sb_diag_stream_ice: ci(nlons,nlats), a host pointer, is staged through pinned       */
+/* memory like a step's planes, and the update of the stream's resident cdist plane is */
+/* enqueued on the context's stream, in order between the steps: rule 0 (lsm + ci >    */
+/* 0.4) and the wrapper's neighbour indexing as sb_get_edges_*(rule 0, SB_BND_WRAPPER), */
+/* the sign from lsm as the driver's get_dist(coast, lsm, ...).  No synchronisation,   */
+/* no download, no comparison on the host.  The cdist handed to sb_diag_stream_begin   */
+/* is replaced by the first ice call, which computes everything.  Later calls compare  */
+/* the new coast with the stored one in 64-cell words; a changed word at columns       */
+/* x0 .. x0+63 of row y marks the (target row, 256-column tile) pairs of rows y-k ..   */
+/* y+k (clamped) and columns x0-k .. x0+63+k (circular; the whole row where 2k + 64 >= */
+/* nlons), and the distance kernel computes the marked tiles again.  That is exact: a  */
+/* target reads coast cells of its own window only, the tiles hold whole waves, and an  */
+/* unmarked tile's windows hold no changed cell, so the resident plane equals, bit for */
+/* bit, sb_get_edges_* + sb_get_dist_*(kwin = -1) of the same inputs after every call. */
+/* sb_diag_stream_ice_report (synchronises): [0] ice calls of this stream [1] those     */
+/* after the first whose coast differed (-1 on the whole-grid path: nothing is          */
+/* compared there) [2] tiles the last call marked [3] tiles of the grid.                */
+/* sb_diag_stream_get_cdist (synchronises): the resident distance plane, for            */
+/* inspection and tests.                                                                */
+/* sb_diag_stream_ice_time (waits for the last ice call): the HIP-event time in ms of   */
+/* its device work -- the plane's upload, the clear of the marks, the kernels -- between */
+/* two events every ice call records on the context's stream (the stream is the         */
+/* context's own, so a caller cannot place events there): for measurements.             */
+/* -------------------------------------------------------------------------------- */
+int sb_diag_stream_coast_f32(sb_ctx *ctx, const float *lsm, const float *lon, const float *lat, float maxdist_km,
+                             int incremental);
+int sb_diag_stream_coast_f64(sb_ctx *ctx, const double *lsm, const double *lon, const double *lat, double maxdist_km,
+                             int incremental);
+int sb_diag_stream_ice_f32(sb_ctx *ctx, const float *ci);
+int sb_diag_stream_ice_f64(sb_ctx *ctx, const double *ci);
+int sb_diag_stream_ice_report(sb_ctx *ctx, long long rep[4]);
+int sb_diag_stream_ice_time(sb_ctx *ctx, double *ms);
+int sb_diag_stream_get_cdist_f32(sb_ctx *ctx, float *cdist);
+int sb_diag_stream_get_cdist_f64(sb_ctx *ctx, double *cdist);
+
+/* -------------------------------------------------------------------------------- */
 /* sigmoid                                                                           */
 /* replaces: subroutine sigmoid(ary, sm)  ref: generic/sea_breeze_diag.f90:457-481,  */
 /*           seabreeze_diag_python.f90:287-311                                       */

@@ -71,6 +71,24 @@ module sb_f2py_state
       integer(c_long), intent(out) :: steps
       real(c_double), intent(out) :: seconds(3)
     end function
+    integer(c_int) function sb_diag_stream_coast_f32(ctx, lsm, lon, lat, maxdist, incremental) &
+        bind(C, name="sb_diag_stream_coast_f32")
+      import :: c_ptr, c_int, c_float
+      type(c_ptr), value :: ctx
+      real(c_float), intent(in) :: lsm(*), lon(*), lat(*)
+      real(c_float), value :: maxdist
+      integer(c_int), value :: incremental
+    end function
+    integer(c_int) function sb_diag_stream_ice_f32(ctx, ci) bind(C, name="sb_diag_stream_ice_f32")
+      import :: c_ptr, c_int, c_float
+      type(c_ptr), value :: ctx
+      real(c_float), intent(in) :: ci(*)
+    end function
+    integer(c_int) function sb_diag_stream_ice_report(ctx, rep) bind(C, name="sb_diag_stream_ice_report")
+      import :: c_ptr, c_int, c_long_long
+      type(c_ptr), value :: ctx
+      integer(c_long_long), intent(out) :: rep(4)
+    end function
     integer(c_int) function sb_set_table_contrast(ctx, on) bind(C, name="sb_set_table_contrast")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx

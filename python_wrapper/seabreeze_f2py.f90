@@ -142,6 +142,12 @@ end subroutine get_threads
 !   set_nonfinite_guard(on)
 !        opt-in: diag and the streamed steps find NaN, Inf and missing (2e20) temperatures and compute the band cells whose
 !        windows hold them again as the reference does (include/seabreeze_hip.h: sb_set_nonfinite_guard).
+!   stream_coast(lsm, lon, lat, [maxdist, incremental]) / stream_ice(ci) / rep = stream_ice_report()
+!        opt-in, between stream_begin and the first stream_step: the stream follows sea ice that moves.  stream_ice, ahead
+!        of a step, enqueues get_edges(lsm, ci) -> get_dist(coast, lsm, lon, lat, maxdist) into the stream's resident cdist
+!        on the device, computing again only what a changed coast cell can reach (include/seabreeze_hip.h:
+!        sb_diag_stream_coast, sb_diag_stream_ice); rep: ice calls, those after the first whose coast differed, tiles the
+!        last call marked, tiles of the grid (sb_diag_stream_ice_report).
 !===============================================================================
 subroutine last_status(rc)
   use sb_f2py_state
@@ -293,3 +299,59 @@ subroutine last_launches(n)
   rc = sb_last_step_report(ctx, rep)
   if (rc == 0) n = rep(1)
 end subroutine last_launches
+
+subroutine stream_coast(lsm, lon, lat, maxdist, incremental, nlons, nlats)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer :: nlons, nlats, incremental
+  real, dimension(nlons) :: lon
+  real, dimension(nlats) :: lat
+  real, dimension(nlons,nlats) :: lsm
+  real :: maxdist
+  integer(c_int) :: rc
+  !f2py integer, intent(in) :: nlons, nlats
+  !f2py real, intent(in) :: lsm, lon, lat
+  !f2py real optional, intent(in) :: maxdist = 180
+  !f2py integer optional, intent(in) :: incremental = 1
+  call sb_ok()
+  call sb_ensure()
+  if (.not. c_associated(ctx)) return
+  rc = sb_diag_stream_coast_f32(ctx, lsm, lon, lat, maxdist, merge(1_c_int, 0_c_int, incremental /= 0))
+  if (rc /= 0) call sb_fail('stream_coast', rc)
+end subroutine stream_coast
+
+subroutine stream_ice(ci, nlons, nlats)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer :: nlons, nlats
+  real, dimension(nlons,nlats) :: ci
+  integer(c_int) :: rc
+  !f2py integer, intent(in) :: nlons, nlats
+  !f2py real, intent(in) :: ci
+  call sb_ok()
+  call sb_ensure()
+  if (.not. c_associated(ctx)) return
+  rc = sb_diag_stream_ice_f32(ctx, ci)
+  if (rc /= 0) call sb_fail('stream_ice', rc)
+end subroutine stream_ice
+
+subroutine stream_ice_report(rep)
+  use iso_c_binding
+  use sb_f2py_state
+  implicit none
+  integer(8) :: rep(4)
+  integer(c_long_long) :: r(4)
+  integer(c_int) :: rc
+  !f2py integer(8), intent(out) :: rep
+  rep = 0
+  call sb_ok()
+  if (.not. c_associated(ctx)) return
+  rc = sb_diag_stream_ice_report(ctx, r)
+  if (rc /= 0) then
+    call sb_fail('stream_ice_report', rc)
+  else
+    rep = r
+  end if
+end subroutine stream_ice_report

@@ -149,6 +149,14 @@ def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
     computes the band cells whose windows hold them again, the reference's way (``sb_set_nonfinite_guard``; without it
     those cells hold finite, wrong numbers).  Switched on before the first step and off again when the call returns.
 
+    ``ice_on_device=True`` (not in the reference; off by default): for sea ice that moves.  The stream is opened once and
+    keeps the land mask and the coast on the device; every step whose ice plane is not provably the memory of the step
+    before hands its plane to ``stream_ice``, which finds the coast cells that changed and computes again only the part
+    of the distance field they can reach -- the same numbers as ``get_edges`` + ``get_dist`` of every step, with no
+    distance field, comparison or close-and-reopen on the host (``sb_diag_stream_coast``, ``sb_diag_stream_ice``).  The
+    distance field is made with ``get_dist``'s default ``maxdist`` of 180 km, as by the driver without the keyword.  On
+    the step-by-step path (``SEABREEZE_NO_STREAM=1``) the keyword changes nothing.
+
     Returns ``(tt, sb_con, thc, ws, wd)``; ``sb_con`` is float64 ``(ntime, lat, lon)``.
     """
     table = bool(_pop(kwargs, "table_contrast", False))
@@ -172,6 +180,7 @@ def diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
 
 
 def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
+    ice_dev = bool(_pop(kwargs, "ice_on_device", False))
     ws, wd, thc = (_pop(kwargs, k) for k in ("ws", "wd", "thc"))
     meta = _pop(kwargs, "meta")
     out_arr = _pop(kwargs, "out")
@@ -212,17 +221,27 @@ def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
         sb_all = out_arr
         sb_all[:, -1, :] = 0.0                    # (the kernels leave the last latitude row alone, ref seabreeze_diag_python.f90:165:
                                                   #  in a fresh result array it reads 0.0, so it does here)
-    dist = None if ci is not None else _coast_distance(lsm, np.zeros_like(lsm), lon, lat)
+    streaming = _HAVE_STREAM and not os.environ.get("SEABREEZE_NO_STREAM")
+    ice_dev = ice_dev and streaming                # (the step-by-step path has no resident distance field to update)
+    if ice_dev and not all(hasattr(_ext, n) for n in ("stream_coast", "stream_ice")):
+        raise RuntimeError("ice_on_device=True: this build of the `seabreeze` extension has no stream_coast / stream_ice")
+    dist = None if (ci is not None or ice_dev) else _coast_distance(lsm, np.zeros_like(lsm), lon, lat)
 
     static_seen = [False]
     last_ice = [None]                                        # the ice plane of the step before, where it is PROVABLY this one
 
+    def ice_plane(ts):
+        """The step's ice plane as float32, and where it lies if it is provably the caller's own memory (else None)."""
+        ice = ci[ts] if has_time else ci
+        ice = ice.filled(0) if hasattr(ice, "filled") else ice
+        ice = np.asarray(ice, dtype=np.float32)              # what f2py would make of it (file data may be big-endian)
+        provable = isinstance(ci, np.ndarray) and np.may_share_memory(ice, ci)
+        return ice, ((ice.__array_interface__["data"][0], ice.shape, ice.strides) if provable else None)
+
     def step_inputs(ts):
         nonlocal dist
-        if ci is not None:
-            ice = ci[ts] if has_time else ci
-            ice = ice.filled(0) if hasattr(ice, "filled") else ice
-            ice = np.asarray(ice, dtype=np.float32)          # what f2py would make of it (file data may be big-endian)
+        if ci is not None and not ice_dev:
+            ice, where = ice_plane(ts)
             # the reference recomputes it every step (:223-228); here: when the ice changes.  lsm, lon, lat are this
             # call's arguments: compared with the kept copies at the first step only.  The comparison of the ice plane
             # itself (0.3 ms at 1024 x 768) is skipped only where the plane is provably the memory of the step before:
@@ -230,8 +249,6 @@ def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
             # this step's plane is the same window into it -- a broadcast time axis, or no time axis.  An equal address
             # alone proves nothing: a file reader hands out views of per-read temporaries (netCDF4's `data[...]`, a
             # nomask MaskedArray's `filled()`), and the next read may land where the last one was freed.
-            provable = isinstance(ci, np.ndarray) and np.may_share_memory(ice, ci)
-            where = (ice.__array_interface__["data"][0], ice.shape, ice.strides) if provable else None
             if not (static_seen[0] and where is not None and where == last_ice[0]):
                 dist = _coast_distance(lsm, ice, lon, lat, static_known_same=static_seen[0])
             last_ice[0] = where
@@ -239,7 +256,37 @@ def _diag(tt, lsm, z, std, lon, lat, pres, *args, **kwargs):
         return (t[ts], v[ts], u[ts]) if has_time else (t[:], v[:], u[:])
 
     f32 = lambda a: np.asarray(a, dtype=np.float32)
-    if _HAVE_STREAM and not os.environ.get("SEABREEZE_NO_STREAM"):
+    if ice_dev:
+        # one stream for the whole call: the land mask and the coast stay on the device beside z, std and the state, and
+        # an ice plane that may differ from the one before is handed over ahead of its step -- the device finds out what
+        # moved and computes that part of the distance field again (seabreeze_f2py.f90: stream_coast, stream_ice).  No
+        # distance field on the host, no comparison of planes, no close and reopen.
+        zf, sdf, pf = c2f(f32(z)), c2f(f32(std)), c2f(f32(pres))
+        scratch = np.zeros((nlon, nlat), order="F")
+        nothing = np.zeros((nlon, nlat), np.float32, order="F")
+        _ext.stream_begin(zf, sdf, nothing, c2f(f32(ws)), c2f(f32(wd)), c2f(f32(thc)))     # (the first ice call fills cdist)
+        _check("stream_begin")
+        _ext.stream_coast(c2f(f32(lsm)), f32(lon), f32(lat))     # get_dist's default maxdist, as the reference's driver (ref :228)
+        _check("stream_coast")
+        last = None
+        for ts in range(nt):
+            if ci is None:
+                ice, where = nothing.T, "no ice"
+            else:
+                ice, where = ice_plane(ts)
+            if where is None or where != last:
+                _ext.stream_ice(c2f(ice))
+                _check("stream_ice")
+            last = where
+            tk, vk, uk = step_inputs(ts)
+            _ext.stream_step(tt, pf, c2f(f32(tk)), c2f(f32(vk)), c2f(f32(uk)), scratch if ts == 0 else c2f(sb_all[ts - 1]), **kwargs)
+            _check("stream_step")
+            tt += 1
+        out, ws, wd, thc = _ext.stream_end(c2f(sb_all[nt - 1]))
+        _check("stream_end")
+        out = c2f(out)
+        return tt, sb_all, np.array(out[1]), np.array(out[2]), np.array(out[3])
+    if streaming:
         # z, std, the distance field and the carried state stay on the device; sb_con of step ts-1 arrives while
         # step ts is being staged, straight into its plane of sb_all (the transpose view of a C-ordered plane is
         # the Fortran-ordered array the extension writes in place)

@@ -5,6 +5,7 @@
 // fallback anywhere in this file: no device => SB_ERR_NO_DEVICE.
 #include "../../include/seabreeze_hip.h"
 #include "sb_launch.hpp"
+#include "sb_ice_plan.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -118,6 +119,20 @@ struct DiagStream {
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
     long steps = 0;
     double host_copy_s = 0.0, enqueue_s = 0.0, wait_s = 0.0;   // where the host spent its time (sb_diag_stream_stats)
+    // a coast that moves with the sea ice (sb_diag_stream_coast / _ice): the land mask and the step's ice plane, the
+    // stream's own coast bit plane (the context's `coastbits` is scratch of other get_dist calls), [marks | rep] and, on
+    // the whole-grid path, a coast plane; the pinned staging of the ice plane; what sb_diag_stream_coast derived
+    bool ice_ready = false;                    // sb_diag_stream_coast since the last sb_diag_stream_begin
+    DevBuf lsm, ice, icebits, icemarks, icecoast;
+    void *pin_ice[2] = {nullptr, nullptr};
+    size_t pin_ice_cap = 0;
+    hipEvent_t ev_ice[2] = {nullptr, nullptr};
+    hipEvent_t ev_ice_t[2] = {nullptr, nullptr};   // round the device work of the last ice call (sb_diag_stream_ice_time)
+    std::vector<unsigned char> ice_lonlat;     // lon(nlons) | lat(nlats): every ice call keys the coordinate tables with them
+    int ice_k = 0, ice_incremental = 1;
+    double ice_maxdist = 0.0;
+    size_t ice_mark_bytes = 0;                 // bytes of the mark plane, rounded up to a word; rep follows
+    long long ice_calls = 0;
 };
 
 struct sb_ctx {
@@ -799,9 +814,16 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 void stream_release(sb_ctx *c) {
     DiagStream &d = c->ds;
-    for (DevBuf *b : {&d.z, &d.sd, &d.cdist, &d.ws, &d.wd, &d.thc, &d.p1, &d.theta, &d.v, &d.u, &d.out})
+    for (DevBuf *b : {&d.z, &d.sd, &d.cdist, &d.ws, &d.wd, &d.thc, &d.p1, &d.theta, &d.v, &d.u, &d.out, &d.lsm, &d.ice, &d.icebits,
+                      &d.icemarks, &d.icecoast})
         if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     for (int k = 0; k < 2; ++k) {
+        if (d.pin_ice[k]) (void)hipHostFree(d.pin_ice[k]);
+        if (d.ev_ice[k]) (void)hipEventDestroy(d.ev_ice[k]);
+        if (d.ev_ice_t[k]) (void)hipEventDestroy(d.ev_ice_t[k]);
+        d.ev_ice_t[k] = nullptr;
+        d.pin_ice[k] = nullptr;
+        d.ev_ice[k] = nullptr;
         if (d.pin_in[k]) (void)hipHostFree(d.pin_in[k]);
         if (d.pin_out[k]) (void)hipHostFree(d.pin_out[k]);
         if (d.ev_in[k]) (void)hipEventDestroy(d.ev_in[k]);
@@ -809,8 +831,9 @@ void stream_release(sb_ctx *c) {
         d.pin_in[k] = d.pin_out[k] = nullptr;
         d.ev_in[k] = d.ev_out[k] = nullptr;
     }
-    d.pin_in_cap = d.pin_out_cap = 0;
+    d.pin_in_cap = d.pin_out_cap = d.pin_ice_cap = 0;
     d.active = false;
+    d.ice_ready = false;
     delete d.pool;
     d.pool = nullptr;
 }
@@ -859,6 +882,7 @@ int stream_begin(sb_ctx *c, int nlons, int nlats, const T *z, const T *sd, const
     d.steps = 0;
     d.host_copy_s = d.enqueue_s = d.wait_s = 0.0;
     d.active = true;
+    d.ice_ready = false;                    // a moving coast is asked for per stream (sb_diag_stream_coast)
     return SB_OK;
 }
 
@@ -1128,6 +1152,135 @@ int get_dist_host(sb_ctx *c, int nx, int ny, const T *coast, const T *mask, cons
     if (rc) return rc;
     s.back(cdist, dcd, n);
     return s.finish();
+}
+
+// ---- a stream whose coast moves with the sea ice (sb_diag_stream_coast_*, sb_diag_stream_ice_*) ----
+// The reference's driver forms get_edges(lsm, ci[ts]) and get_dist(coast, lsm, ...) at every timestep (ref:
+// python_wrapper/seabreezediag/__init__.py:222-245).  Here the stream keeps lsm, the coast as a bit plane and cdist on the
+// device; an ice call stages the plane through pinned memory like a step's planes and enqueues the update on the
+// context's stream, in order between the steps: k_edge_bits_delta and the distance kernel over the marked tiles
+// (sb_ice_plan.hpp says which path, and what a changed word reaches).  k_scan of the next step compares the band planes
+// with what the step before left, so the stored plans and windows follow the rewritten cdist by themselves.
+template <typename T>
+int stream_coast(sb_ctx *c, const T *lsm, const T *lon, const T *lat, T maxdist, int incremental) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    DiagStream &d = c->ds;
+    if (!d.active || d.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_diag_stream_coast without a matching sb_diag_stream_begin");
+    if (d.steps != 0 || d.ice_ready) return fail(c, SB_ERR_ARG, "sb_diag_stream_coast: once, between sb_diag_stream_begin and the first step");
+    if (!lsm || !lon || !lat) return fail(c, SB_ERR_ARG, "null array pointer");
+    const int nx = d.nlons, ny = d.nlats;
+    int k = 0, rc = dist_window<T>(nx, ny, lon, lat, maxdist, &k);
+    if (rc) { c->err = g_err; return rc; }
+    if (k > SB_DIST_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "sb_diag_stream_coast: window half-width " + std::to_string(k) + " exceeds SB_DIST_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
+    const size_t b2 = (size_t)nx * ny * sizeof(T), bitbytes = (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t);
+    const size_t markbytes = ((size_t)ny * sb_ice_tiles(nx) + 3) & ~(size_t)3;
+    if ((rc = ensure(c, d.lsm, b2)) || (rc = ensure(c, d.ice, b2)) || (rc = ensure(c, d.icebits, bitbytes)) ||
+        (rc = ensure(c, d.icemarks, markbytes + 4 * sizeof(unsigned))))
+        return rc;
+    if (sb_ice_path(nx, k, incremental) == SbIcePath::WHOLE && (rc = ensure(c, d.icecoast, b2))) return rc;
+    if (d.pin_ice_cap < b2) {
+        for (int s = 0; s < 2; ++s) {
+            if (d.pin_ice[s]) (void)hipHostFree(d.pin_ice[s]);
+            d.pin_ice[s] = nullptr;
+            d.pin_ice_cap = 0;
+            HIPCHK(c, hipHostMalloc(&d.pin_ice[s], b2, hipHostMallocDefault));
+        }
+        d.pin_ice_cap = b2;
+    }
+    for (int s = 0; s < 2; ++s) {
+        if (!d.ev_ice[s]) HIPCHK(c, hipEventCreateWithFlags(&d.ev_ice[s], hipEventDisableTiming));
+        if (!d.ev_ice_t[s]) HIPCHK(c, hipEventCreate(&d.ev_ice_t[s]));
+    }
+    if ((rc = dist_tables<T>(c, nx, ny, lon, lat, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d.lsm.p, lsm, b2, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d.icebits.p, 0, bitbytes, c->stream));           // the empty coast: the first ice call differs from it
+    HIPCHK(c, hipMemsetAsync((char *)d.icemarks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                                // (lsm is the caller's pageable array)
+    d.ice_lonlat.resize(((size_t)nx + ny) * sizeof(T));
+    std::memcpy(d.ice_lonlat.data(), lon, (size_t)nx * sizeof(T));
+    std::memcpy(d.ice_lonlat.data() + (size_t)nx * sizeof(T), lat, (size_t)ny * sizeof(T));
+    d.ice_k = k; d.ice_incremental = incremental ? 1 : 0; d.ice_maxdist = (double)maxdist;
+    d.ice_mark_bytes = markbytes;
+    d.ice_calls = 0;
+    d.ice_ready = true;
+    c->radius_hint = k + 1;                 // as get_dist_dev: the distance field bounds the search radius of the steps
+    return SB_OK;
+}
+
+template <typename T>
+int stream_ice(sb_ctx *c, const T *ci) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    DiagStream &d = c->ds;
+    if (!d.active || d.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice without a matching sb_diag_stream_begin");
+    if (!d.ice_ready) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice without sb_diag_stream_coast");
+    if (!ci) return fail(c, SB_ERR_ARG, "null array pointer");
+    const int nx = d.nlons, ny = d.nlats, k = d.ice_k;
+    const size_t b2 = (size_t)nx * ny * sizeof(T);
+    const int slot = (int)(d.ice_calls & 1), first = d.ice_calls == 0 ? 1 : 0;
+    double t0 = now_s();
+    if (d.ice_calls >= 2) HIPCHK(c, hipEventSynchronize(d.ev_ice[slot]));      // the slot's upload of two ice calls ago
+    double t1 = now_s();
+    d.wait_s += t1 - t0;
+    {
+        char *pin = (char *)d.pin_ice[slot];
+        const char *src = (const char *)ci;
+        const int parts = d.pool && b2 >= ((size_t)1 << 18) ? d.pool->threads() : 1;
+        auto piece = [&](int j) {
+            const size_t a = b2 * (size_t)j / parts, b = b2 * (size_t)(j + 1) / parts;
+            std::memcpy(pin + a, src + a, b - a);
+        };
+        if (parts > 1) d.pool->run(parts, piece);
+        else piece(0);
+    }
+    double t2 = now_s();
+    d.host_copy_s += t2 - t1;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(d.ev_ice_t[0], st));
+    HIPCHK(c, hipMemcpyAsync(d.ice.p, d.pin_ice[slot], b2, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(d.ev_ice[slot], st));
+    // (the tables are keyed on the coordinates' content: another get_dist call on this context may have replaced them)
+    const T *lon = (const T *)d.ice_lonlat.data(), *lat = lon + nx;
+    int rc;
+    if ((rc = dist_tables<T>(c, nx, ny, lon, lat, st))) return rc;
+    const T *dphi = (const T *)c->vecs.p, *dlam = dphi + ny;
+    const int cuts = sb_dist_cuts(c->dist_traits, k);
+    const T maxdist = (T)d.ice_maxdist;
+    if (sb_ice_path(nx, k, d.ice_incremental) == SbIcePath::WHOLE) {
+        HIPCHK(c, sb_launch_edges<T>((const T *)d.lsm.p, (const T *)d.ice.p, (T *)d.icecoast.p, nx, ny, 0, BND_WRAPPER, st));
+        HIPCHK(c, sb_launch_dist<T>((const T *)d.icecoast.p, (const T *)d.lsm.p, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx,
+                                    (T *)d.cdist.p, nx, ny, k, maxdist, (uint64_t *)d.icebits.p, cuts, st));
+    } else {
+        unsigned char *marks = (unsigned char *)d.icemarks.p;
+        unsigned *rep = (unsigned *)(marks + d.ice_mark_bytes);
+        // the first call computes everything: every tile marked by the host; rep[0] cleared either way
+        if (first) {
+            HIPCHK(c, hipMemsetAsync(marks, 1, d.ice_mark_bytes, st));
+            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
+        } else
+            HIPCHK(c, hipMemsetAsync(marks, 0, d.ice_mark_bytes + sizeof(unsigned), st));
+        HIPCHK(c, sb_launch_edge_bits_delta<T>((const T *)d.lsm.p, (const T *)d.ice.p, (uint64_t *)d.icebits.p, marks, rep, nx, ny, k,
+                                               first, st));
+        HIPCHK(c, sb_launch_dist_dirty<T>((const T *)d.lsm.p, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, (T *)d.cdist.p, nx, ny, k,
+                                          maxdist, (const uint64_t *)d.icebits.p, cuts, marks, st));
+    }
+    HIPCHK(c, hipEventRecord(d.ev_ice_t[1], st));
+    c->radius_hint = k + 1;
+    d.ice_calls++;
+    d.enqueue_s += now_s() - t2;
+    return SB_OK;
+}
+
+template <typename T>
+int stream_get_cdist(sb_ctx *c, T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    DiagStream &d = c->ds;
+    if (!d.active || d.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_diag_stream_get_cdist without a matching sb_diag_stream_begin");
+    if (!cdist) return fail(c, SB_ERR_ARG, "null array pointer");
+    HIPCHK(c, hipMemcpyAsync(cdist, d.cdist.p, (size_t)d.nlons * d.nlats * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SB_OK;
 }
 
 // ---- the coast setup of one latitude band (sb_band_get_edges_*, sb_band_get_dist_*) ----
@@ -1553,6 +1706,41 @@ int sb_diag_stream_stats(sb_ctx *c, long *steps, double seconds[3]) {
     return SB_OK;
 }
 
+int sb_diag_stream_ice_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null report");
+    DiagStream &d = c->ds;
+    if (!d.ice_ready) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice_report without sb_diag_stream_coast");
+    const long long tiles = (long long)d.nlats * sb_ice_tiles(d.nlons);
+    rep[0] = d.ice_calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (sb_ice_path(d.nlons, d.ice_k, d.ice_incremental) == SbIcePath::WHOLE) {
+        // every call computes every tile and compares nothing
+        rep[1] = -1;
+        rep[2] = d.ice_calls ? tiles : 0;
+        return SB_OK;
+    }
+    if (d.ice_calls == 0) return SB_OK;
+    std::vector<unsigned char> host(d.ice_mark_bytes + 2 * sizeof(unsigned));
+    HIPCHK(c, hipMemcpy(host.data(), d.icemarks.p, host.size(), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
+    unsigned words[2];
+    std::memcpy(words, host.data() + d.ice_mark_bytes, sizeof(words));
+    rep[1] = words[1];
+    return SB_OK;
+}
+
+int sb_diag_stream_ice_time(sb_ctx *c, double *ms) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    DiagStream &d = c->ds;
+    if (!ms || !d.ice_ready || d.ice_calls == 0) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice_time without an ice call");
+    HIPCHK(c, hipEventSynchronize(d.ev_ice_t[1]));
+    float t = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&t, d.ev_ice_t[0], d.ev_ice_t[1]));
+    *ms = (double)t;
+    return SB_OK;
+}
+
 int sb_set_search_radius_hint(sb_ctx *c, int radius) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     if (radius < 1) return fail(c, SB_ERR_ARG, "radius must be >= 1");
@@ -1721,6 +1909,11 @@ int sb_last_counters(sb_ctx *c, long long counters[4]) {
     int sb_diag_stream_end_##SFX(sb_ctx *c, double *sb_con_last, T *output4, T *ws, T *wd, T *thc) {                \
         return stream_end<T>(c, sb_con_last, output4, ws, wd, thc);                                                 \
     }                                                                                                              \
+    int sb_diag_stream_coast_##SFX(sb_ctx *c, const T *lsm, const T *lon, const T *lat, T maxdist, int incremental) { \
+        return stream_coast<T>(c, lsm, lon, lat, maxdist, incremental);                                             \
+    }                                                                                                              \
+    int sb_diag_stream_ice_##SFX(sb_ctx *c, const T *ci) { return stream_ice<T>(c, ci); }                           \
+    int sb_diag_stream_get_cdist_##SFX(sb_ctx *c, T *cdist) { return stream_get_cdist<T>(c, cdist); }               \
     int sb_seabreeze_diag_um_##SFX(sb_ctx *c, T dt, int tn, int nx, int ny, int nz, int hs, int hl, const T *p,     \
                                    const T *u, const T *v, T *theta, const T *z, const T *sigma, const T *mask,     \
                                    T *ws, T *wd, T *thc, T *sb_con, int flags, int *error) {                        \

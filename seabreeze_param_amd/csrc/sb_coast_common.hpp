@@ -1,6 +1,7 @@
 // sb_coast_common.hpp -- what the coast setup's kernels share: sb_coast_kernels.hip (regular grids: k_edges, k_dist,
 // k_dist_bits_small, k_dist_bits, k_dist_wide) and sb_um_coast_kernels.hip (the UM layout on curvilinear grids:
-// k_edges_um, k_dist_um, k_dist_um_wide).   ref: sobel.f90:19-193, UM/vn10.7/sea_breeze_diag.F90:386-601
+// k_edges_um, k_dist_um, k_dist_um_wide) and sb_ice_kernels.hip (a stream's moving coast: k_edge_bits_delta).
+// ref: sobel.f90:19-193, UM/vn10.7/sea_breeze_diag.F90:386-601
 // The Sobel block, the coast bit plane and its bit strings, the haversine term, the two forms of the epilogue (minimum a
 // per sweep class -> distance -> sweep-time reset -> sign) and the per-target walk of a window that fits one word.
 // Every piece is stated once; the kernels keep their staging, which is what differs between them.
@@ -25,9 +26,11 @@
 #define EDGE_PITCH 264
 #define EDGE_LDS ((EDGE_ROWS + 2) * EDGE_PITCH)
 
-template <typename T, typename P>
-__device__ __forceinline__ void sb_edges_block(const T *__restrict__ lsm, const T *__restrict__ ci, T *__restrict__ coast,
-                                               unsigned char *s_land, int nx, int ny, const P p) {
+// sb_edges_each is the block without its store: emit(x, y, is_coast) is called for every cell of the block's rows inside
+// the grid, by the threads whose column is (k_edge_bits_delta ballots the flags instead of writing a plane).
+template <typename T, typename P, typename E>
+__device__ __forceinline__ void sb_edges_each(const T *__restrict__ lsm, const T *__restrict__ ci, unsigned char *s_land,
+                                              int nx, int ny, const P p, E emit) {
     const int x0 = blockIdx.x * 256, y0 = blockIdx.y * EDGE_ROWS;
     constexpr int NCELL = (EDGE_ROWS + 2) * 258, NIT = (NCELL + 255) / 256;
     T l[NIT], c[NIT];
@@ -69,8 +72,14 @@ __device__ __forceinline__ void sb_edges_block(const T *__restrict__ lsm, const 
         const int px = (m[0][2] - m[0][0]) + 2 * (m[1][2] - m[1][0]) + (m[2][2] - m[2][0]);
         const int py = (m[2][0] - m[0][0]) + 2 * (m[2][1] - m[0][1]) + (m[2][2] - m[0][2]);
         const int y = y0 + r;
-        if (y < ny) coast[p.dst(x, y)] = (px == 0 && py == 0) ? T(0) : T(1);   // sqrt(px^2+py^2) == 0
+        if (y < ny) emit(x, y, !(px == 0 && py == 0));           // sqrt(px^2+py^2) == 0
     }
+}
+
+template <typename T, typename P>
+__device__ __forceinline__ void sb_edges_block(const T *__restrict__ lsm, const T *__restrict__ ci, T *__restrict__ coast,
+                                               unsigned char *s_land, int nx, int ny, const P p) {
+    sb_edges_each(lsm, ci, s_land, nx, ny, p, [&](int x, int y, bool c) { coast[p.dst(x, y)] = c ? T(1) : T(0); });
 }
 
 // ---- the coast bit plane ----
@@ -245,16 +254,35 @@ __device__ __forceinline__ T sb_dist_finish_wave(T a_early, T a_late, T maxdist)
 //              so a cell is y * ld + x and three scalars are all the kernels carry.
 // Tiling is from column 0 with one target row per wave under either policy: a wave holds the same 64 targets in a band as
 // on the globe, which is what sb_dist_finish_wave's ballots need for equal bits.
+//   DistDirty  the whole grid of a stream whose coast moves (sb_diag_stream_ice_*): DistWhole, but a workgroup whose target
+//              rows and 256-column tile carry no mark (one byte per (row, tile), sb_ice_plan.hpp) leaves before any staging
+//              or barrier and the stored cdist of its cells stands.  skip(y0, rows, ny, tile) is asked first thing, with
+//              workgroup-uniform arguments; the other two policies answer false and their instances are what they were.
 struct DistWhole {
     __device__ __forceinline__ int t0() const { return 0; }
     __device__ __forceinline__ int t1(int ny) const { return ny; }
     __device__ __forceinline__ size_t at(int x, int y, int nx) const { return (size_t)y * nx + x; }
+    __device__ __forceinline__ bool skip(int, int, int, int) const { return false; }
 };
 struct DistBand {
     int r0, r1, ld;
     __device__ __forceinline__ int t0() const { return r0; }
     __device__ __forceinline__ int t1(int) const { return r1; }
     __device__ __forceinline__ size_t at(int x, int y, int) const { return (size_t)y * ld + x; }
+    __device__ __forceinline__ bool skip(int, int, int, int) const { return false; }
+};
+struct DistDirty {
+    const unsigned char *mark;
+    int ntiles;
+    __device__ __forceinline__ int t0() const { return 0; }
+    __device__ __forceinline__ int t1(int ny) const { return ny; }
+    __device__ __forceinline__ size_t at(int x, int y, int nx) const { return (size_t)y * nx + x; }
+    __device__ __forceinline__ bool skip(int y0, int rows, int ny, int tile) const {
+        unsigned m = 0;
+        for (int r = 0; r < rows; ++r)
+            if (y0 + r < ny) m |= mark[(size_t)(y0 + r) * ntiles + tile];
+        return m == 0;
+    }
 };
 
 // ---- what the cuts rest on (SB_CUT_*, sb_dist_plan.hpp; the host sets each only where it is exact) ----

@@ -14,7 +14,8 @@
 // One latitude band of a multi-GPU run in its ghost-celled frame takes the same kernels: k_edges_band is the Sobel block
 // over the policy EdgesBand, and every distance kernel carries a target policy (DistWhole / DistBand, sb_coast_common.hpp)
 // that says which of its source rows it writes and with which pitch -- a template argument, so the whole-grid instances
-// are what they were.
+// are what they were.  DistDirty is the third policy: the whole grid of a stream whose coast moves with the sea ice, where
+// a workgroup without a mark on its rows and tile leaves at once (sb_launch_dist_dirty; sb_ice_kernels.hip, sb_ice_plan.hpp).
 // Which kernel runs, and what it may leave out, is decided in sb_dist_plan.hpp; what the kernels share with the UM
 // layout's (the Sobel block, the bit plane, the epilogues, the one-word walk, why each cut is exact) is in
 // sb_coast_common.hpp.
@@ -148,6 +149,7 @@ __global__ __launch_bounds__(256) void k_dist_bits_small(const uint64_t *__restr
                                                    T maxdist, int nearest, const G g) {
     __shared__ T s_sp2[64], s_cosp[64], s_cost;
     const int xx = blockIdx.x * 256 + threadIdx.x, yy = g.t0() + blockIdx.y;
+    if (g.skip(yy, 1, ny, (int)blockIdx.x)) return;
     const T big = SbDist<T>::big;
     // the row mask of k_dist_bits, but a wave whose reach crosses the seam keeps every row
     uint64_t rowmask;
@@ -226,6 +228,7 @@ __global__ __launch_bounds__(256 * DIST_ROWS) void k_dist_bits(const uint64_t *_
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 256 + tx;
     const int x0 = blockIdx.x * 256, y0 = g.t0() + blockIdx.y * DIST_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
+    if (g.skip(y0, DIST_ROWS, ny, (int)blockIdx.x)) return;
     const bool rowok = yy < g.t1(ny);                            // (an odd number of rows: the last workgroup's second row)
     const T big = SbDist<T>::big;
     // Which of the 2k+1 source rows hold any coast cell within reach of this wave's 64 targets?  Lane i ORs the
@@ -394,6 +397,7 @@ __global__ __launch_bounds__(256 * WIDE_ROWS) void k_dist_wide(const uint64_t *_
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 256 + tx;
     const int x0 = blockIdx.x * 256, y0 = g.t0() + blockIdx.y * WIDE_ROWS;
     const int xx = x0 + tx, yy = y0 + ty;
+    if (g.skip(y0, WIDE_ROWS, ny, (int)blockIdx.x)) return;
     const bool active = xx < nx && yy < g.t1(ny);                // (every thread stays for the barriers)
     const int span = 256 + 2 * k, nws = (span + 63) >> 6;
     int c0 = (x0 - k) % nx;                                      // first column in reach, circular
@@ -579,11 +583,13 @@ hipError_t sb_launch_edges_band(const T *lsm, const T *ci, T *coast, int nx, int
 template <typename T, typename G>
 static hipError_t sb_launch_dist_g(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl,
                                    T *cdist, int nx, int ny, int nt, int ld, int k, T maxdist, uint64_t *bits, int cuts,
-                                   const G g, hipStream_t st) {
+                                   const G g, hipStream_t st, bool pack = true) {
     if (k > SB_DIST_MAX_WINDOW || !bits) return hipErrorInvalidValue;    // (the C ABI holds k <= SB_DIST_MAX_WINDOW)
     const SbDistKernel kern = sb_dist_kernel(nx, k);
     const int nw = (nx + 63) / 64, nearest = cuts & SB_CUT_NEAREST;
-    if (kern != SbDistKernel::BYTES) sb_launch_coastbits<T>(coast, bits, nx, ny, nw, ld, 0, st);
+    // (pack == false: `bits` already holds the coast's bit plane and there is no coast plane -- sb_launch_dist_dirty)
+    if (!pack && kern == SbDistKernel::BYTES) return hipErrorInvalidValue;
+    if (pack && kern != SbDistKernel::BYTES) sb_launch_coastbits<T>(coast, bits, nx, ny, nw, ld, 0, st);
     const dim3 gr((nx + 255) / 256, (nt + DIST_ROWS - 1) / DIST_ROWS), bl(256, DIST_ROWS);
     switch (kern) {
     case SbDistKernel::BYTES:
@@ -622,6 +628,16 @@ hipError_t sb_launch_dist_band(const T *coast, const T *mask, const T *phi, cons
                                          DistBand{r0, r1, ld}, st);
 }
 
+// The whole grid of a stream whose coast moves: `bits` is the stream's own bit plane, kept up to date by k_edge_bits_delta
+// (sb_ice_kernels.hip), which also left the marks; the kernel sb_launch_dist would take, one workgroup per tile as ever --
+// the clean ones leave at once.  Not for grids narrower than the window (k_dist reads a coast plane: sb_ice_plan.hpp).
+template <typename T>
+hipError_t sb_launch_dist_dirty(const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist, int nx, int ny,
+                                int k, T maxdist, const uint64_t *bits, int cuts, const unsigned char *marks, hipStream_t st) {
+    return sb_launch_dist_g<T, DistDirty>(nullptr, mask, phi, lamf, shl, chl, cdist, nx, ny, ny, nx, k, maxdist, (uint64_t *)bits, cuts,
+                                          DistDirty{marks, (nx + 255) / 256}, st, false);
+}
+
 template hipError_t sb_launch_edges<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges_band<float>(const float *, const float *, float *, int, int, int, int, int, int, hipStream_t);
@@ -634,3 +650,7 @@ template hipError_t sb_launch_dist_band<float>(const float *, const float *, con
                                                float *, int, int, int, int, int, int, float, uint64_t *, int, hipStream_t);
 template hipError_t sb_launch_dist_band<double>(const double *, const double *, const double *, const double *, const double *,
                                                 const double *, double *, int, int, int, int, int, int, double, uint64_t *, int, hipStream_t);
+template hipError_t sb_launch_dist_dirty<float>(const float *, const float *, const float *, const float *, const float *, float *, int,
+                                                int, int, float, const uint64_t *, int, const unsigned char *, hipStream_t);
+template hipError_t sb_launch_dist_dirty<double>(const double *, const double *, const double *, const double *, const double *, double *,
+                                                 int, int, int, double, const uint64_t *, int, const unsigned char *, hipStream_t);

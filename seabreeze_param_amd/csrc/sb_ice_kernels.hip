@@ -1,0 +1,74 @@
+// sb_ice_kernels.hip -- the coast of a stream whose sea ice moves (sb_diag_stream_ice_*): one kernel that turns the land
+// mask and a step's ice plane into the stream's coast bit plane and says what the difference can reach.
+//
+//   k_edge_bits_delta  the Sobel block of k_edges (sb_edges_each, sb_coast_common.hpp) with the f2py flavour's cell mapping
+//                      and land rule (rule 0, lsm + ci > 0.4: ref sobel.f90:51,60-69), but the flags are balloted into the
+//                      64-bit words of the bit plane straight away: no coast plane of T is written and read again, which
+//                      k_edges + k_coastbits pay.  A word belongs to one wave of one workgroup, so that wave reads the
+//                      stored word, and where the new one differs writes it, counts it and marks every (target row, tile)
+//                      the word can reach (sb_ice_reach, sb_ice_plan.hpp) -- the distance kernels under DistDirty then
+//                      compute those tiles again and leave the rest of the resident cdist alone.
+// Marks are stores of 1 into a byte plane the host cleared ahead of the launch: stores that race write the same value.
+// rep[0] counts the changed words of this call (cleared with the marks); the wave that counts the first one adds one
+// to rep[1], the calls whose coast differed, unless the call is the stream's first (`first`: everything is marked by the
+// host and the stored plane is the empty one).
+#include "../../include/seabreeze_hip.h"
+#include "sb_device.hpp"
+#include "sb_launch.hpp"
+#include "sb_coast_common.hpp"
+#include "sb_ice_plan.hpp"
+
+template <typename T>
+struct EdgesIce {
+    static constexpr bool tail_by_index = false;
+    Geo g;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X, Y;
+        sb_map_cell(g, x, y, X, Y);
+        return (size_t)Y * g.nx + X;
+    }
+    __device__ __forceinline__ int land(T l, T c) const { return (l + c > T(0.4)) ? 1 : 0; }     // ref: sobel.f90:51,69
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_edge_bits_delta(const T *__restrict__ lsm, const T *__restrict__ ci,
+                                                         uint64_t *__restrict__ bits, unsigned char *__restrict__ marks,
+                                                         unsigned *__restrict__ rep, Geo g, int k, int first) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    const int nx = g.nx, ny = g.ny, nw = (nx + 63) >> 6, nt = sb_ice_tiles(nx);
+    const int lane = threadIdx.x & 63;
+    sb_edges_each(lsm, ci, s_land, nx, ny, EdgesIce<T>{g}, [&](int x, int y, bool c) {
+        // (lanes past nx have left: they add no bit, and the wave's first lane is in whenever any of them is)
+        const uint64_t w = __ballot(c);
+        uint64_t *word = bits + (size_t)y * nw + (x >> 6);
+        const uint64_t old = *word;                              // one address per wave
+        if (old == w) return;                                    // wave-uniform
+        const SbIceReach r = sb_ice_reach(nx, ny, k, x & ~63, y);
+        const int nact = nx - (x & ~63) < 64 ? nx - (x & ~63) : 64;  // lanes still here: fewer than 64 in the ragged last word
+        for (int yt = r.r0 + lane; yt <= r.r1; yt += nact) {
+            unsigned char *row = marks + (size_t)yt * nt;
+            for (int t = r.a0; t <= r.a1; ++t) row[t] = 1;
+            for (int t = r.b0; t <= r.b1; ++t) row[t] = 1;
+        }
+        if (lane == 0) {
+            *word = w;
+            if (atomicAdd(rep, 1u) == 0u && !first) atomicAdd(rep + 1, 1u);
+        }
+    });
+}
+
+template <typename T>
+hipError_t sb_launch_edge_bits_delta(const T *lsm, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx, int ny,
+                                     int k, int first, hipStream_t st) {
+    Geo g;
+    g.nx = nx; g.ny = ny; g.h = 0; g.nxh = nx; g.nyh = ny; g.nw = (nx + 63) / 64; g.bnd = BND_WRAPPER; g.rows = ny;
+    g.band = 0;
+    hipLaunchKernelGGL(k_edge_bits_delta<T>, dim3((nx + 255) / 256, (ny + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lsm, ci, bits,
+                       marks, rep, g, k, first);
+    return hipGetLastError();
+}
+
+template hipError_t sb_launch_edge_bits_delta<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int, int, int,
+                                                     int, hipStream_t);
+template hipError_t sb_launch_edge_bits_delta<double>(const double *, const double *, uint64_t *, unsigned char *, unsigned *, int, int,
+                                                      int, int, hipStream_t);

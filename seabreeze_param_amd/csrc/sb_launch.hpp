@@ -176,6 +176,18 @@ hipError_t sb_launch_dist(const T *coast, const T *mask, const T *phi, const T *
                           int cuts,                           // SB_CUT_* (sb_dist_plan.hpp); the kernel: sb_dist_kernel(nx, k)
                           hipStream_t st);
 
+// A stream whose sea ice moves (sb_diag_stream_ice_*; sb_ice_kernels.hip, sb_ice_plan.hpp): the f2py flavour's coast of
+// lsm and ci as bits, compared with and written into the stream's bit plane (ny * ceil(nx/64) words); every (row, tile) a
+// changed word can reach gets a 1 in marks (ny * ceil(nx/256) bytes, cleared by the caller); rep[0] += changed words,
+// rep[1] += 1 with the first of them unless `first` ...
+template <typename T>
+hipError_t sb_launch_edge_bits_delta(const T *lsm, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx, int ny,
+                                     int k, int first, hipStream_t st);
+// ... and sb_launch_dist's kernel over that bit plane, computing the marked tiles of cdist alone
+template <typename T>
+hipError_t sb_launch_dist_dirty(const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist, int nx, int ny,
+                                int k, T maxdist, const uint64_t *bits, int cuts, const unsigned char *marks, hipStream_t st);
+
 // One latitude band in the band step's frame (pitch nx + 2h, interior at (h, h); south / north: the band touches that
 // pole).  Edges: lsm, ci, coast are the frames; SB_BND_GLOBAL's rule, raw reads of the first ghost row at a cut side.
 template <typename T>

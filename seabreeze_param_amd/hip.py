@@ -107,6 +107,7 @@ class Context:
         if rc != 0:
             raise SeabreezeHipError(f"sb_create failed ({rc}): {self.lib.sb_last_error(None).decode()}")
         self.h = h
+        self._stream = None          # (dtype, nx, ny) of the stream begun last (stream_begin)
 
     def close(self):
         if getattr(self, "h", None):
@@ -293,6 +294,83 @@ class Context:
                 C.c_int(nps), C.c_int(nx), C.c_int(ny), _p(output))
         self._chk(rc, "sb_diag")
         return output
+
+    # ------------------------------------------------------------------ the streamed f2py flavour (sb_diag_stream_*)
+    # Planes are C-ordered (ny, nx) arrays of one working dtype (that of `z`); the stream keeps that dtype.
+    def _stream_shape(self):
+        if self._stream is None:
+            raise SeabreezeHipError("no stream: call stream_begin first")
+        return self._stream
+
+    def stream_begin(self, z, std, cdist, ws, wd, thc):
+        """z, std, cdist and the carried state go to the device and stay there until stream_end."""
+        z = np.ascontiguousarray(z)
+        dt = np.dtype(z.dtype)
+        ny, nx = z.shape
+        std, cdist, ws, wd, thc = (_host(a, dt) for a in (std, cdist, ws, wd, thc))
+        fn = getattr(self.lib, f"sb_diag_stream_begin_{_SFX[dt]}")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), _p(z), _p(std), _p(cdist), _p(ws), _p(wd), _p(thc)), "sb_diag_stream_begin")
+        self._stream = (dt, nx, ny)
+
+    def stream_step(self, tn, p, theta, v, u, sb_con_prev=None, target_plev=700.0, thresh_wind=11.0, thresh_winddir=90.0,
+                    thresh_windch=5.0, thresh_thc=0.75, target_time=6.0, maxdist=180.0, timestep=24.0):
+        """One step; sb_con of the step before lands in rows 0 .. ny-2 of sb_con_prev (float64 (ny, nx)).  Returns whether
+        it did."""
+        dt, nx, ny = self._stream_shape()
+        ct = _CT[dt]
+        p = _host(p, dt); theta = _host(theta, dt); v = _host(v, dt); u = _host(u, dt)
+        if sb_con_prev is not None and not (sb_con_prev.dtype == np.float64 and sb_con_prev.flags.c_contiguous):
+            raise ValueError("sb_con_prev must be a C-contiguous float64 array")
+        have = C.c_int(0)
+        fn = getattr(self.lib, f"sb_diag_stream_step_{_SFX[dt]}")
+        rc = fn(self.h, C.c_int(tn), _p(p), C.c_int(p.shape[0]), _p(theta), _p(v), _p(u), ct(target_plev), ct(thresh_wind),
+                ct(thresh_winddir), ct(thresh_windch), ct(thresh_thc), ct(target_time), ct(maxdist), ct(timestep),
+                _p(sb_con_prev), C.byref(have))
+        self._chk(rc, "sb_diag_stream_step")
+        return bool(have.value)
+
+    def stream_end(self):
+        """-> (output (4, ny, nx) of the last step, ws, wd, thc)."""
+        dt, nx, ny = self._stream_shape()
+        out = np.zeros((4, ny, nx), dt)
+        ws, wd, thc = (np.zeros((ny, nx), dt) for _ in range(3))
+        fn = getattr(self.lib, f"sb_diag_stream_end_{_SFX[dt]}")
+        self._chk(fn(self.h, None, _p(out), _p(ws), _p(wd), _p(thc)), "sb_diag_stream_end")
+        return out, ws, wd, thc
+
+    def stream_coast(self, lsm, lon, lat, maxdist=180.0, incremental=True, dtype=None):
+        """Opt-in, between stream_begin and the first step: the stream's coast follows the sea ice on the device
+        (include/seabreeze_hip.h: sb_diag_stream_coast).  dtype: the precision of the call (default: the stream's)."""
+        dt = np.dtype(dtype) if dtype is not None else self._stream_shape()[0]
+        lsm = _host(lsm, dt); lon = _host(lon, dt); lat = _host(lat, dt)
+        fn = getattr(self.lib, f"sb_diag_stream_coast_{_SFX[dt]}")
+        self._chk(fn(self.h, _p(lsm), _p(lon), _p(lat), _CT[dt](maxdist), C.c_int(1 if incremental else 0)), "sb_diag_stream_coast")
+
+    def stream_ice(self, ci, dtype=None):
+        """Enqueue the coast and distance update of the stream's resident cdist for this ice plane; no synchronisation."""
+        dt = np.dtype(dtype) if dtype is not None else self._stream_shape()[0]
+        ci = _host(ci, dt)
+        self._chk(getattr(self.lib, f"sb_diag_stream_ice_{_SFX[dt]}")(self.h, _p(ci)), "sb_diag_stream_ice")
+
+    def stream_ice_report(self):
+        """Ice calls of the stream / those after the first whose coast differed (-1 on the whole-grid path) / (row, tile)
+        pairs the last call marked / pairs of the grid.  Synchronises."""
+        arr = (C.c_longlong * 4)()
+        self._chk(self.lib.sb_diag_stream_ice_report(self.h, arr), "sb_diag_stream_ice_report")
+        return dict(calls=arr[0], changed_calls=arr[1], tiles_marked=arr[2], tiles=arr[3])
+
+    def stream_ice_time(self):
+        """HIP-event time [ms] of the last ice call's device work (upload, clear, kernels).  Waits for it."""
+        ms = C.c_double(0.0)
+        self._chk(self.lib.sb_diag_stream_ice_time(self.h, C.byref(ms)), "sb_diag_stream_ice_time")
+        return ms.value
+
+    def stream_get_cdist(self):
+        """The stream's resident distance plane (ny, nx).  Synchronises."""
+        dt, nx, ny = self._stream_shape()
+        out = np.empty((ny, nx), dt)
+        self._chk(getattr(self.lib, f"sb_diag_stream_get_cdist_{_SFX[dt]}")(self.h, _p(out)), "sb_diag_stream_get_cdist")
+        return out
 
     def sigmoid(self, ary):
         ary = np.ascontiguousarray(ary)
