@@ -126,3 +126,72 @@ def test_band_runner_single_precision_wide_windows(tmp_path):
     port = _free_port()
     mp.spawn(_worker_wide, args=(2, port, 256, 192, 3, str(tmp_path)), nprocs=2, join=True)
     assert all((tmp_path / f"ok{r}").exists() for r in range(2))
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+def test_band_step_that_fails_behind_the_fork_leaves_nothing_behind(oracles, dt):
+    """A band step whose p is null is refused by a host-side check (SB_ERR_ARG, "null array pointer") -- but only in its
+    first phase, behind the fork to the communication stream and the exchange of theta's ghost rows.  What a band step
+    means to the diag code underneath (the gathered moments, Geo::band, where k_scan leaves the band's moments) must not
+    outlive it: a plain SB_BND_HALO call and a correct band step on the same context give, bit for bit, what they give on
+    a fresh context.  (The plain call's ghost cells of theta are NOT the wrap of its interior, so a Geo::band left behind
+    would show; so would gathered moments left in place.)"""
+    from seabreeze_param_amd import hip, synth
+    nx, ny, nz, h = 96, 72, 5, 16
+    f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    orc = oracles[8]
+    st = synth.static_fields(nx, ny, dt)
+    coast = orc.get_edges(f8(st.landfrac), f8(st.icefrac))
+    cd = orc.get_dist(coast, f8(st.landfrac), st.lon, st.lat, maxdist=20000.0, kwin=h - 1)
+    cd = np.where(np.abs(cd) < 12000.0, np.sign(cd) * np.minimum(np.abs(cd), 179.0), cd).astype(dt)
+    tdt = torch.float64 if dt == np.float64 else torch.float32
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda()
+    pd = dev(synth.pressure_3d(st, nz, dt))
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run(fail_first):
+        ctx = hip.Context(0)
+        try:
+            ctx.set_search_radius_hint(h)
+
+            def frame(a, ghosts=0.0):
+                f = torch.zeros((ny + 2 * h, nx + 2 * h), dtype=tdt, device="cuda")
+                f[h:h + ny, h:h + nx] = dev(a)
+                torch.cuda.synchronize()        # (torch's default stream and the context's own do not order each other)
+                ctx.swap_bounds_dev(dt, f.data_ptr(), nx, ny, h, stream)
+                torch.cuda.synchronize()
+                f += ghosts
+                f[h:h + ny, h:h + nx] = dev(a)
+                torch.cuda.synchronize()
+                return f
+
+            z, sg, mk = frame(st.z), frame(st.sigma), frame(cd)
+            outs = []
+            for tn, call in ((1, "null p"), (1, "plain"), (2, "band")):
+                if call == "null p" and not fail_first:
+                    continue
+                u, v = synth.wind_step(st, nz, tn, dt)
+                ud, vd = dev(u), dev(v)
+                thf = frame(synth.theta_step(st, tn, dt), ghosts=0.75 if call == "plain" else 0.0)
+                state = [torch.zeros((ny, nx), dtype=tdt, device="cuda") for _ in range(4)]
+                rest = (ud.data_ptr(), vd.data_ptr(), thf.data_ptr(), mk.data_ptr(), z.data_ptr(), sg.data_ptr(),
+                        *[s.data_ptr() for s in state], stream)
+                torch.cuda.synchronize()        # (the inputs and the zeroed state have landed before the context's stream reads them)
+                if call == "null p":
+                    with pytest.raises(hip.SeabreezeHipError, match=r"\(1\): null array pointer"):
+                        ctx.band_seabreeze_diag_dev(dt, 5400.0, tn, nx, ny, nz, h, None, *rest)
+                elif call == "plain":
+                    ctx.seabreeze_diag_dev(dt, 5400.0, tn, nx, ny, nz, h, hip.SB_BND_HALO, pd.data_ptr(), *rest)
+                else:
+                    ctx.band_seabreeze_diag_dev(dt, 5400.0, tn, nx, ny, nz, h, pd.data_ptr(), *rest)
+                torch.cuda.synchronize()
+                if call != "null p":
+                    outs += [s.cpu().numpy() for s in state] + [thf.cpu().numpy()]
+            return outs
+        finally:
+            ctx.close()
+
+    fresh, after = run(False), run(True)
+    assert np.count_nonzero(fresh[2]) > 0 and np.count_nonzero(fresh[7]) > 0      # (thc of both calls: band cells exist)
+    for k, (a, b) in enumerate(zip(fresh, after)):
+        assert np.array_equal(a, b, equal_nan=True), f"array {k} differs after the refused band step"

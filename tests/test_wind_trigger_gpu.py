@@ -171,7 +171,7 @@ def test_level_choice_generic(hipctx, oracles, prec, dt, nz):
 @pytest.mark.parametrize("prec,dt", PRECS, ids=["f64", "f32"])
 def test_level_choice_f2py_1d(hipctx, oracles, prec, dt, nz):
     """The Python surface's 1-D p, each pattern in a call of its own.  One level serves the whole grid; the host-pointer
-    entry point picks it on the host (diag_host in sb_capi.hip, the same strict first-minimum loop) and uploads that
+    entry point picks it on the host (pick_level in sb_ctx.hpp, the same strict first-minimum loop) and uploads that
     level's u / v planes only, so this pins the host loop; k_wind's own 1-D loop runs only for device-pointer callers
     with more than one level, which the Python binding does not expose."""
     nx, ny = 66, 3
