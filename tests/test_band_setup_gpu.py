@@ -22,10 +22,10 @@ import numpy as np
 import pytest
 
 from seabreeze_param_amd import hip, synth
+from band_frames import SENTINEL, band_dist, cuts_of, frame, frame_lat, interior, only_interior_written
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -777.0
 TOL = {8: 1e-12, 4: 2e-6}
 
 #        id              nx  kwin halo  band heights        kernel
@@ -67,38 +67,6 @@ def land_ice(nx, ny, dt, seed=8, level=2.3):
     return np.ascontiguousarray(land, dt), np.ascontiguousarray(ice, dt)
 
 
-def cuts_of(heights):
-    r = np.concatenate(([0], np.cumsum(heights)))
-    return [(int(r[i]), int(r[i + 1])) for i in range(len(heights))]
-
-
-def frame(full, r0, r1, h, fill=np.nan):
-    """Rows r0 .. r1-1 of `full` in a frame of h ghost cells: the cut-side ghost rows are the neighbour's rows, everything
-    else outside the interior is `fill`."""
-    ny, nx = full.shape
-    f = np.full((r1 - r0 + 2 * h, nx + 2 * h), fill, dtype=full.dtype)
-    lo, hi = max(r0 - h, 0), min(r1 + h, ny)
-    f[h - (r0 - lo):h + (hi - r0), h:h + nx] = full[lo:hi]
-    return f
-
-
-def frame_lat(lat, r0, r1, h):
-    f = np.full(r1 - r0 + 2 * h, np.nan, dtype=lat.dtype)
-    lo, hi = max(r0 - h, 0), min(r1 + h, lat.size)
-    f[h - (r0 - lo):h + (hi - r0)] = lat[lo:hi]
-    return f
-
-
-def interior(f, h):
-    return f[h:f.shape[0] - h, h:f.shape[1] - h] if h else f
-
-
-def only_interior_written(f, h):
-    g = f.copy()
-    interior(g, h)[...] = SENTINEL
-    return np.all(g == SENTINEL)
-
-
 def band_edges(ctx, land, ice, bands, h, rule):
     ny = land.shape[0]
     rows = []
@@ -106,18 +74,6 @@ def band_edges(ctx, land, ice, bands, h, rule):
         out = np.full((r1 - r0 + 2 * h, land.shape[1] + 2 * h), SENTINEL, dtype=land.dtype)
         ctx.band_get_edges(frame(land, r0, r1, h), frame(ice, r0, r1, h), h, r0 == 0, r1 == ny, rule=rule, out=out)
         assert only_interior_written(out, h), f"band {r0}:{r1}: ghost cells of coast were written"
-        rows.append(interior(out, h).copy())
-    return np.concatenate(rows)
-
-
-def band_dist(ctx, coast, land, lon, lat, bands, h, kwin, maxdist=180.0):
-    ny = land.shape[0]
-    rows = []
-    for r0, r1 in bands:
-        out = np.full((r1 - r0 + 2 * h, land.shape[1] + 2 * h), SENTINEL, dtype=land.dtype)
-        ctx.band_get_dist(frame(coast, r0, r1, h), frame(land, r0, r1, h), lon, frame_lat(lat, r0, r1, h), h,
-                          r0 == 0, r1 == ny, kwin, maxdist=maxdist, out=out)
-        assert only_interior_written(out, h), f"band {r0}:{r1}: ghost cells of cdist were written"
         rows.append(interior(out, h).copy())
     return np.concatenate(rows)
 
