@@ -43,6 +43,7 @@ module sea_breeze_diag_mod
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
   public :: get_edges_um, get_dist_um, get_dist_um_win
   public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
+  public :: band_coast_open, band_ice_dev, band_ice_report, band_coast_close
   public :: search_radius, band_search_radius
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
@@ -63,6 +64,8 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f64"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f64_dev"
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f64_dev"
+#define SB_BAND_COAST_OPEN    "sb_band_coast_open_f64"
+#define SB_BAND_ICE_DEV       "sb_band_ice_f64_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f64"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f64"
 #else
@@ -82,6 +85,8 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f32"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f32_dev"
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f32_dev"
+#define SB_BAND_COAST_OPEN    "sb_band_coast_open_f32"
+#define SB_BAND_ICE_DEV       "sb_band_ice_f32_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f32"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f32"
 #endif
@@ -219,6 +224,27 @@ module sea_breeze_diag_mod
       integer(c_int), value :: nx, ny, halo, south, north, kwin
       real(rk), value :: maxdist
       real(rk), intent(in) :: lon(*), lat(*)
+    end function
+    integer(c_int) function c_band_coast_open(ctx, nx, ny, halo, south, north, lon, lat, maxdist, kwin, rule, incremental) &
+        bind(C, name=SB_BAND_COAST_OPEN)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, halo, south, north, kwin, rule, incremental
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: lon(*), lat(*)
+    end function
+    integer(c_int) function c_band_ice_dev(ctx, lsm, ci, cdist, stream) bind(C, name=SB_BAND_ICE_DEV)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, lsm, ci, cdist, stream
+    end function
+    integer(c_int) function c_band_ice_report(ctx, rep) bind(C, name="sb_band_ice_report")
+      import :: c_ptr, c_int, c_long_long
+      type(c_ptr), value :: ctx
+      integer(c_long_long), intent(inout) :: rep(4)
+    end function
+    integer(c_int) function c_band_coast_close(ctx) bind(C, name="sb_band_coast_close")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
     end function
     integer(c_int) function c_search_radius(ctx, nx, ny, halo, bnd, mask, maxdist, radius, summary, hist, nhist) &
         bind(C, name=SB_SEARCH_RADIUS)
@@ -591,6 +617,56 @@ contains
                              real(maxdist, rk), k, cdist, c_null_ptr)
     if (rc /= 0) call fail('band_get_dist_dev', rc)
   end subroutine band_get_dist_dev
+
+  ! A band whose coast moves with the sea ice (include/seabreeze_hip.h: sb_band_coast_open): open once per land mask --
+  ! lon (nx) and lat (ny + 2*halo_size, one per frame row) are host arrays and are copied; a cut side needs
+  ! kwin + 1 <= halo_size -- then band_ice_dev per ice plane: landfrac, icefrac and cdist are device frames in the band
+  ! step's layout, and the call only enqueues on the context's stream.  What the caller exchanges per plane: the ghost rows
+  ! of icefrac before the call, the ghost cells of cdist after it; no coast travels.
+  subroutine band_coast_open(lon, lat, maxdist, halo_size, south, north, kwin, rule, incremental)
+    real, intent(in), contiguous :: lon(:), lat(:)
+    real, intent(in) :: maxdist
+    integer, intent(in) :: halo_size, kwin
+    logical, intent(in) :: south, north
+    integer, intent(in), optional :: rule
+    logical, intent(in), optional :: incremental
+    integer(c_int) :: rc, r, inc
+    r = 1_c_int
+    if (present(rule)) r = int(rule, c_int)
+    inc = 1_c_int
+    if (present(incremental)) inc = merge(1_c_int, 0_c_int, incremental)
+    call ensure_ctx()
+    rc = c_band_coast_open(ctx, int(size(lon), c_int), int(size(lat) - 2*halo_size, c_int), int(halo_size, c_int), &
+                           merge(1_c_int, 0_c_int, south), merge(1_c_int, 0_c_int, north), lon, lat, real(maxdist, rk), &
+                           int(kwin, c_int), r, inc)
+    if (rc /= 0) call fail('band_coast_open', rc)
+  end subroutine band_coast_open
+
+  subroutine band_ice_dev(landfrac, icefrac, cdist)
+    type(c_ptr), intent(in) :: landfrac, icefrac, cdist
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_band_ice_dev(ctx, landfrac, icefrac, cdist, c_null_ptr)
+    if (rc /= 0) call fail('band_ice_dev', rc)
+  end subroutine band_ice_dev
+
+  ! (synchronises) calls since the open / those after the first whose coast differed (-1: every call computes the whole
+  ! band) / (own row, tile) pairs the last call marked / pairs of the band
+  subroutine band_ice_report(rep)
+    integer(c_long_long), intent(out) :: rep(4)
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rep = 0
+    rc = c_band_ice_report(ctx, rep)
+    if (rc /= 0) call fail('band_ice_report', rc)
+  end subroutine band_ice_report
+
+  subroutine band_coast_close()
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_band_coast_close(ctx)
+    if (rc /= 0) call fail('band_coast_close', rc)
+  end subroutine band_coast_close
 
   !---------------------------------------------------------------------------
   ! The UM copy's get_edges(mask, icefrac, landfrac) (ref: UM/vn10.7/sea_breeze_diag.F90:328-446) in its argument

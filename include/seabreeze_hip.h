@@ -636,6 +636,66 @@ int sb_band_get_dist_f32_dev(sb_ctx *ctx, int nx, int ny, int halo, int south, i
                          float maxdist, int kwin, float *cdist, void *stream);
 
 /* -------------------------------------------------------------------------------- */
+/* A band whose coast moves with the sea ice -- the coast distance of one latitude    */
+/* band, kept up to date on the device without any exchange of coast                  */
+/* Where the sea ice moves, a coupled run needs the band's cdist again at every       */
+/* timestep.  sb_band_get_edges_* + sb_band_get_dist_* cost four ghost exchanges      */
+/* (lsm, ci, coast, cdist) and the whole band.  Here the band keeps its coast as a    */
+/* bit plane over its SOURCE rows (its own and kwin ghost rows on each cut side) and  */
+/* forms the bits of the ghost source rows itself from kwin + 1 ghost rows of lsm and */
+/* ci -- integer logic on land flags: exactly what the neighbour would have sent.  An */
+/* ice call compares the new coast with the stored one in 64-cell words and computes  */
+/* again only the (own row, 256-column tile) pairs a changed word can reach.  Per     */
+/* timestep: one exchange going in (ci's ghost rows), one going out (cdist's).        */
+/*                                                                                    */
+/* sb_band_coast_open_*: geometry as sb_band_get_dist_*; lon (nx) and lat (ny+2*halo, */
+/* one per frame row; entries beyond a pole are never read) are HOST pointers and are */
+/* copied.  Allocates the context's band planes and may synchronise.  rule: the land  */
+/* rule of sb_get_edges_* (0 or 1); the boundary is SB_BND_GLOBAL's.  incremental = 0:*/
+/* every ice call computes the whole band (also taken where the grid is narrower than */
+/* the window, 2*kwin + 1 > nx, kwin < 32).  SB_ERR_ARG: sb_band_get_dist's refusals  */
+/* (kwin < 0, kwin > SB_DIST_MAX_WINDOW, bad sizes, NULL), kwin + 1 > halo with a cut */
+/* side (the Sobel of the kwin-th ghost row reads the next one), rule outside 0..1,   */
+/* already open.  south and north both set with halo = 0 is the whole grid of a       */
+/* single-GPU host model.                                                             */
+/*                                                                                    */
+/* sb_band_ice_*_dev: lsm, ci, cdist are DEVICE frames in the band step's layout, in  */
+/* the precision the coast was opened with (else SB_ERR_ARG; NULL, not open: same).   */
+/* lsm and ci are read on the source rows and one row beyond them on cut sides; lsm   */
+/* also gives the sign, read in the interior only.  Only the interior of cdist is     */
+/* written: all of it by the first call, the marked tiles by later ones.  Enqueues on */
+/* `stream` (NULL: the context's own) a clear of the marks, the delta kernel and the  */
+/* distance kernel; no synchronisation, no download, no host compare (but: another    */
+/* get_dist call on the context in between replaces the coordinate tables, and the    */
+/* next ice call uploads them again).  Sets the search-radius hint to kwin + 1.       */
+/* The caller's side of the contract:                                                 */
+/*   * the content of lsm stands between calls (a changed lsm: close and reopen);     */
+/*   * the interior of cdist is left alone between calls;                             */
+/*   * every cut-side ghost row of lsm and ci is a real row of the globe, filled by   */
+/*     sb_swap_bounds_* or the caller's exchange (no band thinner than halo);         */
+/*   * the ghost cells of cdist are the caller's swap_bounds, as ever.                */
+/* Result: after every call the interior of cdist equals, bit for bit,                */
+/* sb_band_get_edges_* followed by sb_band_get_dist_*(kwin) of the same inputs -- by  */
+/* their contract the rows of the whole-grid calls.  A band step after an ice call    */
+/* needs nothing new: it finds the changed planes by content.                         */
+/*                                                                                    */
+/* sb_band_ice_report (synchronises the device): [0] ice calls since the open [1]     */
+/* those after the first whose coast differed (-1 on the whole path) [2] (own row,    */
+/* tile) pairs the last call marked (the first call: all) [3] pairs of the band.      */
+/* sb_band_coast_close (synchronises the device) frees the planes.                    */
+/* -------------------------------------------------------------------------------- */
+int sb_band_coast_open_f64(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                           const double *lon, const double *lat, double maxdist, int kwin, int rule,
+                           int incremental);
+int sb_band_coast_open_f32(sb_ctx *ctx, int nx, int ny, int halo, int south, int north,
+                           const float *lon, const float *lat, float maxdist, int kwin, int rule,
+                           int incremental);
+int sb_band_ice_f64_dev(sb_ctx *ctx, const double *lsm, const double *ci, double *cdist, void *stream);
+int sb_band_ice_f32_dev(sb_ctx *ctx, const float *lsm, const float *ci, float *cdist, void *stream);
+int sb_band_ice_report(sb_ctx *ctx, long long rep[4]);
+int sb_band_coast_close(sb_ctx *ctx);
+
+/* -------------------------------------------------------------------------------- */
 /* search_radius -- every band cell's window radius, from mask alone                  */
 /* no counterpart in the reference: the radius is the final nn of its expanding       */
 /*           window, ref: generic/sea_breeze_diag.f90:188-214                         */

@@ -180,19 +180,28 @@ class BandRunner:
                 exchange_ns(loc, self.nyl, self.h, self.rank, self.world, self.dist, self.torch)
                 fill_ew_ghosts(loc, self.nx, self.h)
 
-    def setup_mask(self, lsm, ci, lon, lat, rule: int, kwin: int, maxdist: float = 180.0):
+    def setup_mask(self, lsm, ci, lon, lat, rule: int, kwin: int, maxdist: float = 180.0, follow_ice: bool = False,
+                   incremental: bool = True):
         """The signed coast distance of this band from this rank's rows alone -- get_edges(rule, SB_BND_GLOBAL) and
         get_dist(kwin) of the whole grid, bit for bit, without any rank holding or computing the globe: framed lsm and
         ci, their ghost rows from the band neighbours, the band edges call, coast's ghost rows, the band distance call,
         the result's ghost cells; kept as self.mask for `step` (upload_static may then be called without a mask).
         lsm, ci: the full (ny, nx) fields (only rows r0:r1 are touched) or this band's rows (r1-r0, nx); lon (nx) and lat
-        (ny) are the global vectors.  kwin <= halo: the half-width of the window, e.g. hip.dist_window(lon, lat)."""
+        (ny) are the global vectors.  kwin <= halo: the half-width of the window, e.g. hip.dist_window(lon, lat).
+        follow_ice=True (opt-in): the sea ice moves -- the framed lsm and ci stay on the device beside the mask, the band's
+        moving coast is opened on the context (sb_band_coast_open: kwin + 1 <= halo on more than one rank) and its first ice
+        call takes the place of the edges - exchange - distance chain: no coast is exchanged.  update_ice(ci) then follows
+        every later ice plane with two exchanges (ci in, the mask's ghost cells out) and the changed tiles alone;
+        incremental=False computes the whole band in every update.  Calling it again reopens the coast (a new lsm)."""
         t, h, nx, nyl = self.torch, self.h, self.nx, self.nyl
         lon, lat = np.asarray(lon, dtype=self.dtype), np.asarray(lat, dtype=self.dtype)
         if lon.shape != (nx,) or lat.shape != (self.ny,):
             raise ValueError("lon and lat are the global vectors: nx and ny entries")
         if kwin < 0 or (self.world > 1 and kwin > h):
             raise ValueError(f"kwin = {kwin} must lie in 0 .. halo = {h}: the window reads kwin ghost rows")
+        if follow_ice and self.world > 1 and kwin + 1 > h:
+            raise ValueError(f"follow_ice: kwin + 1 = {kwin + 1} must not exceed halo = {h}: the Sobel of the kwin-th ghost row "
+                             "reads the next one")
         mine = lambda a: a if a.shape == (nyl, nx) else a[self.r0:self.r1]
         lsm_f, ci_f = (self._halo_rows(mine(np.asarray(a))) for a in (lsm, ci))
         coast_f, mask_f = t.zeros_like(lsm_f), t.zeros_like(lsm_f)
@@ -210,7 +219,18 @@ class BandRunner:
         for a in (lsm_f, ci_f):
             self._fill_ghosts(a)
         hand_over()
-        if self.world == 1:
+        if getattr(self, "_ice", None) is not None:               # (a coast followed before: a new lsm needs a reopen)
+            self.ctx.band_coast_close()
+            self._ice = None
+        if follow_ice:
+            # one rank: the band is the globe, south and north both set, no ghost cells
+            self.ctx.band_coast_open(self.dtype, nx, nyl, h, south, north, lon, latf if self.world > 1 else lat, kwin, rule=rule,
+                                     maxdist=maxdist, incremental=incremental)
+            self._ice = (lsm_f, ci_f)
+            self.ctx.band_ice_dev(self.dtype, lsm_f.data_ptr(), ci_f.data_ptr(), mask_f.data_ptr(), stream=stream)
+            hand_over()
+            self._fill_ghosts(mask_f)
+        elif self.world == 1:
             self.ctx.get_edges_dev(self.dtype, nx, nyl, lsm_f.data_ptr(), ci_f.data_ptr(), coast_f.data_ptr(), rule=rule,
                                    bnd=_hip.SB_BND_GLOBAL, stream=stream)
             self.ctx.get_dist_dev(self.dtype, nx, nyl, coast_f.data_ptr(), lsm_f.data_ptr(), lon, lat, mask_f.data_ptr(),
@@ -226,6 +246,33 @@ class BandRunner:
             hand_over()
             self._fill_ghosts(mask_f)
         self.mask = mask_f
+        self.synchronize()
+        return self.mask
+
+    def update_ice(self, ci):
+        """After setup_mask(follow_ice=True): self.mask follows this ice plane.  ci: the full (ny, nx) field (only rows
+        r0:r1 are touched) or this band's rows.  This band's rows go into the resident frame, its ghost rows come from the
+        band neighbours (one exchange), the ice call computes the tiles of self.mask the changed coast can reach, and the
+        mask's ghost cells are filled (one exchange).  No frame is allocated; self.mask keeps its address, so the stored
+        plans of the following steps notice the change by content."""
+        if getattr(self, "_ice", None) is None:
+            raise ValueError("update_ice needs setup_mask(..., follow_ice=True) first")
+        t, h, nx, nyl = self.torch, self.h, self.nx, self.nyl
+        lsm_f, ci_f = self._ice
+        a = np.asarray(ci)
+        rows = a if a.shape == (nyl, nx) else a[self.r0:self.r1]
+        ci_f[h:h + nyl, h:h + nx].copy_(t.from_numpy(np.ascontiguousarray(rows, dtype=self.dtype)))
+
+        def hand_over():                                         # as in setup_mask
+            if not (self.world > 1 and self.comm == "native"):
+                self.ctx.synchronize()
+                t.cuda.synchronize()
+
+        self._fill_ghosts(ci_f)
+        hand_over()
+        self.ctx.band_ice_dev(self.dtype, lsm_f.data_ptr(), ci_f.data_ptr(), self.mask.data_ptr(), stream=self._stream())
+        hand_over()
+        self._fill_ghosts(self.mask)
         self.synchronize()
         return self.mask
 

@@ -1,6 +1,7 @@
 // sb_capi_coast.hip -- the coast setup of the C ABI: get_edges and get_dist on the whole grid, on one latitude band and in
-// the UM layout, and search_radius.
+// the UM layout, a band's coast that moves with the sea ice, and search_radius.
 #include "sb_ctx.hpp"
+#include "sb_ice_plan.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -254,6 +255,98 @@ int band_get_dist_host(sb_ctx *c, int nx, int ny, int halo, int south, int north
     return s.finish();
 }
 
+// ---- a band whose coast moves with the sea ice (sb_band_coast_open_*, sb_band_ice_*_dev) ----
+// setup_mask's chain -- ghost rows of lsm and ci, band edges, ghost rows of coast, band distance -- per timestep costs four
+// exchanges and the whole band again.  Here the band keeps its coast as a bit plane over its SOURCE rows and forms the
+// bits of the ghost source rows itself from k+1 ghost rows of lsm and ci (integer logic on land flags: exactly what the
+// neighbour would have sent), so an ice call is a clear of the marks, k_edge_bits_delta_band and the band's distance
+// kernel over the marked tiles (sb_ice_plan.hpp says which path, and what a changed word reaches); nothing is exchanged
+// here, nothing waits.  k_scan of the next band step compares the band planes with what the step before left, so the
+// stored plans and windows follow the rewritten cdist by themselves.
+template <typename T>
+int band_coast_open(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lon, const T *lat, T maxdist, int kwin,
+                    int rule, int incremental) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (c->bc.open) return fail(c, SB_ERR_ARG, "sb_band_coast_open: already open (sb_band_coast_close first)");
+    if (nx < 1 || ny < 1 || halo < 0 || !lon || !lat) return fail(c, SB_ERR_ARG, "bad band_coast_open arguments");
+    if (rule < 0 || rule > 1) return fail(c, SB_ERR_ARG, "unknown mask rule");
+    if (kwin < 0)
+        return fail(c, SB_ERR_ARG, "band_coast_open: kwin must be given (the derived half-width needs the global latitudes: "
+                                   "sb_dist_window_* on those)");
+    if (kwin > SB_DIST_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "band_coast_open: window half-width " + std::to_string(kwin) + " exceeds SB_DIST_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_MAX_WINDOW) + " cells");
+    const SbBandIcePlan pl = sb_band_ice_plan(nx, ny, halo, south != 0, north != 0, kwin, incremental);
+    if (!pl.ok)
+        return fail(c, SB_ERR_ARG, "band_coast_open: a cut side needs kwin + 1 <= halo (the Sobel of the kwin-th ghost row reads "
+                                   "the next one), got kwin = " + std::to_string(kwin) + ", halo = " + std::to_string(halo));
+    BandCoast &b = c->bc;
+    const int nys = pl.rows.nys, ld = nx + 2 * halo;
+    const size_t bitbytes = (size_t)nys * pl.nw * sizeof(uint64_t);
+    const size_t markbytes = ((size_t)ny * pl.ntiles + 3) & ~(size_t)3;
+    int rc;
+    if ((rc = ensure(c, b.bits, bitbytes)) || (rc = ensure(c, b.marks, markbytes + 4 * sizeof(unsigned)))) return rc;
+    if (pl.path == SbIcePath::WHOLE && (rc = ensure(c, b.coast, (size_t)nys * ld * sizeof(T)))) return rc;
+    b.lonlat.resize(((size_t)nx + nys) * sizeof(T));
+    std::memcpy(b.lonlat.data(), lon, (size_t)nx * sizeof(T));
+    std::memcpy(b.lonlat.data() + (size_t)nx * sizeof(T), lat + pl.rows.f0, (size_t)nys * sizeof(T));   // (nothing beyond a pole)
+    // the tables of these coordinates now, so that the first ice call finds them and only enqueues
+    if ((rc = dist_tables<T>(c, nx, nys, (const T *)b.lonlat.data(), (const T *)b.lonlat.data() + nx, c->stream))) return rc;
+    HIPCHK(c, hipMemsetAsync(b.bits.p, 0, bitbytes, c->stream));              // the empty coast: the first ice call differs from it
+    HIPCHK(c, hipMemsetAsync((char *)b.marks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->dist_upload_stream == c->stream) c->dist_upload_stream = nullptr;   // (they have landed)
+    b.esz = (int)sizeof(T);
+    b.nx = nx; b.ny = ny; b.halo = halo; b.south = south ? 1 : 0; b.north = north ? 1 : 0;
+    b.k = kwin; b.rule = rule; b.incremental = incremental ? 1 : 0; b.maxdist = (double)maxdist;
+    b.mark_bytes = markbytes;
+    b.calls = 0;
+    b.open = true;
+    return SB_OK;
+}
+
+template <typename T>
+int band_ice_dev(sb_ctx *c, const T *lsm, const T *ci, T *cdist, void *stream) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    BandCoast &b = c->bc;
+    if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_ice without sb_band_coast_open");
+    if (b.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_band_ice: the band coast was opened in the other precision");
+    if (!lsm || !ci || !cdist) return fail(c, SB_ERR_ARG, "null array pointer");
+    const int nx = b.nx, k = b.k, ld = nx + 2 * b.halo, first = b.calls == 0 ? 1 : 0;
+    const SbBandIcePlan pl = sb_band_ice_plan(nx, b.ny, b.halo, b.south != 0, b.north != 0, k, b.incremental);
+    const SbBandRows br = pl.rows;
+    hipStream_t st = stream_of(c, stream);
+    // (the tables are keyed on the coordinates' content: another get_dist call on this context may have replaced them)
+    const T *lon = (const T *)b.lonlat.data(), *lat = lon + nx;
+    int rc;
+    if ((rc = dist_tables<T>(c, nx, br.nys, lon, lat, st))) return rc;
+    const T *dphi = (const T *)c->vecs.p, *dlam = dphi + br.nys;
+    const int cuts = sb_dist_cuts(c->dist_traits, k);
+    const T maxdist = (T)b.maxdist;
+    const size_t o = (size_t)br.f0 * ld + b.halo;                // (column 0, source row 0) of a frame
+    if (pl.path == SbIcePath::WHOLE) {
+        HIPCHK(c, sb_launch_edges_band_src<T>(lsm, ci, (T *)b.coast.p, nx, b.halo, br, b.south, b.north, b.rule, k, st));
+        HIPCHK(c, sb_launch_dist_band<T>((const T *)b.coast.p, lsm + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx,
+                                         br.nys, br.r0, br.r1, ld, k, maxdist, (uint64_t *)b.bits.p, cuts, st));
+    } else {
+        unsigned char *marks = (unsigned char *)b.marks.p;
+        unsigned *rep = (unsigned *)(marks + b.mark_bytes);
+        // the first call computes everything: every tile marked by the host; rep[0] cleared either way
+        if (first) {
+            HIPCHK(c, hipMemsetAsync(marks, 1, b.mark_bytes, st));
+            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
+        } else
+            HIPCHK(c, hipMemsetAsync(marks, 0, b.mark_bytes + sizeof(unsigned), st));
+        HIPCHK(c, sb_launch_edge_bits_delta_band<T>(lsm, ci, (uint64_t *)b.bits.p, marks, rep, nx, b.halo, br, b.south, b.north,
+                                                    b.rule, k, first, st));
+        HIPCHK(c, sb_launch_dist_band_dirty<T>(lsm + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx, br.nys, br.r0,
+                                               br.r1, ld, k, maxdist, (const uint64_t *)b.bits.p, cuts, marks, st));
+    }
+    c->radius_hint = k + 1;
+    b.calls++;
+    return SB_OK;
+}
+
 // ---- search_radius: every band cell's window radius from mask alone (sb_radius_kernels.hip) ----
 // band < 0: the whole-grid form under rule bnd; else the band step's frame (SB_BND_HALO) with GEO_BAND_* = band.
 template <typename T>
@@ -428,6 +521,43 @@ int sb_set_search_radius_hint(sb_ctx *c, int radius) {
     return SB_OK;
 }
 
+int sb_band_ice_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null report");
+    BandCoast &b = c->bc;
+    if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_ice_report without sb_band_coast_open");
+    const long long tiles = (long long)b.ny * sb_ice_tiles(b.nx);
+    rep[0] = b.calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
+    HIPCHK(c, hipDeviceSynchronize());                           // (the ice calls ran on whichever stream the caller named)
+    if (sb_ice_path(b.nx, b.k, b.incremental) == SbIcePath::WHOLE) {
+        // every call computes every tile and compares nothing
+        rep[1] = -1;
+        rep[2] = b.calls ? tiles : 0;
+        return SB_OK;
+    }
+    if (b.calls == 0) return SB_OK;
+    std::vector<unsigned char> host(b.mark_bytes + 2 * sizeof(unsigned));
+    HIPCHK(c, hipMemcpy(host.data(), b.marks.p, host.size(), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
+    unsigned words[2];
+    std::memcpy(words, host.data() + b.mark_bytes, sizeof(words));
+    rep[1] = words[1];
+    return SB_OK;
+}
+
+int sb_band_coast_close(sb_ctx *c) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    BandCoast &b = c->bc;
+    if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_coast_close without sb_band_coast_open");
+    HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
+    for (DevBuf *d : {&b.bits, &b.marks, &b.coast})
+        if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    b.lonlat.clear();
+    b.open = false;
+    b.calls = 0;
+    return SB_OK;
+}
+
 #define SB_DEFINE(T, SFX)                                                                                          \
     int sb_get_edges_##SFX(sb_ctx *c, int nx, int ny, const T *lsm, const T *ci, int rule, int bnd, T *coast) {     \
         return get_edges_host<T>(c, nx, ny, lsm, ci, rule, bnd, coast);                                             \
@@ -461,6 +591,13 @@ int sb_set_search_radius_hint(sb_ctx *c, int radius) {
                                      void *stream) {                                                                \
         return band_get_dist_dev<T>(c, nx, ny, halo, south, north, coast, mask, lon, lat, maxdist, kwin, cdist,     \
                                     stream);                                                                        \
+    }                                                                                                              \
+    int sb_band_coast_open_##SFX(sb_ctx *c, int nx, int ny, int halo, int south, int north, const T *lon,           \
+                                 const T *lat, T maxdist, int kwin, int rule, int incremental) {                    \
+        return band_coast_open<T>(c, nx, ny, halo, south, north, lon, lat, maxdist, kwin, rule, incremental);       \
+    }                                                                                                              \
+    int sb_band_ice_##SFX##_dev(sb_ctx *c, const T *lsm, const T *ci, T *cdist, void *stream) {                     \
+        return band_ice_dev<T>(c, lsm, ci, cdist, stream);                                                          \
     }                                                                                                              \
     int sb_search_radius_##SFX(sb_ctx *c, int nx, int ny, int halo, int bnd, const T *mask, T maxdist, int *radius,\
                                long long *summary, long long *hist, int nhist) {                                   \

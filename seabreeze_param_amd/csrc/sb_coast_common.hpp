@@ -7,6 +7,7 @@
 // Every piece is stated once; the kernels keep their staging, which is what differs between them.
 #pragma once
 #include <stdint.h>
+#include "sb_device.hpp"
 #include "sb_dist_plan.hpp"
 
 // ---- the Sobel of a 256-column x EDGE_ROWS-row block ----
@@ -81,6 +82,49 @@ __device__ __forceinline__ void sb_edges_block(const T *__restrict__ lsm, const 
                                                unsigned char *s_land, int nx, int ny, const P p) {
     sb_edges_each(lsm, ci, s_land, nx, ny, p, [&](int x, int y, bool c) { coast[p.dst(x, y)] = c ? T(1) : T(0); });
 }
+
+// k_edges' layout: the boundary mapping of sb_map_cell (cyclic longitudes with the f2py flavour's column quirk, clamped
+// latitudes; ref: sobel.f90:60-66, generic :340-352) and either flavour's land rule
+template <typename T>
+struct EdgesGrid {
+    static constexpr bool tail_by_index = false;
+    Geo g;
+    int rule;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X, Y;
+        sb_map_cell(g, x, y, X, Y);
+        return (size_t)Y * g.nx + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)y * g.nx + x; }
+    __device__ __forceinline__ int land(T l, T c) const {
+        if (rule == 0) return (l + c > T(0.4)) ? 1 : 0;            // ref: sobel.f90:51,69
+        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;             // ref: generic :325-330
+        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: generic :332-336
+    }
+};
+
+// The SOURCE rows of one latitude band in its ghost-celled frame (sb_band_ice_*: pitch ld = nx + 2h, interior at (h, h);
+// source row y is frame row f0 + y, sb_band_rows): EdgesBand's rule -- SB_BND_GLOBAL seen from a band -- for the rows a
+// distance window may find a coast cell in, the band's own and the k ghost rows on each cut side, so that a rank forms
+// the coast bits of its ghost source rows itself instead of receiving them.  Longitude is cyclic by index arithmetic (the
+// east-west ghost columns are never read); at a pole side (lo = 0 / hi = nys-1) the row clamps to the band's edge row and
+// no ghost row is read; at a cut side (lo = -1 / hi = nys) the one frame row beyond the source rows is read, the (k+1)-th
+// ghost row: the host holds k + 1 <= h there, so it lies inside the frame.  Rows further out are staged only for the
+// unwritten rows of a ragged block and are held at that row.  dst: the whole path's scratch coast, which starts at
+// (column 0, source row 0) with the frame's pitch (what sb_launch_dist_band is handed).
+template <typename T>
+struct EdgesBandSrc {
+    static constexpr bool tail_by_index = false;
+    int nx, nys, h, ld, f0, lo, hi, rule;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X = x % nx;
+        X = X < 0 ? X + nx : X;
+        const int Y = y < lo ? lo : (y > hi ? hi : y);
+        return (size_t)(f0 + Y) * ld + h + X;                    // (f0 + lo >= 0: f0 >= 1 wherever lo == -1)
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)y * ld + x; }
+    __device__ __forceinline__ int land(T l, T c) const { return EdgesGrid<T>{Geo{}, rule}.land(l, c); }
+};
 
 // ---- the coast bit plane ----
 // coast > 0 of an nx x ny field with row pitch ld whose first cell is at off0 (a regular grid: nx, 0; the interior of a
@@ -258,6 +302,8 @@ __device__ __forceinline__ T sb_dist_finish_wave(T a_early, T a_late, T maxdist)
 //              rows and 256-column tile carry no mark (one byte per (row, tile), sb_ice_plan.hpp) leaves before any staging
 //              or barrier and the stored cdist of its cells stands.  skip(y0, rows, ny, tile) is asked first thing, with
 //              workgroup-uniform arguments; the other two policies answer false and their instances are what they were.
+//   DistBandDirty  a band whose coast moves (sb_band_ice_*): DistBand's targets and pitch, DistDirty's early exit -- the marks
+//              are one byte per (OWN row, tile), so a target row y is row y - r0 of the plane.
 struct DistWhole {
     __device__ __forceinline__ int t0() const { return 0; }
     __device__ __forceinline__ int t1(int ny) const { return ny; }
@@ -281,6 +327,20 @@ struct DistDirty {
         unsigned m = 0;
         for (int r = 0; r < rows; ++r)
             if (y0 + r < ny) m |= mark[(size_t)(y0 + r) * ntiles + tile];
+        return m == 0;
+    }
+};
+struct DistBandDirty {
+    int r0, r1, ld;
+    const unsigned char *mark;
+    int ntiles;
+    __device__ __forceinline__ int t0() const { return r0; }
+    __device__ __forceinline__ int t1(int) const { return r1; }
+    __device__ __forceinline__ size_t at(int x, int y, int) const { return (size_t)y * ld + x; }
+    __device__ __forceinline__ bool skip(int y0, int rows, int, int tile) const {
+        unsigned m = 0;
+        for (int r = 0; r < rows; ++r)
+            if (y0 + r < r1) m |= mark[(size_t)(y0 + r - r0) * ntiles + tile];
         return m == 0;
     }
 };

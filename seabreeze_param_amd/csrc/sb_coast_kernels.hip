@@ -15,7 +15,8 @@
 // over the policy EdgesBand, and every distance kernel carries a target policy (DistWhole / DistBand, sb_coast_common.hpp)
 // that says which of its source rows it writes and with which pitch -- a template argument, so the whole-grid instances
 // are what they were.  DistDirty is the third policy: the whole grid of a stream whose coast moves with the sea ice, where
-// a workgroup without a mark on its rows and tile leaves at once (sb_launch_dist_dirty; sb_ice_kernels.hip, sb_ice_plan.hpp).
+// a workgroup without a mark on its rows and tile leaves at once (sb_launch_dist_dirty; sb_ice_kernels.hip, sb_ice_plan.hpp);
+// DistBandDirty the fourth: the same for one band (sb_launch_dist_band_dirty, sb_band_ice_*).
 // Which kernel runs, and what it may leave out, is decided in sb_dist_plan.hpp; what the kernels share with the UM
 // layout's (the Sobel block, the bit plane, the epilogues, the one-word walk, why each cut is exact) is in
 // sb_coast_common.hpp.
@@ -24,25 +25,8 @@
 #include "sb_launch.hpp"
 #include "sb_coast_common.hpp"
 
-// k_edges' layout: the boundary mapping of sb_map_cell (cyclic longitudes with the f2py flavour's column quirk, clamped
-// latitudes; ref: sobel.f90:60-66, generic :340-352) and either flavour's land rule
-template <typename T>
-struct EdgesGrid {
-    static constexpr bool tail_by_index = false;
-    Geo g;
-    int rule;
-    __device__ __forceinline__ size_t src(int x, int y) const {
-        int X, Y;
-        sb_map_cell(g, x, y, X, Y);
-        return (size_t)Y * g.nx + X;
-    }
-    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)y * g.nx + x; }
-    __device__ __forceinline__ int land(T l, T c) const {
-        if (rule == 0) return (l + c > T(0.4)) ? 1 : 0;            // ref: sobel.f90:51,69
-        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;             // ref: generic :325-330
-        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: generic :332-336
-    }
-};
+// (EdgesGrid, k_edges' layout and either flavour's land rule: sb_coast_common.hpp -- the band's moving coast takes its
+// land rule from there too)
 
 // One latitude band of the global grid in its ghost-celled frame (the band step's layout: pitch nx + 2h, interior at
 // (h, h)): EdgesGrid's SB_BND_GLOBAL rule seen from a band.  Longitude is cyclic by index arithmetic (the east-west ghost
@@ -638,6 +622,18 @@ hipError_t sb_launch_dist_dirty(const T *mask, const T *phi, const T *lamf, cons
                                           DistDirty{marks, (nx + 255) / 256}, st, false);
 }
 
+// One latitude band whose coast moves (sb_band_ice_*): sb_launch_dist_band's arguments without a coast plane -- `bits` is
+// the band's own bit plane over its nys source rows, kept up to date by k_edge_bits_delta_band, which also left the marks
+// (one byte per (own row, tile)).  The kernel sb_launch_dist_band would take; not k_dist (sb_ice_plan.hpp).
+template <typename T>
+hipError_t sb_launch_dist_band_dirty(const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist, int nx,
+                                     int nys, int r0, int r1, int ld, int k, T maxdist, const uint64_t *bits, int cuts,
+                                     const unsigned char *marks, hipStream_t st) {
+    if (r0 < 0 || r1 > nys || r1 <= r0 || ld < nx || !marks) return hipErrorInvalidValue;
+    return sb_launch_dist_g<T, DistBandDirty>(nullptr, mask, phi, lamf, shl, chl, cdist, nx, nys, r1 - r0, ld, k, maxdist,
+                                              (uint64_t *)bits, cuts, DistBandDirty{r0, r1, ld, marks, (nx + 255) / 256}, st, false);
+}
+
 template hipError_t sb_launch_edges<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges_band<float>(const float *, const float *, float *, int, int, int, int, int, int, hipStream_t);
@@ -654,3 +650,9 @@ template hipError_t sb_launch_dist_dirty<float>(const float *, const float *, co
                                                 int, int, float, const uint64_t *, int, const unsigned char *, hipStream_t);
 template hipError_t sb_launch_dist_dirty<double>(const double *, const double *, const double *, const double *, const double *, double *,
                                                  int, int, int, double, const uint64_t *, int, const unsigned char *, hipStream_t);
+template hipError_t sb_launch_dist_band_dirty<float>(const float *, const float *, const float *, const float *, const float *,
+                                                     float *, int, int, int, int, int, int, float, const uint64_t *, int,
+                                                     const unsigned char *, hipStream_t);
+template hipError_t sb_launch_dist_band_dirty<double>(const double *, const double *, const double *, const double *, const double *,
+                                                      double *, int, int, int, int, int, int, double, const uint64_t *, int,
+                                                      const unsigned char *, hipStream_t);

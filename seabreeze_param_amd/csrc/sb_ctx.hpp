@@ -58,6 +58,20 @@ struct DiagStream {
     long long ice_calls = 0;
 };
 
+// A band whose coast moves with the sea ice (sb_band_coast_open / sb_band_ice_*_dev): the geometry it was opened for, the
+// band's own coast bit plane over its source rows (the context's `coastbits` is scratch of other get_dist calls),
+// [marks | rep] and, on the whole path, a coast plane over the source rows; lon and the source rows' latitudes, with
+// which every ice call keys the coordinate tables.
+struct BandCoast {
+    bool open = false;
+    int esz = 0, nx = 0, ny = 0, halo = 0, south = 0, north = 0, k = 0, rule = 0, incremental = 1;
+    double maxdist = 0.0;
+    DevBuf bits, marks, coast;
+    size_t mark_bytes = 0;                     // bytes of the mark plane, rounded up to a word; rep follows
+    std::vector<unsigned char> lonlat;         // lon(nx) | lat(nys)
+    long long calls = 0;
+};
+
 struct sb_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -143,6 +157,7 @@ struct sb_ctx {
     void *comm = nullptr;
     int rank = 0, nranks = 1;
     DiagStream ds;
+    BandCoast bc;
 };
 
 // What a band step means to the diag code underneath travels as an argument: band_diag_dev builds one value per phase,

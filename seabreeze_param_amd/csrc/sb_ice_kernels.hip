@@ -8,6 +8,10 @@
 //                      stored word, and where the new one differs writes it, counts it and marks every (target row, tile)
 //                      the word can reach (sb_ice_reach, sb_ice_plan.hpp) -- the distance kernels under DistDirty then
 //                      compute those tiles again and leave the rest of the resident cdist alone.
+//   k_edge_bits_delta_band  the same for one latitude band in its ghost-celled frame (sb_band_ice_*): the Sobel over the band's
+//                      SOURCE rows (EdgesBandSrc: either land rule, SB_BND_GLOBAL seen from a band), the band's reach
+//                      (sb_band_ice_reach), DistBandDirty behind it; k_edges_band_src writes the same coast as a plane
+//                      for the whole path.
 // Marks are stores of 1 into a byte plane the host cleared ahead of the launch: stores that race write the same value.
 // rep[0] counts the changed words of this call (cleared with the marks); the wave that counts the first one adds one
 // to rep[1], the calls whose coast differed, unless the call is the stream's first (`first`: everything is marked by the
@@ -67,6 +71,78 @@ hipError_t sb_launch_edge_bits_delta(const T *lsm, const T *ci, uint64_t *bits, 
                        marks, rep, g, k, first);
     return hipGetLastError();
 }
+
+// ---- one latitude band (sb_band_ice_*) ----
+// k_edge_bits_delta over the band's SOURCE rows (EdgesBandSrc, sb_coast_common.hpp): the ballot, the compare against the
+// stored word, the store, the count and the marks are the whole grid's statement for statement -- change both together --
+// with the band's reach (sb_band_ice_reach: the targets are the own rows only) and a mark plane that starts at the band's
+// first own row.  Ghost source rows are compared and stored like own rows.  lsm, ci: the frame's first cell.
+template <typename T>
+__global__ __launch_bounds__(256) void k_edge_bits_delta_band(const T *__restrict__ lsm, const T *__restrict__ ci,
+                                                              uint64_t *__restrict__ bits, unsigned char *__restrict__ marks,
+                                                              unsigned *__restrict__ rep, EdgesBandSrc<T> p, int r0, int r1, int k,
+                                                              int first) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    const int nx = p.nx, nw = (nx + 63) >> 6, nt = sb_ice_tiles(nx);
+    const int lane = threadIdx.x & 63;
+    sb_edges_each(lsm, ci, s_land, nx, p.nys, p, [&](int x, int y, bool c) {
+        const uint64_t w = __ballot(c);
+        uint64_t *word = bits + (size_t)y * nw + (x >> 6);
+        const uint64_t old = *word;                              // one address per wave
+        if (old == w) return;                                    // wave-uniform
+        const SbIceReach r = sb_band_ice_reach(nx, r0, r1, k, x & ~63, y);
+        const int nact = nx - (x & ~63) < 64 ? nx - (x & ~63) : 64;  // lanes still here: fewer than 64 in the ragged last word
+        for (int yt = r.r0 + lane; yt <= r.r1; yt += nact) {
+            unsigned char *row = marks + (size_t)(yt - r0) * nt;
+            for (int t = r.a0; t <= r.a1; ++t) row[t] = 1;
+            for (int t = r.b0; t <= r.b1; ++t) row[t] = 1;
+        }
+        if (lane == 0) {
+            *word = w;
+            if (atomicAdd(rep, 1u) == 0u && !first) atomicAdd(rep + 1, 1u);
+        }
+    });
+}
+
+// the whole path: the same Sobel policy writes a coast plane over the source rows (scratch of the frame's pitch)
+template <typename T>
+__global__ __launch_bounds__(256) void k_edges_band_src(const T *__restrict__ lsm, const T *__restrict__ ci,
+                                                        T *__restrict__ coast, EdgesBandSrc<T> p) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    sb_edges_block(lsm, ci, coast, s_land, p.nx, p.nys, p);
+}
+
+template <typename T>
+static EdgesBandSrc<T> band_src_policy(int nx, int h, const SbBandRows &br, int south, int north, int rule) {
+    return EdgesBandSrc<T>{nx, br.nys, h, nx + 2 * h, br.f0, south ? 0 : -1, north ? br.nys - 1 : br.nys, rule};
+}
+
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_band(const T *lsm, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                          int h, SbBandRows br, int south, int north, int rule, int k, int first, hipStream_t st) {
+    if ((!south || !north) && k + 1 > h) return hipErrorInvalidValue;        // (the (k+1)-th ghost row lies inside the frame)
+    hipLaunchKernelGGL(k_edge_bits_delta_band<T>, dim3((nx + 255) / 256, (br.nys + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lsm,
+                       ci, bits, marks, rep, band_src_policy<T>(nx, h, br, south, north, rule), br.r0, br.r1, k, first);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t sb_launch_edges_band_src(const T *lsm, const T *ci, T *coast, int nx, int h, SbBandRows br, int south, int north,
+                                    int rule, int k, hipStream_t st) {
+    if ((!south || !north) && k + 1 > h) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_edges_band_src<T>, dim3((nx + 255) / 256, (br.nys + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lsm, ci,
+                       coast, band_src_policy<T>(nx, h, br, south, north, rule));
+    return hipGetLastError();
+}
+
+template hipError_t sb_launch_edge_bits_delta_band<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int,
+                                                          int, SbBandRows, int, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edge_bits_delta_band<double>(const double *, const double *, uint64_t *, unsigned char *, unsigned *,
+                                                           int, int, SbBandRows, int, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edges_band_src<float>(const float *, const float *, float *, int, int, SbBandRows, int, int, int, int,
+                                                    hipStream_t);
+template hipError_t sb_launch_edges_band_src<double>(const double *, const double *, double *, int, int, SbBandRows, int, int, int,
+                                                     int, hipStream_t);
 
 template hipError_t sb_launch_edge_bits_delta<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int, int, int,
                                                      int, hipStream_t);

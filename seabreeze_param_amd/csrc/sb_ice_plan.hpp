@@ -1,6 +1,7 @@
-// sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*) decides: which path it takes, and what a changed
-// word of the coast bit plane can reach.  sb_capi.hip asks for the path, k_edge_bits_delta (sb_ice_kernels.hip) marks with
-// the same sb_ice_reach the host-only test walks (tests/ice_plan_dump.cpp).  Plain C++17: no HIP, no heap -- a host
+// sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*) or of a latitude band (sb_band_ice_*) decides:
+// which path it takes, and what a changed word of the coast bit plane can reach.  sb_capi_stream.hip and sb_capi_coast.hip
+// ask for the path, k_edge_bits_delta[_band] (sb_ice_kernels.hip) mark with the same sb_ice_reach / sb_band_ice_reach the
+// host-only tests walk (tests/ice_plan_dump.cpp, tests/band_ice_plan_dump.cpp).  Plain C++17: no HIP, no heap -- a host
 // compiler builds it alone; under hipcc the functions are also device functions.
 //
 // The mark plane holds one byte per (target row, 256-column tile): the tiles of the distance kernels (a workgroup of
@@ -48,6 +49,24 @@ SB_ICE_HD SbIceReach sb_ice_reach(int nx, int ny, int k, int x0, int y) {
     return r;
 }
 
+// ---- one latitude band in its ghost-celled frame (sb_band_ice_*; sb_capi_coast.hip) ----
+// The bit plane covers the band's SOURCE rows 0 .. nys-1 (sb_band_rows, sb_dist_plan.hpp: the band's own rows and k ghost
+// rows on each cut side), the targets are source rows r0 .. r1-1, the mark plane holds one byte per (own row, tile): row
+// yt - r0.  The argument above holds with "rows inside the grid" read as "source rows of the band": a target (xx, yy)
+// under DistBand reads the bit plane's rows yy-k .. yy+k inside 0 .. nys-1 and nothing else of the coast (rows past a pole
+// add no sources, rows past a cut side's k-th ghost row lie beyond the window of every own row), and the columns xx-k ..
+// xx+k round the circle.  So a changed word at source row s, columns x0 .. x0+63, can move the targets of rows
+// max(s-k, r0) .. min(s+k, r1-1) -- never an empty range: r0 <= k and r1-1 >= nys-1-k -- and of sb_ice_reach's tile columns.
+// DistBand tiles from column 0 with one target row per wave, as on the globe, so a tile holds whole waves here too.
+// Ghost source rows are compared and stored like own rows: their bits are what the neighbour band holds for its own
+// rows, formed here from the k+1 ghost rows of lsm and ci (the Sobel of the k-th ghost row reads the (k+1)-th).
+// r0, r1 of the result are source rows; a0 .. b1 as in sb_ice_reach.
+SB_ICE_HD SbIceReach sb_band_ice_reach(int nx, int r0, int r1, int k, int x0, int s) {
+    SbIceReach r = sb_ice_reach(nx, r1, k, x0, s);               // rows max(s-k, 0) .. min(s+k, r1-1)
+    r.r0 = r.r0 < r0 ? r0 : r.r0;
+    return r;
+}
+
 // WHOLE: k_edges into a scratch plane and the whole-grid distance launch (sb_launch_dist), for a stream opened with
 // incremental = 0 and for grids narrower than the window, where the distance kernel is k_dist (byte probes of a coast
 // plane: it has no bit plane to compare).  DELTA: k_edge_bits_delta and the distance kernel under DistDirty.
@@ -56,4 +75,26 @@ enum class SbIcePath { WHOLE, DELTA };
 inline SbIcePath sb_ice_path(int nx, int k, int incremental) {
     if (!incremental || sb_dist_kernel(nx, k) == SbDistKernel::BYTES) return SbIcePath::WHOLE;
     return SbIcePath::DELTA;
+}
+
+// What sb_band_coast_open_* decides for a band of ny own rows with `halo` ghost cells: ok == false where a cut side lacks
+// the (k+1)-th ghost row of lsm and ci -- frame rows f0-1 and f0+nys, which the Sobel of the outermost ghost source rows
+// reads (a pole side reads nothing beyond the band's edge row, so south and north both set needs no ghost row at all);
+// else the source rows, the path (the whole grid's rule: the kernels are the same) and the sizes of the planes.
+struct SbBandIcePlan {
+    bool ok;
+    SbBandRows rows;
+    SbIcePath path;
+    int nw, ntiles;          // words per row of the bit plane (rows.nys rows), tiles per row of the mark plane (ny rows)
+};
+
+inline SbBandIcePlan sb_band_ice_plan(int nx, int ny, int halo, bool south, bool north, int k, int incremental) {
+    SbBandIcePlan p{};
+    p.ok = k >= 0 && halo >= 0 && ((south && north) || k + 1 <= halo);
+    if (!p.ok) return p;
+    p.rows = sb_band_rows(ny, halo, south, north, k);
+    p.path = sb_ice_path(nx, k, incremental);
+    p.nw = (nx + 63) / 64;
+    p.ntiles = sb_ice_tiles(nx);
+    return p;
 }

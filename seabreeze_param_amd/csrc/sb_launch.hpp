@@ -199,6 +199,24 @@ template <typename T>
 hipError_t sb_launch_dist_band(const T *coast, const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist,
                                int nx, int nys, int r0, int r1, int ld, int k, T maxdist, uint64_t *bits, int cuts, hipStream_t st);
 
+// A band whose sea ice moves (sb_band_ice_*; sb_ice_kernels.hip, sb_ice_plan.hpp).  lsm, ci: the frames (first cell); br:
+// sb_band_rows of the band and k; a cut side needs k + 1 <= h (else hipErrorInvalidValue).  The coast of the band's SOURCE
+// rows under SB_BND_GLOBAL's rule as bits, compared with and written into the band's bit plane (br.nys * ceil(nx/64)
+// words); every (own row, tile) a changed word can reach gets a 1 in marks (ny * ceil(nx/256) bytes, cleared by the
+// caller); rep as sb_launch_edge_bits_delta ...
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_band(const T *lsm, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                          int h, SbBandRows br, int south, int north, int rule, int k, int first, hipStream_t st);
+// ... or, on the whole path, as a coast plane of pitch nx + 2h that starts at (column 0, source row 0) ...
+template <typename T>
+hipError_t sb_launch_edges_band_src(const T *lsm, const T *ci, T *coast, int nx, int h, SbBandRows br, int south, int north,
+                                    int rule, int k, hipStream_t st);
+// ... and sb_launch_dist_band's kernel over that bit plane, computing the marked tiles of the band's own rows alone
+template <typename T>
+hipError_t sb_launch_dist_band_dirty(const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist, int nx,
+                                     int nys, int r0, int r1, int ld, int k, T maxdist, const uint64_t *bits, int cuts,
+                                     const unsigned char *marks, hipStream_t st);
+
 // the UM vn10.7 copy's coast setup on the tdims_l layout (sb_um_coast_kernels.hip): lf, ci, coast are
 // (nx + 2hi) x (ny + 2hj) with hi, hj >= 1; coast's interior is written, its ghost cells are not
 template <typename T>

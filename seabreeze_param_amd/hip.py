@@ -623,6 +623,34 @@ class Context:
                      _p(coast_f), _p(mask_f), _p(lon), _p(lat_f), _CT[dt](maxdist), C.c_int(kwin), _p(cdist_f),
                      C.c_void_p(stream) if stream else None), "sb_band_get_dist_dev")
 
+    def band_coast_open(self, dtype, nx, ny, halo, south, north, lon, lat_f, kwin, rule=1, maxdist=180.0, incremental=True):
+        """Open the band's moving coast (include/seabreeze_hip.h: sb_band_coast_open): lon (nx) and lat_f (ny + 2*halo,
+        one per frame row) are host vectors and are copied; a cut side needs kwin + 1 <= halo."""
+        dt = np.dtype(dtype)
+        lon = _host(lon, dt); lat_f = _host(lat_f, dt)
+        if lon.shape != (nx,) or lat_f.shape != (ny + 2 * halo,):
+            raise ValueError("lon must have nx entries, lat_f ny + 2*halo")
+        fn = getattr(self.lib, f"sb_band_coast_open_{_SFX[dt]}")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo), C.c_int(1 if south else 0), C.c_int(1 if north else 0),
+                     _p(lon), _p(lat_f), _CT[dt](maxdist), C.c_int(kwin), C.c_int(rule), C.c_int(1 if incremental else 0)),
+                  "sb_band_coast_open")
+
+    def band_ice_dev(self, dtype, lsm_f, ci_f, cdist_f, stream=None):
+        """Enqueue the coast and distance update of the band's cdist frame for this ice frame (device frames, raw
+        addresses, the precision the coast was opened with); no synchronisation."""
+        fn = getattr(self.lib, f"sb_band_ice_{_SFX[np.dtype(dtype)]}_dev")
+        self._chk(fn(self.h, _p(lsm_f), _p(ci_f), _p(cdist_f), C.c_void_p(stream) if stream else None), "sb_band_ice_dev")
+
+    def band_ice_report(self):
+        """Ice calls since the open / those after the first whose coast differed (-1 on the whole path) / (own row, tile)
+        pairs the last call marked / pairs of the band.  Synchronises."""
+        arr = (C.c_longlong * 4)()
+        self._chk(self.lib.sb_band_ice_report(self.h, arr), "sb_band_ice_report")
+        return dict(calls=arr[0], changed_calls=arr[1], tiles_marked=arr[2], tiles=arr[3])
+
+    def band_coast_close(self):
+        self._chk(self.lib.sb_band_coast_close(self.h), "sb_band_coast_close")
+
     def get_edges_um_dev(self, dtype, nx, ny, halo_i, halo_j, landfrac_l, icefrac_l, coast, stream=None):
         """UM-layout get_edges on device arrays (raw addresses); enqueues without synchronising."""
         fn = getattr(self.lib, f"sb_get_edges_um_{_SFX[np.dtype(dtype)]}_dev")
