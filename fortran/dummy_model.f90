@@ -22,6 +22,11 @@
 !                                (window +-(halo_size + 3) cells, 2-D coordinates: the broadcast of lon and lat)
 !                                -> seabreeze_diag_um; output.bin: the distance field on tdims_l (its ghost cells
 !                                the edge cells, filled here), then per step sb_con windspeed winddir thc
+!     um2dice                    um2d's sub-domain with sea ice that differs from step to step, as the UM rebuilds its mask
+!                                from icefrac inside the timestep routine: um_coast_open once, then um_ice ahead of
+!                                every seabreeze_diag_um.  Step s ices (0.6) the sea cells of the sub-domain that touch
+!                                land and whose row j has mod(j + s, 3) == 0.  output.bin: per step the distance field on
+!                                tdims_l (ghost cells the edge cells, filled here), then sb_con windspeed winddir thc
 !     host                       the reference's call shape: host arrays in, host arrays out (default)
 !     dev                        the fields live on the device (sb_dev_alloc); per step only theta, u, v go up
 !                                and the four outputs come back; seabreeze_diag_dev
@@ -71,7 +76,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | um2dice | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -116,6 +121,8 @@ program dummy_model
     call run_um()
   case ('um2d')
     call run_um2d()
+  case ('um2dice')
+    call run_um2dice()
   case ('status')
     call check_status()
   case ('bandsetup')
@@ -392,6 +399,84 @@ contains
     sb_con = 0.
     sb_con(1+hl:nx-hl, 1+hl:ny-hl) = sb_i
   end subroutine run_um2d
+
+  !---------------------------------------------------------------------------
+  ! um2d with a coast that follows the sea ice: the sub-domain, coordinates and window of run_um2d; landfrac and
+  ! icefrac on tdims_l with their ghost cells the edge cells; um_ice ahead of every step's seabreeze_diag_um -- the
+  ! first call computes the whole interior, later ones what the moved coast can reach.  The interior of cdist_l is left
+  ! alone between the calls: the diagnostic gets a copy whose ghost cells are filled by edge replication.
+  !---------------------------------------------------------------------------
+  subroutine run_um2dice()
+    use sea_breeze_diag_mod, only : um_coast_open, um_ice, um_ice_report, um_coast_close, seabreeze_diag_um
+    integer :: hs, hl, nxi, nyi, error, i, j, ii, jj
+    integer(c_long_long) :: rep(4)
+    real, allocatable :: p_i(:,:,:), u_i(:,:,:), v_i(:,:,:), th_s(:,:), z_s(:,:), sg_s(:,:)
+    real, allocatable :: ws_i(:,:), wd_i(:,:), thc_i(:,:), sb_i(:,:), lf_i(:,:), ci_i(:,:)
+    real, allocatable :: tlat(:,:), tlon(:,:), lf_l(:,:), ci_l(:,:), cdist_l(:,:), mask_l(:,:)
+    logical, allocatable :: shore(:,:)
+    hs = halo_size + 1; hl = halo_size + 3
+    nxi = nx - 2*hl; nyi = ny - 2*hl
+    if (nxi < 1 .or. nyi < 1) error stop 'um2dice mode: grid too small for the ghost frame'
+    allocate(lf_i(nxi,nyi), ci_i(nxi,nyi), tlat(nxi,nyi), tlon(nxi,nyi), shore(nxi,nyi))
+    allocate(lf_l(nxi+2*hl,nyi+2*hl), ci_l(nxi+2*hl,nyi+2*hl), cdist_l(nxi+2*hl,nyi+2*hl), mask_l(nxi+2*hl,nyi+2*hl))
+    lf_i = land_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    do j = 1, nyi
+      tlon(:, j) = lon(1+hl:nx-hl)
+    end do
+    do i = 1, nxi
+      tlat(i, :) = lat(1+hl:ny-hl)
+    end do
+    do j = 1, nyi                                ! sea cells that touch land
+      do i = 1, nxi
+        shore(i, j) = lf_i(i, j) == 0. .and. any(lf_i(max(i-1,1):min(i+1,nxi), max(j-1,1):min(j+1,nyi)) > 0.)
+      end do
+    end do
+    do jj = 1, nyi + 2*hl
+      do ii = 1, nxi + 2*hl
+        lf_l(ii, jj) = lf_i(min(max(ii - hl, 1), nxi), min(max(jj - hl, 1), nyi))
+      end do
+    end do
+    cdist_l = 0.
+    call um_coast_open(tlat, tlon, hl, hl, hl, hl)
+    allocate(p_i(nxi,nyi,nz), u_i(nxi,nyi,nz), v_i(nxi,nyi,nz))
+    allocate(th_s(nxi+2*hs,nyi+2*hs), z_s(nxi+2*hs,nyi+2*hs), sg_s(nxi+2*hs,nyi+2*hs))
+    allocate(ws_i(nxi,nyi), wd_i(nxi,nyi), thc_i(nxi,nyi), sb_i(nxi,nyi))
+    ws_i = 0.; wd_i = 0.; thc_i = 0.; sb_i = 0.
+    p_i = p(1+hl:nx-hl, 1+hl:ny-hl, :)
+    z_s = z(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+    sg_s = sigma(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+    do step = 1, nsteps
+      read (uin) theta, u, v
+      ci_i = ice_frac(1+hl:nx-hl, 1+hl:ny-hl)
+      do j = 1, nyi
+        if (mod(j + step, 3) == 0) then
+          where (shore(:, j)) ci_i(:, j) = 0.6
+        end if
+      end do
+      do jj = 1, nyi + 2*hl
+        do ii = 1, nxi + 2*hl
+          ci_l(ii, jj) = ci_i(min(max(ii - hl, 1), nxi), min(max(jj - hl, 1), nyi))
+        end do
+      end do
+      call um_ice(lf_l, ci_l, cdist_l)
+      do jj = 1, nyi + 2*hl                      ! ghost cells: the edge cells
+        do ii = 1, nxi + 2*hl
+          mask_l(ii, jj) = cdist_l(min(max(ii, 1+hl), nxi+hl), min(max(jj, 1+hl), nyi+hl))
+        end do
+      end do
+      u_i = u(1+hl:nx-hl, 1+hl:ny-hl, :)
+      v_i = v(1+hl:nx-hl, 1+hl:ny-hl, :)
+      th_s = theta(1+hl-hs:nx-hl+hs, 1+hl-hs:ny-hl+hs)
+      call seabreeze_diag_um(timestep, step, p_i, u_i, v_i, th_s, z_s, sg_s, mask_l, ws_i, wd_i, thc_i, sb_i, error)
+      if (error /= 0) error stop 'um2dice mode: seabreeze_diag_um reported an error'
+      write (uout) mask_l, sb_i, ws_i, wd_i, thc_i
+    end do
+    call um_ice_report(rep)
+    print '(a,4(1x,i0))', 'um2dice: ice report', rep
+    call um_coast_close()
+    sb_con = 0.
+    sb_con(1+hl:nx-hl, 1+hl:ny-hl) = sb_i
+  end subroutine run_um2dice
 
   !---------------------------------------------------------------------------
   ! Argument checks of the status-returning entry points: they answer error = 1 before any device work

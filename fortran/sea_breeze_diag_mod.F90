@@ -44,6 +44,7 @@ module sea_breeze_diag_mod
   public :: get_edges_um, get_dist_um, get_dist_um_win
   public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
   public :: band_coast_open, band_ice_dev, band_ice_report, band_coast_close
+  public :: um_coast_open, um_ice, um_ice_dev, um_ice_report, um_coast_close
   public :: search_radius, band_search_radius
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
@@ -66,6 +67,9 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f64_dev"
 #define SB_BAND_COAST_OPEN    "sb_band_coast_open_f64"
 #define SB_BAND_ICE_DEV       "sb_band_ice_f64_dev"
+#define SB_UM_COAST_OPEN      "sb_um_coast_open_f64"
+#define SB_UM_ICE             "sb_um_ice_f64"
+#define SB_UM_ICE_DEV         "sb_um_ice_f64_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f64"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f64"
 #else
@@ -87,11 +91,15 @@ module sea_breeze_diag_mod
 #define SB_BAND_GET_DIST_DEV  "sb_band_get_dist_f32_dev"
 #define SB_BAND_COAST_OPEN    "sb_band_coast_open_f32"
 #define SB_BAND_ICE_DEV       "sb_band_ice_f32_dev"
+#define SB_UM_COAST_OPEN      "sb_um_coast_open_f32"
+#define SB_UM_ICE             "sb_um_ice_f32"
+#define SB_UM_ICE_DEV         "sb_um_ice_f32_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f32"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f32"
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
+  integer(c_int), save :: um_shape(4) = 0     ! nx, ny, halo_i, halo_j of the open UM coast (um_coast_open)
 
   interface band_get_dist       ! (maxdist as a real or as the integer literal, like get_dist)
     module procedure band_get_dist_r
@@ -243,6 +251,33 @@ module sea_breeze_diag_mod
       integer(c_long_long), intent(inout) :: rep(4)
     end function
     integer(c_int) function c_band_coast_close(ctx) bind(C, name="sb_band_coast_close")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function c_um_coast_open(ctx, nx, ny, hi, hj, wi, wj, tlat, tlon, maxdist, incremental) &
+        bind(C, name=SB_UM_COAST_OPEN)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj, wi, wj, incremental
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: tlat(*), tlon(*)
+    end function
+    integer(c_int) function c_um_ice(ctx, lf, ci, cdist) bind(C, name=SB_UM_ICE)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      real(rk), intent(in) :: lf(*), ci(*)
+      real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_um_ice_dev(ctx, lf, ci, cdist, stream) bind(C, name=SB_UM_ICE_DEV)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, lf, ci, cdist, stream
+    end function
+    integer(c_int) function c_um_ice_report(ctx, rep) bind(C, name="sb_um_ice_report")
+      import :: c_ptr, c_int, c_long_long
+      type(c_ptr), value :: ctx
+      integer(c_long_long), intent(inout) :: rep(4)
+    end function
+    integer(c_int) function c_um_coast_close(ctx) bind(C, name="sb_um_coast_close")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
     end function
@@ -760,6 +795,78 @@ contains
     if (rc /= 0) call fail('get_dist_um_win', rc)
     deallocate(c2)
   end subroutine get_dist_um_win
+
+  !---------------------------------------------------------------------------
+  ! A UM-layout coast that moves with the sea ice (include/seabreeze_hip.h: sb_um_coast_open): the UM rebuilds its mask
+  ! from icefrac inside the timestep routine (ref: UM/vn10.7/sea_breeze_diag.F90:384-445); get_edges_um + get_dist_um_win
+  ! per step would compute the whole interior again.  Open once per landfrac -- true_latitude, true_longitude on tdims
+  ! (nx, ny), degrees, are copied; halo_i, halo_j >= 1 are the ghost widths of the tdims_l arrays of the ice calls, the
+  ! window is +-win_i x +-win_j, each 0 .. 255 -- then um_ice per ice frame: landfrac_l, icefrac_l and cdist_l on tdims_l
+  ! (nx+2*halo_i, ny+2*halo_j), the one-cell ring of the first two filled.  Only the interior of cdist_l is written, and
+  ! what a call left there must still be there at the next one (later calls compute only what the moved coast can
+  ! reach).  um_ice_dev takes device frames and only enqueues on the context's stream.
+  !---------------------------------------------------------------------------
+  subroutine um_coast_open(true_latitude, true_longitude, halo_i, halo_j, win_i, win_j, maxdist, incremental)
+    real, intent(in), contiguous :: true_latitude(:,:), true_longitude(:,:)
+    integer, intent(in) :: halo_i, halo_j, win_i, win_j
+    real, intent(in), optional :: maxdist
+    logical, intent(in), optional :: incremental
+    real :: md
+    integer(c_int) :: rc, inc
+    if (any(shape(true_longitude) /= shape(true_latitude))) &
+      call fail('um_coast_open: need true_latitude, true_longitude (nx, ny)', 1_c_int)
+    md = 180.
+    if (present(maxdist)) md = maxdist
+    inc = 1_c_int
+    if (present(incremental)) inc = merge(1_c_int, 0_c_int, incremental)
+    call ensure_ctx()
+    rc = c_um_coast_open(ctx, int(size(true_latitude, 1), c_int), int(size(true_latitude, 2), c_int), int(halo_i, c_int), &
+                         int(halo_j, c_int), int(win_i, c_int), int(win_j, c_int), true_latitude, true_longitude, &
+                         real(md, rk), inc)
+    if (rc /= 0) call fail('um_coast_open', rc)
+    um_shape = [int(size(true_latitude, 1), c_int), int(size(true_latitude, 2), c_int), int(halo_i, c_int), int(halo_j, c_int)]
+  end subroutine um_coast_open
+
+  subroutine um_ice(landfrac_l, icefrac_l, cdist_l)
+    real, intent(in), contiguous :: landfrac_l(:,:), icefrac_l(:,:)
+    real, intent(inout), contiguous :: cdist_l(:,:)
+    integer(c_int) :: rc
+    integer :: want(2)
+    want = [um_shape(1) + 2*um_shape(3), um_shape(2) + 2*um_shape(4)]
+    if (um_shape(1) < 1) call fail('um_ice without um_coast_open', 1_c_int)
+    if (any(shape(landfrac_l) /= want) .or. any(shape(icefrac_l) /= want) .or. any(shape(cdist_l) /= want)) &
+      call fail('um_ice: need landfrac_l, icefrac_l, cdist_l (nx+2*halo_i, ny+2*halo_j) of the open coast', 1_c_int)
+    call ensure_ctx()
+    rc = c_um_ice(ctx, landfrac_l, icefrac_l, cdist_l)
+    if (rc /= 0) call fail('um_ice', rc)
+  end subroutine um_ice
+
+  subroutine um_ice_dev(landfrac_l, icefrac_l, cdist_l)
+    type(c_ptr), intent(in) :: landfrac_l, icefrac_l, cdist_l
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_um_ice_dev(ctx, landfrac_l, icefrac_l, cdist_l, c_null_ptr)
+    if (rc /= 0) call fail('um_ice_dev', rc)
+  end subroutine um_ice_dev
+
+  ! (synchronises) calls since the open / those after the first whose coast differed (-1: every call computes the whole
+  ! interior) / workgroup tiles (4 rows x 64 columns) the last call marked / tiles of the grid
+  subroutine um_ice_report(rep)
+    integer(c_long_long), intent(out) :: rep(4)
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rep = 0
+    rc = c_um_ice_report(ctx, rep)
+    if (rc /= 0) call fail('um_ice_report', rc)
+  end subroutine um_ice_report
+
+  subroutine um_coast_close()
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_um_coast_close(ctx)
+    if (rc /= 0) call fail('um_coast_close', rc)
+    um_shape = 0
+  end subroutine um_coast_close
 
   !---------------------------------------------------------------------------
   ! ref: generic/sea_breeze_diag.f90:457-481

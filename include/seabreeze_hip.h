@@ -855,6 +855,77 @@ int sb_get_dist_um_win_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo
                        float maxdist, float *cdist, void *stream);
 
 /* -------------------------------------------------------------------------------- */
+/* a UM-layout coast that moves with the sea ice -- get_edges_um + get_dist_um_win,   */
+/* kept up to date on the device, incrementally                                       */
+/* The UM copy rebuilds its land mask from icefrac inside the timestep routine and    */
+/* runs get_edges and get_dist on it (ref: UM/vn10.7/sea_breeze_diag.F90:384-445): the*/
+/* coast moves with the ice at every model step.  sb_get_edges_um_* +                 */
+/* sb_get_dist_um_win_* per step cost the whole interior, whatever changed.  Here the */
+/* context keeps the interior's coast as a bit plane of its own; an ice call compares */
+/* the new coast with the stored one in 64-cell words and computes again only the     */
+/* workgroups of the distance kernels (4 rows x 64 columns) a changed word can reach  */
+/* through the window.                                                                */
+/*                                                                                    */
+/* sb_um_coast_open_*: geometry as sb_get_dist_um_win_*: landfrac_l, icefrac_l and    */
+/* cdist_l of the ice calls are (nx+2*halo_i, ny+2*halo_j) frames with the interior   */
+/* at (halo_i, halo_j); halo_i, halo_j >= 1 (the Sobel reads the one-cell ring, as in */
+/* sb_get_edges_um_*); the window is +-win_i x +-win_j, each 0 ..                     */
+/* SB_DIST_UM_MAX_WINDOW, stated apart from the ghost width.  true_lat, true_lon      */
+/* (nx, ny), degrees, are HOST pointers and are copied to the device.  Allocates the  */
+/* context's UM planes and may synchronise.  incremental = 0: every ice call computes */
+/* the whole interior with sb_get_edges_um's and sb_get_dist_um_win's kernels (for    */
+/* A/B runs, and for runs in which every tile changes).  SB_ERR_ARG: bad sizes, a     */
+/* halo below 1, a window outside 0 .. 255, NULL, already open.  The UM state is      */
+/* independent of the stream's (sb_diag_stream_coast) and the band's                  */
+/* (sb_band_coast_open_*) moving coasts: one context may hold all three.              */
+/*                                                                                    */
+/* The rule is the UM's ice-aware land rule (:390-403) and sb_get_dist_um_win_*'s     */
+/* distance rule in every respect: interior sources and targets only, no wrap, no     */
+/* clamp, both longitude corrections, the sweep-order reset, 12000 where the window   */
+/* holds no coast.  The sign comes from landfrac_l > 0, read in the interior of the   */
+/* frame (sb_get_dist_um_* takes an interior (nx, ny) landfrac: the same values, read */
+/* here through the frame's pitch and offset).                                        */
+/*                                                                                    */
+/* sb_um_ice_*_dev: landfrac_l, icefrac_l, cdist_l are DEVICE frames in the precision */
+/* the coast was opened with (else SB_ERR_ARG; NULL, not open: same).  Enqueues on    */
+/* `stream` (NULL: the context's own) one clear of [marks | changed-word counter],    */
+/* the delta kernel and the distance kernel; no synchronisation, no download, no host */
+/* compare.  Only the interior of cdist_l is written: all of it by the first call,    */
+/* the marked workgroups by later ones.  The caller's side of the contract:           */
+/*   * the content of landfrac_l stands between calls (a changed landfrac: close and  */
+/*     reopen);                                                                       */
+/*   * the interior of cdist_l is left alone between calls;                           */
+/*   * the one-cell ring of landfrac_l and icefrac_l is filled (swap_bounds);         */
+/*   * the ghost cells of cdist_l are the caller's swap_bounds, as ever.              */
+/* sb_um_ice_f64 / _f32 take HOST frames: they stage all three (cdist_l too: what the */
+/* call before left in its interior stands where nothing is marked), synchronise and  */
+/* return the interior of cdist_l; its ghost cells are untouched.                     */
+/* Result: after every call the interior of cdist_l equals, bit for bit,              */
+/* sb_get_edges_um_* followed by sb_get_dist_um_win_*(win_i, win_j) of the same       */
+/* inputs -- sb_get_dist_um_*'s field where win == halo <= 31.  A                     */
+/* sb_seabreeze_diag_um_* call after an ice call needs nothing new: it finds the      */
+/* changed band planes by content.  The coast bit plane is the context's own, not the */
+/* scratch plane other get_dist calls overwrite: any other coast call on the context  */
+/* between two ice calls leaves the next ice call exact.                              */
+/*                                                                                    */
+/* sb_um_ice_report (synchronises the device): [0] ice calls since the open [1]       */
+/* those after the first whose coast differed (-1 on the whole path) [2] workgroup    */
+/* tiles the last call marked (the first call: all) [3] tiles of the grid,            */
+/* ceil(ny/4) * ceil(nx/64).  sb_um_coast_close (synchronises the device) frees the   */
+/* planes.                                                                            */
+/* -------------------------------------------------------------------------------- */
+int sb_um_coast_open_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                         const double *true_lat, const double *true_lon, double maxdist, int incremental);
+int sb_um_coast_open_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j,
+                         const float *true_lat, const float *true_lon, float maxdist, int incremental);
+int sb_um_ice_f64_dev(sb_ctx *ctx, const double *landfrac_l, const double *icefrac_l, double *cdist_l, void *stream);
+int sb_um_ice_f32_dev(sb_ctx *ctx, const float *landfrac_l, const float *icefrac_l, float *cdist_l, void *stream);
+int sb_um_ice_f64(sb_ctx *ctx, const double *landfrac_l, const double *icefrac_l, double *cdist_l);
+int sb_um_ice_f32(sb_ctx *ctx, const float *landfrac_l, const float *icefrac_l, float *cdist_l);
+int sb_um_ice_report(sb_ctx *ctx, long long rep[4]);
+int sb_um_coast_close(sb_ctx *ctx);
+
+/* -------------------------------------------------------------------------------- */
 /* swap_bounds -- ghost-cell fill of one latitude band of a multi-GPU run            */
 /* replaces: subroutine swap_bounds(field, halo_size)                                */
 /*           ref: generic/halo_exchange_mod.f90:12-17 (an empty stub; the UM copy    */

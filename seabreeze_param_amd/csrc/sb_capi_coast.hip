@@ -1,5 +1,5 @@
 // sb_capi_coast.hip -- the coast setup of the C ABI: get_edges and get_dist on the whole grid, on one latitude band and in
-// the UM layout, a band's coast that moves with the sea ice, and search_radius.
+// the UM layout, a band's and a UM-layout coast that move with the sea ice, and search_radius.
 #include "sb_ctx.hpp"
 #include "sb_ice_plan.hpp"
 
@@ -510,6 +510,114 @@ int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, 
     return get_dist_um_win_host<T>(c, nx, ny, hi, hj, hi, hj, coast, lf, tlat, tlon, maxdist, cdist);
 }
 
+// ---- a UM-layout coast that moves with the sea ice (sb_um_coast_open_*, sb_um_ice_*) ----
+// The UM rebuilds its mask from icefrac inside the timestep routine (ref: UM/vn10.7/sea_breeze_diag.F90:384-445), so
+// get_edges_um + get_dist_um_win per timestep cost the whole interior again.  Here the context keeps the interior's coast
+// as a bit plane of its own and the coordinates on the device; an ice call is one clear of [marks | changed-word counter],
+// k_edge_bits_delta_um and the UM distance kernel over the marked workgroups (sb_ice_plan.hpp says which path, and what a
+// changed word reaches).  Nothing waits.  k_scan of the next sb_seabreeze_diag_um_* call finds the changed band planes by
+// content.
+template <typename T>
+int um_coast_open(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *tlat, const T *tlon, T maxdist,
+                  int incremental) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    UmCoast &u = c->um;
+    if (u.open) return fail(c, SB_ERR_ARG, "sb_um_coast_open: already open (sb_um_coast_close first)");
+    if (nx < 1 || ny < 1 || !tlat || !tlon) return fail(c, SB_ERR_ARG, "bad um_coast_open arguments");
+    if (hi < 1 || hj < 1) return fail(c, SB_ERR_ARG, "um_coast_open: halo_i and halo_j must be >= 1 (the Sobel reads the ghost ring)");
+    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "um_coast_open: the window +-" + std::to_string(wi) + " x +-" + std::to_string(wj) +
+                                       " needs 0 <= win_i, win_j <= SB_DIST_UM_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_UM_MAX_WINDOW) + " cells");
+    if ((double)(nx + 2.0 * hi) * (double)(ny + 2.0 * hj) > 2.0e9) return fail(c, SB_ERR_ARG, "grid too large");
+    const SbUmIcePlan pl = sb_um_ice_plan(nx, ny, hi, hj, wi, wj, incremental);
+    if (!pl.ok) return fail(c, SB_ERR_ARG, "bad um_coast_open arguments");
+    const size_t n = (size_t)nx * ny, bitbytes = (size_t)ny * pl.nw * sizeof(uint64_t);
+    const size_t markbytes = ((size_t)pl.ngroups * pl.ntiles + 3) & ~(size_t)3;
+    int rc;
+    if ((rc = ensure(c, u.coords, 2 * n * sizeof(T))) || (rc = ensure(c, u.bits, bitbytes)) ||
+        (rc = ensure(c, u.marks, markbytes + 4 * sizeof(unsigned))))
+        return rc;
+    if (pl.path == SbIcePath::WHOLE &&
+        ((rc = ensure(c, u.coast, (size_t)(nx + 2 * hi) * (ny + 2 * hj) * sizeof(T))) || (rc = ensure(c, u.lf, n * sizeof(T)))))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(u.coords.p, tlat, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync((T *)u.coords.p + n, tlon, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(u.bits.p, 0, bitbytes, c->stream));              // the empty coast: the first ice call differs from it
+    HIPCHK(c, hipMemsetAsync((char *)u.marks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                                // (the caller's coordinates may go now)
+    u.esz = (int)sizeof(T);
+    u.nx = nx; u.ny = ny; u.hi = hi; u.hj = hj; u.wi = wi; u.wj = wj;
+    u.incremental = incremental ? 1 : 0; u.maxdist = (double)maxdist;
+    u.mark_bytes = markbytes;
+    u.calls = 0;
+    u.open = true;
+    return SB_OK;
+}
+
+template <typename T>
+int check_um_ice(sb_ctx *c, const T *lf, const T *ci, const T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    const UmCoast &u = c->um;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_ice without sb_um_coast_open");
+    if (u.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_um_ice: the UM coast was opened in the other precision");
+    if (!lf || !ci || !cdist) return fail(c, SB_ERR_ARG, "null array pointer");
+    return SB_OK;
+}
+
+template <typename T>
+int um_ice_dev(sb_ctx *c, const T *lf, const T *ci, T *cdist, void *stream) {
+    int rc = check_um_ice<T>(c, lf, ci, cdist);
+    if (rc) return rc;
+    UmCoast &u = c->um;
+    const int nx = u.nx, ny = u.ny, hi = u.hi, hj = u.hj, NX = nx + 2 * hi, first = u.calls == 0 ? 1 : 0;
+    const T *tlat = (const T *)u.coords.p, *tlon = tlat + (size_t)nx * ny;
+    const T maxdist = (T)u.maxdist;
+    hipStream_t st = stream_of(c, stream);
+    if (sb_um_ice_path(u.incremental) == SbIcePath::WHOLE) {
+        // today's chain on the context's own planes; sb_launch_dist_um_win reads an interior landfrac: a copy of the frame's
+        HIPCHK(c, hipMemcpy2DAsync(u.lf.p, (size_t)nx * sizeof(T), lf + (size_t)hj * NX + hi, (size_t)NX * sizeof(T),
+                                   (size_t)nx * sizeof(T), (size_t)ny, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, sb_launch_edges_um<T>(lf, ci, (T *)u.coast.p, nx, ny, hi, hj, st));
+        HIPCHK(c, sb_launch_dist_um_win<T>((const T *)u.coast.p, (const T *)u.lf.p, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj,
+                                           maxdist, (uint64_t *)u.bits.p, st));
+    } else {
+        unsigned char *marks = (unsigned char *)u.marks.p;
+        unsigned *rep = (unsigned *)(marks + u.mark_bytes);
+        // the first call computes everything: every workgroup marked by the host; rep[0] cleared either way
+        if (first) {
+            HIPCHK(c, hipMemsetAsync(marks, 1, u.mark_bytes, st));
+            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
+        } else
+            HIPCHK(c, hipMemsetAsync(marks, 0, u.mark_bytes + sizeof(unsigned), st));
+        HIPCHK(c, sb_launch_edge_bits_delta_um<T>(lf, ci, (uint64_t *)u.bits.p, marks, rep, nx, ny, hi, hj, u.wi, u.wj, first, st));
+        HIPCHK(c, sb_launch_dist_um_dirty<T>(lf, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj, maxdist, (const uint64_t *)u.bits.p,
+                                             marks, st));
+    }
+    u.calls++;
+    return SB_OK;
+}
+
+template <typename T>
+int um_ice_host(sb_ctx *c, const T *lf, const T *ci, T *cdist) {
+    int rc = check_um_ice<T>(c, lf, ci, cdist);
+    if (rc) return rc;
+    const UmCoast &u = c->um;
+    const int NX = u.nx + 2 * u.hi;
+    const size_t nl = (size_t)NX * (u.ny + 2 * u.hj);
+    Stager s(c);
+    // (cdist in as well: later calls write the marked workgroups only, the rest of the interior is the caller's from the call before)
+    T *dl = s.in(lf, nl), *dc = s.in(ci, nl), *dcd = s.in((const T *)cdist, nl);
+    if (s.rc) return s.rc;
+    rc = um_ice_dev<T>(c, dl, dc, dcd, nullptr);
+    if (rc) return rc;
+    // the interior only: the caller's ghost cells are untouched
+    hipError_t e = hipMemcpy2DAsync(cdist + (size_t)u.hj * NX + u.hi, (size_t)NX * sizeof(T), dcd + (size_t)u.hj * NX + u.hi,
+                                    (size_t)NX * sizeof(T), (size_t)u.nx * sizeof(T), (size_t)u.ny, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) return hipfail(c, e, "hipMemcpy2DAsync D2H");
+    return s.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -555,6 +663,42 @@ int sb_band_coast_close(sb_ctx *c) {
     b.lonlat.clear();
     b.open = false;
     b.calls = 0;
+    return SB_OK;
+}
+
+int sb_um_ice_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null report");
+    UmCoast &u = c->um;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_ice_report without sb_um_coast_open");
+    const long long tiles = (long long)sb_um_ice_groups(u.ny) * sb_um_ice_tiles(u.nx);
+    rep[0] = u.calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
+    HIPCHK(c, hipDeviceSynchronize());                           // (the ice calls ran on whichever stream the caller named)
+    if (sb_um_ice_path(u.incremental) == SbIcePath::WHOLE) {
+        // every call computes every workgroup and compares nothing
+        rep[1] = -1;
+        rep[2] = u.calls ? tiles : 0;
+        return SB_OK;
+    }
+    if (u.calls == 0) return SB_OK;
+    std::vector<unsigned char> host(u.mark_bytes + 2 * sizeof(unsigned));
+    HIPCHK(c, hipMemcpy(host.data(), u.marks.p, host.size(), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
+    unsigned words[2];
+    std::memcpy(words, host.data() + u.mark_bytes, sizeof(words));
+    rep[1] = words[1];
+    return SB_OK;
+}
+
+int sb_um_coast_close(sb_ctx *c) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    UmCoast &u = c->um;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_coast_close without sb_um_coast_open");
+    HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
+    for (DevBuf *d : {&u.coords, &u.bits, &u.marks, &u.coast, &u.lf})
+        if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    u.open = false;
+    u.calls = 0;
     return SB_OK;
 }
 
@@ -642,6 +786,14 @@ int sb_band_coast_close(sb_ctx *c) {
                                        void *stream) {                                                              \
         return get_dist_um_win_dev<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, maxdist, cdist, stream);    \
     }                                                                                                              \
+    int sb_um_coast_open_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *tlat,            \
+                               const T *tlon, T maxdist, int incremental) {                                         \
+        return um_coast_open<T>(c, nx, ny, hi, hj, wi, wj, tlat, tlon, maxdist, incremental);                       \
+    }                                                                                                              \
+    int sb_um_ice_##SFX##_dev(sb_ctx *c, const T *lf, const T *ci, T *cdist, void *stream) {                        \
+        return um_ice_dev<T>(c, lf, ci, cdist, stream);                                                             \
+    }                                                                                                              \
+    int sb_um_ice_##SFX(sb_ctx *c, const T *lf, const T *ci, T *cdist) { return um_ice_host<T>(c, lf, ci, cdist); } \
     int sb_dist_window_##SFX(int nx, int ny, const T *lon, const T *lat, T maxdist, int *k) {                       \
         return dist_window<T>(nx, ny, lon, lat, maxdist, k);                                                        \
     }

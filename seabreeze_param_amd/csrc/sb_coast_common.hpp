@@ -1,6 +1,6 @@
 // sb_coast_common.hpp -- what the coast setup's kernels share: sb_coast_kernels.hip (regular grids: k_edges, k_dist,
 // k_dist_bits_small, k_dist_bits, k_dist_wide) and sb_um_coast_kernels.hip (the UM layout on curvilinear grids:
-// k_edges_um, k_dist_um, k_dist_um_wide) and sb_ice_kernels.hip (a stream's moving coast: k_edge_bits_delta).
+// k_edges_um, k_dist_um, k_dist_um_wide) and sb_ice_kernels.hip (a moving coast: k_edge_bits_delta[_band|_um]).
 // ref: sobel.f90:19-193, UM/vn10.7/sea_breeze_diag.F90:386-601
 // The Sobel block, the coast bit plane and its bit strings, the haversine term, the two forms of the epilogue (minimum a
 // per sweep class -> distance -> sweep-time reset -> sign) and the per-target walk of a window that fits one word.
@@ -124,6 +124,26 @@ struct EdgesBandSrc {
     }
     __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)y * ld + x; }
     __device__ __forceinline__ int land(T l, T c) const { return EdgesGrid<T>{Geo{}, rule}.land(l, c); }
+};
+
+// k_edges_um's layout: the interior offset by (hi, hj) inside the ghost-celled field of NX x NY cells.  The ring cells are
+// ghost cells of the caller; cells past the ring are clamped into the field (their flags are never read for a written
+// cell).
+template <typename T>
+struct EdgesUm {
+    static constexpr bool tail_by_index = true;
+    int NX, NY, hi, hj;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X = x + hi, Y = y + hj;
+        X = X < NX ? X : NX - 1;
+        Y = Y < NY ? Y : NY - 1;
+        return (size_t)Y * NX + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + hj) * NX + x + hi; }
+    __device__ __forceinline__ int land(T l, T c) const {
+        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
+        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
+    }
 };
 
 // ---- the coast bit plane ----

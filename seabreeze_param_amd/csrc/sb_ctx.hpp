@@ -72,6 +72,19 @@ struct BandCoast {
     long long calls = 0;
 };
 
+// A UM-layout coast that moves with the sea ice (sb_um_coast_open / sb_um_ice_*): the geometry it was opened for, the
+// coordinates on the device (tlat | tlon, interior fields), the context's own coast bit plane over the interior (`umbits`
+// is scratch of other get_dist_um calls), [marks | rep] with one mark byte per workgroup of the UM distance kernels, and, on
+// the whole path, a coast frame and an interior copy of landfrac.  Independent of the stream's and the band's moving coasts.
+struct UmCoast {
+    bool open = false;
+    int esz = 0, nx = 0, ny = 0, hi = 0, hj = 0, wi = 0, wj = 0, incremental = 1;
+    double maxdist = 0.0;
+    DevBuf coords, bits, marks, coast, lf;
+    size_t mark_bytes = 0;                     // bytes of the mark plane, rounded up to a word; rep follows
+    long long calls = 0;
+};
+
 struct sb_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -158,6 +171,7 @@ struct sb_ctx {
     int rank = 0, nranks = 1;
     DiagStream ds;
     BandCoast bc;
+    UmCoast um;
 };
 
 // What a band step means to the diag code underneath travels as an argument: band_diag_dev builds one value per phase,

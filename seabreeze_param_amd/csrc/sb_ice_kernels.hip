@@ -12,6 +12,8 @@
 //                      SOURCE rows (EdgesBandSrc: either land rule, SB_BND_GLOBAL seen from a band), the band's reach
 //                      (sb_band_ice_reach), DistBandDirty behind it; k_edges_band_src writes the same coast as a plane
 //                      for the whole path.
+//   k_edge_bits_delta_um    the same for the UM layout (sb_um_ice_*): EdgesUm over the interior of the tdims_l frames, the UM's
+//                      reach (sb_um_ice_reach), one mark byte per workgroup of the UM distance kernels, DistUmDirty behind it.
 // Marks are stores of 1 into a byte plane the host cleared ahead of the launch: stores that race write the same value.
 // rep[0] counts the changed words of this call (cleared with the marks); the wave that counts the first one adds one
 // to rep[1], the calls whose coast differed, unless the call is the stream's first (`first`: everything is marked by the
@@ -74,7 +76,7 @@ hipError_t sb_launch_edge_bits_delta(const T *lsm, const T *ci, uint64_t *bits, 
 
 // ---- one latitude band (sb_band_ice_*) ----
 // k_edge_bits_delta over the band's SOURCE rows (EdgesBandSrc, sb_coast_common.hpp): the ballot, the compare against the
-// stored word, the store, the count and the marks are the whole grid's statement for statement -- change both together --
+// stored word, the store, the count and the marks are the whole grid's statement for statement -- change all three together --
 // with the band's reach (sb_band_ice_reach: the targets are the own rows only) and a mark plane that starts at the band's
 // first own row.  Ghost source rows are compared and stored like own rows.  lsm, ci: the frame's first cell.
 template <typename T>
@@ -134,6 +136,55 @@ hipError_t sb_launch_edges_band_src(const T *lsm, const T *ci, T *coast, int nx,
                        coast, band_src_policy<T>(nx, h, br, south, north, rule));
     return hipGetLastError();
 }
+
+// ---- the UM layout (sb_um_ice_*) ----
+// k_edge_bits_delta over the interior of the tdims_l frames (EdgesUm, sb_coast_common.hpp: the UM's ice-aware rule on the
+// interior and the one-cell ring; 256-column blocks from interior column 0, so a 64-cell word belongs to one wave): the
+// ballot, the compare against the stored word, the store, the count and the marks are the whole grid's statement for
+// statement -- change all three together -- with the UM's reach (sb_um_ice_reach: no wrap, one piece) and a mark plane of
+// one byte per workgroup of the UM distance kernels (row group x 64-column tile), DistUmDirty behind it.  EdgesUm keeps
+// tail_by_index: that only says how lanes past the ring are staged; lanes whose column is past nx still leave
+// sb_edges_each before emit, so here too the wave's first lane is in whenever any of them is.  lf, ci: the frame's first
+// cell.  k_edges_um writes the same coast as a plane for the whole path.
+template <typename T>
+__global__ __launch_bounds__(256) void k_edge_bits_delta_um(const T *__restrict__ lf, const T *__restrict__ ci,
+                                                            uint64_t *__restrict__ bits, unsigned char *__restrict__ marks,
+                                                            unsigned *__restrict__ rep, int nx, int ny, int hi, int hj, int wi,
+                                                            int wj, int first) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    const int nw = (nx + 63) >> 6, nt = sb_um_ice_tiles(nx);
+    const int lane = threadIdx.x & 63;
+    sb_edges_each(lf, ci, s_land, nx, ny, EdgesUm<T>{nx + 2 * hi, ny + 2 * hj, hi, hj}, [&](int x, int y, bool c) {
+        const uint64_t w = __ballot(c);
+        uint64_t *word = bits + (size_t)y * nw + (x >> 6);
+        const uint64_t old = *word;                              // one address per wave
+        if (old == w) return;                                    // wave-uniform
+        const SbUmIceReach r = sb_um_ice_reach(nx, ny, wi, wj, x & ~63, y);
+        const int nact = nx - (x & ~63) < 64 ? nx - (x & ~63) : 64;  // lanes still here: fewer than 64 in the ragged last word
+        for (int gy = r.g0 + lane; gy <= r.g1; gy += nact) {
+            unsigned char *row = marks + (size_t)gy * nt;
+            for (int t = r.t0; t <= r.t1; ++t) row[t] = 1;
+        }
+        if (lane == 0) {
+            *word = w;
+            if (atomicAdd(rep, 1u) == 0u && !first) atomicAdd(rep + 1, 1u);
+        }
+    });
+}
+
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_um(const T *lf, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                        int ny, int hi, int hj, int wi, int wj, int first, hipStream_t st) {
+    if (hi < 1 || hj < 1 || wi < 0 || wj < 0) return hipErrorInvalidValue;       // (the ring lies inside the frame)
+    hipLaunchKernelGGL(k_edge_bits_delta_um<T>, dim3((nx + 255) / 256, (ny + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lf, ci,
+                       bits, marks, rep, nx, ny, hi, hj, wi, wj, first);
+    return hipGetLastError();
+}
+
+template hipError_t sb_launch_edge_bits_delta_um<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int,
+                                                        int, int, int, int, int, int, hipStream_t);
+template hipError_t sb_launch_edge_bits_delta_um<double>(const double *, const double *, uint64_t *, unsigned char *, unsigned *,
+                                                         int, int, int, int, int, int, int, hipStream_t);
 
 template hipError_t sb_launch_edge_bits_delta_band<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int,
                                                           int, SbBandRows, int, int, int, int, int, hipStream_t);

@@ -1,7 +1,8 @@
-// sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*) or of a latitude band (sb_band_ice_*) decides:
-// which path it takes, and what a changed word of the coast bit plane can reach.  sb_capi_stream.hip and sb_capi_coast.hip
-// ask for the path, k_edge_bits_delta[_band] (sb_ice_kernels.hip) mark with the same sb_ice_reach / sb_band_ice_reach the
-// host-only tests walk (tests/ice_plan_dump.cpp, tests/band_ice_plan_dump.cpp).  Plain C++17: no HIP, no heap -- a host
+// sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*), of a latitude band (sb_band_ice_*) or of the UM
+// layout (sb_um_ice_*) decides: which path it takes, and what a changed word of the coast bit plane can reach.
+// sb_capi_stream.hip and sb_capi_coast.hip ask for the path, k_edge_bits_delta[_band|_um] (sb_ice_kernels.hip) mark with the
+// same sb_ice_reach / sb_band_ice_reach / sb_um_ice_reach the host-only tests walk (tests/ice_plan_dump.cpp,
+// tests/band_ice_plan_dump.cpp, tests/um_ice_plan_dump.cpp).  Plain C++17: no HIP, no heap -- a host
 // compiler builds it alone; under hipcc the functions are also device functions.
 //
 // The mark plane holds one byte per (target row, 256-column tile): the tiles of the distance kernels (a workgroup of
@@ -96,5 +97,65 @@ inline SbBandIcePlan sb_band_ice_plan(int nx, int ny, int halo, bool south, bool
     p.path = sb_ice_path(nx, k, incremental);
     p.nw = (nx + 63) / 64;
     p.ntiles = sb_ice_tiles(nx);
+    return p;
+}
+
+// ---- the UM layout (sb_um_coast_open_*, sb_um_ice_*; sb_capi_coast.hip) ----
+// The mark plane holds one byte per WORKGROUP of the UM distance kernels (k_dist_um, k_dist_um_wide:
+// sb_um_coast_kernels.hip): SB_UM_ICE_ROWS target rows x SB_UM_ICE_COLS columns, tiled from interior cell (0, 0).  The
+// granularity can be the workgroup, finer than a stream's tiles of whole waves, because these two kernels have no coupling
+// between targets: no ballot over targets decides a value (sb_dist_finish_both is per lane; __syncthreads_or only asks
+// whether the reach holds a coast bit at all), and the early exits -- a reach, a pass, a chunk or a row without a coast
+// bit, the wide kernel's per-pair latitude cut -- skip work that cannot lower a minimum: they are value-neutral.  So a
+// target's value is a function of its own window and nothing its neighbours do.
+// A target (xx, yy) reads the coast bits of interior rows yy-wj .. yy+wj and interior columns xx-wi .. xx+wi that exist --
+// no wrap, no clamp: a window that reaches past the interior finds nothing there -- and nothing else of the coast;
+// landfrac, the coordinates and maxdist stand while the coast is open, and both sweep classes and the reset are
+// functions of those bits alone.  So the changed word at columns x0 .. x0+63 of interior row y can move the targets of
+// rows max(y-wj, 0) .. min(y+wj, ny-1) and columns max(x0-wi, 0) .. min(x0+63+wi, nx-1), one piece, and nothing else.
+// Over-marking costs time and comes from whole words, whole row groups and whole tiles; under-marking would leave a
+// stale distance.
+#define SB_UM_ICE_ROWS 4                                         // target rows of a workgroup (UM_DIST_TY, UMW_TY)
+#define SB_UM_ICE_COLS 64                                        // its columns: one wave per row
+
+SB_ICE_HD int sb_um_ice_groups(int ny) { return (ny + SB_UM_ICE_ROWS - 1) / SB_UM_ICE_ROWS; }
+SB_ICE_HD int sb_um_ice_tiles(int nx) { return (nx + SB_UM_ICE_COLS - 1) / SB_UM_ICE_COLS; }
+
+// the row groups g0 .. g1 and the tiles t0 .. t1 (both inclusive, never empty) whose workgroups hold a target the word at
+// columns x0 .. x0+63 (x0 a multiple of 64, < nx) of interior row y (< ny) can move
+struct SbUmIceReach {
+    int g0, g1, t0, t1;
+};
+
+SB_ICE_HD SbUmIceReach sb_um_ice_reach(int nx, int ny, int wi, int wj, int x0, int y) {
+    SbUmIceReach r;
+    const int ra = y - wj < 0 ? 0 : y - wj, rb = y + wj > ny - 1 ? ny - 1 : y + wj;
+    const int ca = x0 - wi < 0 ? 0 : x0 - wi, cb = x0 + 63 + wi > nx - 1 ? nx - 1 : x0 + 63 + wi;
+    r.g0 = ra / SB_UM_ICE_ROWS; r.g1 = rb / SB_UM_ICE_ROWS;
+    r.t0 = ca / SB_UM_ICE_COLS; r.t1 = cb / SB_UM_ICE_COLS;
+    return r;
+}
+
+// The UM layout has no byte-probe kernel -- both distance kernels read the bit plane -- so `incremental` alone decides.
+// WHOLE: k_edges_um into a scratch frame and sb_launch_dist_um_win; DELTA: k_edge_bits_delta_um and the distance kernel
+// under DistUmDirty.
+inline SbIcePath sb_um_ice_path(int incremental) { return incremental ? SbIcePath::DELTA : SbIcePath::WHOLE; }
+
+// What sb_um_coast_open_* decides: ok == false for sizes, halos (the Sobel reads the one-cell ring) or windows it refuses;
+// else the path and the sizes of the planes.
+struct SbUmIcePlan {
+    bool ok;
+    SbIcePath path;
+    int nw, ngroups, ntiles;     // words per row of the bit plane (ny rows); row groups and tiles per group of the mark plane
+};
+
+inline SbUmIcePlan sb_um_ice_plan(int nx, int ny, int hi, int hj, int wi, int wj, int incremental) {
+    SbUmIcePlan p{};
+    p.ok = nx >= 1 && ny >= 1 && hi >= 1 && hj >= 1 && wi >= 0 && wi <= 255 && wj >= 0 && wj <= 255;
+    if (!p.ok) return p;
+    p.path = sb_um_ice_path(incremental);
+    p.nw = (nx + 63) / 64;
+    p.ngroups = sb_um_ice_groups(ny);
+    p.ntiles = sb_um_ice_tiles(nx);
     return p;
 }

@@ -228,6 +228,20 @@ template <typename T>
 hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                                  int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st);
 
+// A UM-layout coast that moves with the sea ice (sb_um_ice_*; sb_ice_kernels.hip, sb_ice_plan.hpp).  lf, ci: the
+// (nx + 2hi) x (ny + 2hj) frames (first cell), hi, hj >= 1 (else hipErrorInvalidValue).  The interior's coast under the UM's
+// rule as bits, compared with and written into the context's UM bit plane (ny * ceil(nx/64) words); every workgroup of the
+// UM distance kernels (4-row group x 64-column tile) a changed word can reach through the +-wi x +-wj window gets a 1 in
+// marks (ceil(ny/4) * ceil(nx/64) bytes, cleared by the caller); rep as sb_launch_edge_bits_delta ...
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_um(const T *lf, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                        int ny, int hi, int hj, int wi, int wj, int first, hipStream_t st);
+// ... and sb_launch_dist_um_win's kernel over that bit plane, computing the marked workgroups of cdist's interior alone;
+// landfrac_l is the frame (first cell), read in its interior
+template <typename T>
+hipError_t sb_launch_dist_um_dirty(const T *landfrac_l, const T *tlat, const T *tlon, T *cdist, int nx, int ny, int hi, int hj,
+                                   int wi, int wj, T maxdist, const uint64_t *bits, const unsigned char *marks, hipStream_t st);
+
 // search_radius (sb_radius_kernels.hip): the radius of every band cell's window from mask alone.  The kernels work in
 // WINDOW coordinates: a row as the windows see it has W cells -- the nx cells of the circle (SB_BND_GLOBAL, a band;
 // SB_BND_WRAPPER with column nx-1 standing for column 0, the rule's quirk), or the nx + 2h cells of a plain

@@ -7,6 +7,7 @@
 //   k_dist_um      signed haversine distance to the nearest interior coast cell within +-halo_i columns x +-halo_j
 //                  rows, from per-cell coordinates     ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)
 //   k_dist_um_wide the same rule for a window of up to +-255 cells stated apart from the ghost width (sb_get_dist_um_win_*)
+//   k_dist_um_dirty, k_dist_um_wide_dirty  the two under DistUmDirty: only the workgroups an ice call marked (sb_um_ice_*)
 //
 // The UM's get_dist is a scatter from interior coast cells into a window that reaches into the halo; swap_bounds then
 // throws the halo writes away (:584-598).  So sources and targets are interior cells only -- no wrap, no clamp -- and
@@ -16,27 +17,9 @@
 #include "../../include/seabreeze_hip.h"
 #include "sb_launch.hpp"
 #include "sb_coast_common.hpp"
+#include "sb_ice_plan.hpp"
 
-// k_edges_um's layout: the interior offset by (hi, hj) inside the ghost-celled field of NX x NY cells.  The ring cells are
-// ghost cells of the caller; cells past the ring are clamped into the field (their flags are never read for a written
-// cell).
-template <typename T>
-struct EdgesUm {
-    static constexpr bool tail_by_index = true;
-    int NX, NY, hi, hj;
-    __device__ __forceinline__ size_t src(int x, int y) const {
-        int X = x + hi, Y = y + hj;
-        X = X < NX ? X : NX - 1;
-        Y = Y < NY ? Y : NY - 1;
-        return (size_t)Y * NX + X;
-    }
-    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + hj) * NX + x + hi; }
-    __device__ __forceinline__ int land(T l, T c) const {
-        if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
-        return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
-    }
-};
-
+// (EdgesUm, k_edges_um's layout and land rule: sb_coast_common.hpp -- k_edge_bits_delta_um shares it)
 template <typename T>
 __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, const T *__restrict__ ci, T *__restrict__ coast,
                                                   int nx, int ny, int hi, int hj) {
@@ -44,6 +27,26 @@ __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, cons
     sb_edges_block(lf, ci, coast, s_land, nx, ny, EdgesUm<T>{nx + 2 * hi, ny + 2 * hj, hi, hj});   // ref: UM :420-435
 }
 
+// ---- which workgroups a UM distance launch computes, and where landfrac lies ----
+// A policy G, the body's last argument (the kernels are thin __global__ wrappers round um_dist_body / um_dist_wide_body, so
+// the whole-interior instances keep their names and are the kernels they were before the policy came):
+//   DistUmWhole  every workgroup computes; landfrac is an interior (nx, ny) field.  An empty type.
+//   DistUmDirty  the coast moves with the sea ice (sb_um_ice_*): a workgroup whose byte of the mark plane (one per
+//                SB_UM_ICE_ROWS-row group x 64-column tile, sb_ice_plan.hpp) is clear returns before any bit word, barrier or
+//                coordinate, and the stored cdist of its cells stands.  The exit is workgroup-uniform (one byte, read by every
+//                thread), so no barrier is left half-entered.  landfrac is read in the interior of its ghost-celled frame:
+//                pitch ld, interior at off.
+struct DistUmWhole {
+    __device__ __forceinline__ bool skip(int, int) const { return false; }
+    __device__ __forceinline__ size_t lf(int x, int y, int nx) const { return (size_t)y * nx + x; }
+};
+struct DistUmDirty {
+    const unsigned char *mark;
+    int ntiles, ld;
+    size_t off;
+    __device__ __forceinline__ bool skip(int group, int tile) const { return mark[(size_t)group * ntiles + tile] == 0; }
+    __device__ __forceinline__ size_t lf(int x, int y, int) const { return off + (size_t)y * ld + x; }
+};
 
 // The gather.  A workgroup holds UM_DIST_TY target rows of 64 columns (one wave per row).  Its reach is the
 // (64 + 2hi) x (UM_DIST_TY + 2hj) cells round them; every reach row is one 128-bit string of coast bits in LDS, starting at
@@ -68,11 +71,12 @@ __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, cons
 #define UM_DIST_TY 4
 #define UM_DIST_CH 8
 #define UM_DIST_W (64 + 2 * 31)
-template <typename T>
-__global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
-                                                           const T *__restrict__ tlat, const T *__restrict__ tlon,
-                                                           T *__restrict__ cdist, int nx, int ny, int hi, int hj, int nw,
-                                                           T maxdist) {
+static_assert(UM_DIST_TY == SB_UM_ICE_ROWS, "a byte of the mark plane is one workgroup of k_dist_um");
+template <typename T, typename G>
+__device__ __forceinline__ void um_dist_body(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                             const T *__restrict__ tlat, const T *__restrict__ tlon, T *__restrict__ cdist,
+                                             int nx, int ny, int hi, int hj, int nw, T maxdist, const G g) {
+    if (g.skip(blockIdx.y, blockIdx.x)) return;                    // workgroup-uniform, ahead of every barrier
     __shared__ uint64_t s_bw[UM_DIST_TY + 62][2];
     __shared__ T s_sh[UM_DIST_CH][UM_DIST_W], s_ch[UM_DIST_CH][UM_DIST_W], s_cp[UM_DIST_CH][UM_DIST_W], s_l1[UM_DIST_CH][UM_DIST_W];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, tid = threadIdx.x;
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
         l2 = ((r2d * lam1) > T(180.)) ? d2r * ((r2d * lam1) - T(360.)) : lam1;   // ref: UM :560-564
         cost = cos(phit);
         if constexpr (sizeof(T) == 8) { sht = sin(phit / T(2)); cht = cos(phit / T(2)); }
-        lf = landfrac[o];
+        lf = landfrac[g.lf(xx, yy, nx)];
     }
     T a_early = SbDist<T>::none, a_late = SbDist<T>::none;
     const uint64_t lmask = (1ull << L) - 1ull;                     // (L <= 63)
@@ -158,6 +162,21 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__r
     }
     if (!valid) return;
     sb_dist_write(cdist + (size_t)(yy + hj) * NX + xx + hi, sb_dist_finish_both(a_early, a_late, maxdist), &lf);
+}
+template <typename T>
+__global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                           const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                           T *__restrict__ cdist, int nx, int ny, int hi, int hj, int nw,
+                                                           T maxdist) {
+    um_dist_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, nw, maxdist, DistUmWhole{});
+}
+// landfrac: the first cell of the ghost-celled frame (g says where its interior lies)
+template <typename T>
+__global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um_dirty(const uint64_t *__restrict__ bits,
+                                                                 const T *__restrict__ landfrac, const T *__restrict__ tlat,
+                                                                 const T *__restrict__ tlon, T *__restrict__ cdist, int nx,
+                                                                 int ny, int hi, int hj, int nw, T maxdist, DistUmDirty g) {
+    um_dist_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, nw, maxdist, g);
 }
 
 // ------------------------------------------------------------------------------------
@@ -213,11 +232,13 @@ __device__ __forceinline__ T um_sin_as_written(T x) {
     else return sin(x);
 }
 
-template <typename T>
-__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
-                                                              const T *__restrict__ tlat, const T *__restrict__ tlon,
-                                                              T *__restrict__ cdist, int nx, int ny, int hi, int hj, int wi,
-                                                              int wj, int nw, T maxdist) {
+static_assert(UMW_TY == SB_UM_ICE_ROWS, "a byte of the mark plane is one workgroup of k_dist_um_wide");
+template <typename T, typename G>
+__device__ __forceinline__ void um_dist_wide_body(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                  const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                  T *__restrict__ cdist, int nx, int ny, int hi, int hj, int wi, int wj,
+                                                  int nw, T maxdist, const G g) {
+    if (g.skip(blockIdx.y, blockIdx.x)) return;                  // workgroup-uniform, ahead of every barrier
     __shared__ uint64_t s_bw[UMW_SLOTS][UMW_WORDS];
     __shared__ unsigned short s_off[UMW_SLOTS][UMW_WORDS], s_cnt[UMW_SLOTS];
     __shared__ T s_phi[UMW_CAP], s_cp[UMW_CAP], s_l1[UMW_CAP];
@@ -343,7 +364,22 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__
     }
     if (!valid) return;
     sb_dist_write(cdist + (size_t)(yy + hj) * NX + xx + hi, sb_dist_finish_both(a_early, a_late, maxdist),
-                  landfrac + (size_t)yy * nx + xx);
+                  landfrac + g.lf(xx, yy, nx));
+}
+template <typename T>
+__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                              const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                              T *__restrict__ cdist, int nx, int ny, int hi, int hj, int wi,
+                                                              int wj, int nw, T maxdist) {
+    um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, DistUmWhole{});
+}
+template <typename T>
+__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide_dirty(const uint64_t *__restrict__ bits,
+                                                                    const T *__restrict__ landfrac, const T *__restrict__ tlat,
+                                                                    const T *__restrict__ tlon, T *__restrict__ cdist, int nx,
+                                                                    int ny, int hi, int hj, int wi, int wj, int nw, T maxdist,
+                                                                    DistUmDirty g) {
+    um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
 }
 
 template <typename T>
@@ -370,6 +406,29 @@ hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tla
     return hipGetLastError();
 }
 
+// sb_launch_dist_um_win's choice of kernel over a bit plane that is already complete (k_edge_bits_delta_um wrote it),
+// computing the marked workgroups alone.  landfrac_l: the ghost-celled frame, read in its interior; marks: one byte per
+// workgroup, ceil(ny/4) x ceil(nx/64).  One workgroup per tile as ever: an unmarked one leaves at once.
+template <typename T>
+hipError_t sb_launch_dist_um_dirty(const T *landfrac_l, const T *tlat, const T *tlon, T *cdist, int nx, int ny, int hi, int hj,
+                                   int wi, int wj, T maxdist, const uint64_t *bits, const unsigned char *marks, hipStream_t st) {
+    if (hi < 0 || hj < 0 || wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
+    const int nw = (nx + 63) / 64, NX = nx + 2 * hi;
+    const DistUmDirty g{marks, sb_um_ice_tiles(nx), NX, (size_t)hj * NX + hi};
+    const dim3 grid(sb_um_ice_tiles(nx), sb_um_ice_groups(ny));
+    if (wi == hi && wj == hj && wi <= 31 && wj <= 31)
+        hipLaunchKernelGGL(k_dist_um_dirty<T>, grid, dim3(64 * UM_DIST_TY), 0, st, bits, landfrac_l, tlat, tlon, cdist, nx, ny, hi,
+                           hj, nw, maxdist, g);
+    else
+        hipLaunchKernelGGL(k_dist_um_wide_dirty<T>, grid, dim3(64 * UMW_TY), 0, st, bits, landfrac_l, tlat, tlon, cdist, nx, ny, hi,
+                           hj, wi, wj, nw, maxdist, g);
+    return hipGetLastError();
+}
+
+template hipError_t sb_launch_dist_um_dirty<float>(const float *, const float *, const float *, float *, int, int, int, int, int,
+                                                   int, float, const uint64_t *, const unsigned char *, hipStream_t);
+template hipError_t sb_launch_dist_um_dirty<double>(const double *, const double *, const double *, double *, int, int, int, int,
+                                                    int, int, double, const uint64_t *, const unsigned char *, hipStream_t);
 template hipError_t sb_launch_edges_um<float>(const float *, const float *, float *, int, int, int, int, hipStream_t);
 template hipError_t sb_launch_edges_um<double>(const double *, const double *, double *, int, int, int, int, hipStream_t);
 
