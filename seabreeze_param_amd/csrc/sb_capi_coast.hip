@@ -259,7 +259,7 @@ int band_get_dist_host(sb_ctx *c, int nx, int ny, int halo, int south, int north
 // setup_mask's chain -- ghost rows of lsm and ci, band edges, ghost rows of coast, band distance -- per timestep costs four
 // exchanges and the whole band again.  Here the band keeps its coast as a bit plane over its SOURCE rows and forms the
 // bits of the ghost source rows itself from k+1 ghost rows of lsm and ci (integer logic on land flags: exactly what the
-// neighbour would have sent), so an ice call is a clear of the marks, k_edge_bits_delta_band and the band's distance
+// neighbour would have sent), so an ice call is a clear of the marks, k_edge_bits_delta and the band's distance
 // kernel over the marked tiles (sb_ice_plan.hpp says which path, and what a changed word reaches); nothing is exchanged
 // here, nothing waits.  k_scan of the next band step compares the band planes with what the step before left, so the
 // stored plans and windows follow the rewritten cdist by themselves.
@@ -282,25 +282,20 @@ int band_coast_open(sb_ctx *c, int nx, int ny, int halo, int south, int north, c
                                    "the next one), got kwin = " + std::to_string(kwin) + ", halo = " + std::to_string(halo));
     BandCoast &b = c->bc;
     const int nys = pl.rows.nys, ld = nx + 2 * halo;
-    const size_t bitbytes = (size_t)nys * pl.nw * sizeof(uint64_t);
-    const size_t markbytes = ((size_t)ny * pl.ntiles + 3) & ~(size_t)3;
     int rc;
-    if ((rc = ensure(c, b.bits, bitbytes)) || (rc = ensure(c, b.marks, markbytes + 4 * sizeof(unsigned)))) return rc;
-    if (pl.path == SbIcePath::WHOLE && (rc = ensure(c, b.coast, (size_t)nys * ld * sizeof(T)))) return rc;
+    if ((rc = ice_open(c, b.it, (size_t)nys * pl.nw * sizeof(uint64_t), pl.marks,
+                       pl.path == SbIcePath::WHOLE ? (size_t)nys * ld * sizeof(T) : 0, incremental, c->stream)))
+        return rc;
     b.lonlat.resize(((size_t)nx + nys) * sizeof(T));
     std::memcpy(b.lonlat.data(), lon, (size_t)nx * sizeof(T));
     std::memcpy(b.lonlat.data() + (size_t)nx * sizeof(T), lat + pl.rows.f0, (size_t)nys * sizeof(T));   // (nothing beyond a pole)
     // the tables of these coordinates now, so that the first ice call finds them and only enqueues
     if ((rc = dist_tables<T>(c, nx, nys, (const T *)b.lonlat.data(), (const T *)b.lonlat.data() + nx, c->stream))) return rc;
-    HIPCHK(c, hipMemsetAsync(b.bits.p, 0, bitbytes, c->stream));              // the empty coast: the first ice call differs from it
-    HIPCHK(c, hipMemsetAsync((char *)b.marks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->dist_upload_stream == c->stream) c->dist_upload_stream = nullptr;   // (they have landed)
     b.esz = (int)sizeof(T);
     b.nx = nx; b.ny = ny; b.halo = halo; b.south = south ? 1 : 0; b.north = north ? 1 : 0;
-    b.k = kwin; b.rule = rule; b.incremental = incremental ? 1 : 0; b.maxdist = (double)maxdist;
-    b.mark_bytes = markbytes;
-    b.calls = 0;
+    b.k = kwin; b.rule = rule; b.maxdist = (double)maxdist;
     b.open = true;
     return SB_OK;
 }
@@ -312,8 +307,8 @@ int band_ice_dev(sb_ctx *c, const T *lsm, const T *ci, T *cdist, void *stream) {
     if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_ice without sb_band_coast_open");
     if (b.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_band_ice: the band coast was opened in the other precision");
     if (!lsm || !ci || !cdist) return fail(c, SB_ERR_ARG, "null array pointer");
-    const int nx = b.nx, k = b.k, ld = nx + 2 * b.halo, first = b.calls == 0 ? 1 : 0;
-    const SbBandIcePlan pl = sb_band_ice_plan(nx, b.ny, b.halo, b.south != 0, b.north != 0, k, b.incremental);
+    const int nx = b.nx, k = b.k, ld = nx + 2 * b.halo;
+    const SbBandIcePlan pl = sb_band_ice_plan(nx, b.ny, b.halo, b.south != 0, b.north != 0, k, b.it.incremental);
     const SbBandRows br = pl.rows;
     hipStream_t st = stream_of(c, stream);
     // (the tables are keyed on the coordinates' content: another get_dist call on this context may have replaced them)
@@ -325,25 +320,19 @@ int band_ice_dev(sb_ctx *c, const T *lsm, const T *ci, T *cdist, void *stream) {
     const T maxdist = (T)b.maxdist;
     const size_t o = (size_t)br.f0 * ld + b.halo;                // (column 0, source row 0) of a frame
     if (pl.path == SbIcePath::WHOLE) {
-        HIPCHK(c, sb_launch_edges_band_src<T>(lsm, ci, (T *)b.coast.p, nx, b.halo, br, b.south, b.north, b.rule, k, st));
-        HIPCHK(c, sb_launch_dist_band<T>((const T *)b.coast.p, lsm + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx,
-                                         br.nys, br.r0, br.r1, ld, k, maxdist, (uint64_t *)b.bits.p, cuts, st));
+        HIPCHK(c, sb_launch_edges_band_src<T>(lsm, ci, (T *)b.it.coast.p, nx, b.halo, br, b.south, b.north, b.rule, k, st));
+        HIPCHK(c, sb_launch_dist_band<T>((const T *)b.it.coast.p, lsm + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx,
+                                         br.nys, br.r0, br.r1, ld, k, maxdist, (uint64_t *)b.it.bits.p, cuts, st));
     } else {
-        unsigned char *marks = (unsigned char *)b.marks.p;
-        unsigned *rep = (unsigned *)(marks + b.mark_bytes);
-        // the first call computes everything: every tile marked by the host; rep[0] cleared either way
-        if (first) {
-            HIPCHK(c, hipMemsetAsync(marks, 1, b.mark_bytes, st));
-            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
-        } else
-            HIPCHK(c, hipMemsetAsync(marks, 0, b.mark_bytes + sizeof(unsigned), st));
-        HIPCHK(c, sb_launch_edge_bits_delta_band<T>(lsm, ci, (uint64_t *)b.bits.p, marks, rep, nx, b.halo, br, b.south, b.north,
-                                                    b.rule, k, first, st));
+        IceCall ic;
+        if ((rc = ice_begin(c, b.it, st, ic))) return rc;
+        HIPCHK(c, sb_launch_edge_bits_delta_band<T>(lsm, ci, (uint64_t *)b.it.bits.p, ic.marks, ic.rep, nx, b.halo, br, b.south,
+                                                    b.north, b.rule, k, ic.first, st));
         HIPCHK(c, sb_launch_dist_band_dirty<T>(lsm + o, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, cdist + o, nx, br.nys, br.r0,
-                                               br.r1, ld, k, maxdist, (const uint64_t *)b.bits.p, cuts, marks, st));
+                                               br.r1, ld, k, maxdist, (const uint64_t *)b.it.bits.p, cuts, ic.marks, st));
     }
     c->radius_hint = k + 1;
-    b.calls++;
+    b.it.calls++;
     return SB_OK;
 }
 
@@ -514,7 +503,7 @@ int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, 
 // The UM rebuilds its mask from icefrac inside the timestep routine (ref: UM/vn10.7/sea_breeze_diag.F90:384-445), so
 // get_edges_um + get_dist_um_win per timestep cost the whole interior again.  Here the context keeps the interior's coast
 // as a bit plane of its own and the coordinates on the device; an ice call is one clear of [marks | changed-word counter],
-// k_edge_bits_delta_um and the UM distance kernel over the marked workgroups (sb_ice_plan.hpp says which path, and what a
+// k_edge_bits_delta and the UM distance kernel over the marked workgroups (sb_ice_plan.hpp says which path, and what a
 // changed word reaches).  Nothing waits.  k_scan of the next sb_seabreeze_diag_um_* call finds the changed band planes by
 // content.
 template <typename T>
@@ -532,25 +521,19 @@ int um_coast_open(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, con
     if ((double)(nx + 2.0 * hi) * (double)(ny + 2.0 * hj) > 2.0e9) return fail(c, SB_ERR_ARG, "grid too large");
     const SbUmIcePlan pl = sb_um_ice_plan(nx, ny, hi, hj, wi, wj, incremental);
     if (!pl.ok) return fail(c, SB_ERR_ARG, "bad um_coast_open arguments");
-    const size_t n = (size_t)nx * ny, bitbytes = (size_t)ny * pl.nw * sizeof(uint64_t);
-    const size_t markbytes = ((size_t)pl.ngroups * pl.ntiles + 3) & ~(size_t)3;
+    const size_t n = (size_t)nx * ny;
+    const bool whole = pl.path == SbIcePath::WHOLE;
     int rc;
-    if ((rc = ensure(c, u.coords, 2 * n * sizeof(T))) || (rc = ensure(c, u.bits, bitbytes)) ||
-        (rc = ensure(c, u.marks, markbytes + 4 * sizeof(unsigned))))
-        return rc;
-    if (pl.path == SbIcePath::WHOLE &&
-        ((rc = ensure(c, u.coast, (size_t)(nx + 2 * hi) * (ny + 2 * hj) * sizeof(T))) || (rc = ensure(c, u.lf, n * sizeof(T)))))
+    if ((rc = ensure(c, u.coords, 2 * n * sizeof(T))) || (whole && (rc = ensure(c, u.lf, n * sizeof(T)))) ||
+        (rc = ice_open(c, u.it, (size_t)ny * pl.nw * sizeof(uint64_t), pl.marks,
+                       whole ? (size_t)(nx + 2 * hi) * (ny + 2 * hj) * sizeof(T) : 0, incremental, c->stream)))
         return rc;
     HIPCHK(c, hipMemcpyAsync(u.coords.p, tlat, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync((T *)u.coords.p + n, tlon, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(u.bits.p, 0, bitbytes, c->stream));              // the empty coast: the first ice call differs from it
-    HIPCHK(c, hipMemsetAsync((char *)u.marks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                                // (the caller's coordinates may go now)
     u.esz = (int)sizeof(T);
     u.nx = nx; u.ny = ny; u.hi = hi; u.hj = hj; u.wi = wi; u.wj = wj;
-    u.incremental = incremental ? 1 : 0; u.maxdist = (double)maxdist;
-    u.mark_bytes = markbytes;
-    u.calls = 0;
+    u.maxdist = (double)maxdist;
     u.open = true;
     return SB_OK;
 }
@@ -570,31 +553,26 @@ int um_ice_dev(sb_ctx *c, const T *lf, const T *ci, T *cdist, void *stream) {
     int rc = check_um_ice<T>(c, lf, ci, cdist);
     if (rc) return rc;
     UmCoast &u = c->um;
-    const int nx = u.nx, ny = u.ny, hi = u.hi, hj = u.hj, NX = nx + 2 * hi, first = u.calls == 0 ? 1 : 0;
+    const int nx = u.nx, ny = u.ny, hi = u.hi, hj = u.hj, NX = nx + 2 * hi;
     const T *tlat = (const T *)u.coords.p, *tlon = tlat + (size_t)nx * ny;
     const T maxdist = (T)u.maxdist;
     hipStream_t st = stream_of(c, stream);
-    if (sb_um_ice_path(u.incremental) == SbIcePath::WHOLE) {
+    if (sb_um_ice_path(u.it.incremental) == SbIcePath::WHOLE) {
         // today's chain on the context's own planes; sb_launch_dist_um_win reads an interior landfrac: a copy of the frame's
         HIPCHK(c, hipMemcpy2DAsync(u.lf.p, (size_t)nx * sizeof(T), lf + (size_t)hj * NX + hi, (size_t)NX * sizeof(T),
                                    (size_t)nx * sizeof(T), (size_t)ny, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, sb_launch_edges_um<T>(lf, ci, (T *)u.coast.p, nx, ny, hi, hj, st));
-        HIPCHK(c, sb_launch_dist_um_win<T>((const T *)u.coast.p, (const T *)u.lf.p, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj,
-                                           maxdist, (uint64_t *)u.bits.p, st));
+        HIPCHK(c, sb_launch_edges_um<T>(lf, ci, (T *)u.it.coast.p, nx, ny, hi, hj, st));
+        HIPCHK(c, sb_launch_dist_um_win<T>((const T *)u.it.coast.p, (const T *)u.lf.p, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj,
+                                           maxdist, (uint64_t *)u.it.bits.p, st));
     } else {
-        unsigned char *marks = (unsigned char *)u.marks.p;
-        unsigned *rep = (unsigned *)(marks + u.mark_bytes);
-        // the first call computes everything: every workgroup marked by the host; rep[0] cleared either way
-        if (first) {
-            HIPCHK(c, hipMemsetAsync(marks, 1, u.mark_bytes, st));
-            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
-        } else
-            HIPCHK(c, hipMemsetAsync(marks, 0, u.mark_bytes + sizeof(unsigned), st));
-        HIPCHK(c, sb_launch_edge_bits_delta_um<T>(lf, ci, (uint64_t *)u.bits.p, marks, rep, nx, ny, hi, hj, u.wi, u.wj, first, st));
-        HIPCHK(c, sb_launch_dist_um_dirty<T>(lf, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj, maxdist, (const uint64_t *)u.bits.p,
-                                             marks, st));
+        IceCall ic;
+        if ((rc = ice_begin(c, u.it, st, ic))) return rc;
+        HIPCHK(c, sb_launch_edge_bits_delta_um<T>(lf, ci, (uint64_t *)u.it.bits.p, ic.marks, ic.rep, nx, ny, hi, hj, u.wi, u.wj,
+                                                  ic.first, st));
+        HIPCHK(c, sb_launch_dist_um_dirty<T>(lf, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj, maxdist,
+                                             (const uint64_t *)u.it.bits.p, ic.marks, st));
     }
-    u.calls++;
+    u.it.calls++;
     return SB_OK;
 }
 
@@ -634,23 +612,7 @@ int sb_band_ice_report(sb_ctx *c, long long rep[4]) {
     if (!rep) return fail(c, SB_ERR_ARG, "null report");
     BandCoast &b = c->bc;
     if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_ice_report without sb_band_coast_open");
-    const long long tiles = (long long)b.ny * sb_ice_tiles(b.nx);
-    rep[0] = b.calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
-    HIPCHK(c, hipDeviceSynchronize());                           // (the ice calls ran on whichever stream the caller named)
-    if (sb_ice_path(b.nx, b.k, b.incremental) == SbIcePath::WHOLE) {
-        // every call computes every tile and compares nothing
-        rep[1] = -1;
-        rep[2] = b.calls ? tiles : 0;
-        return SB_OK;
-    }
-    if (b.calls == 0) return SB_OK;
-    std::vector<unsigned char> host(b.mark_bytes + 2 * sizeof(unsigned));
-    HIPCHK(c, hipMemcpy(host.data(), b.marks.p, host.size(), hipMemcpyDeviceToHost));
-    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
-    unsigned words[2];
-    std::memcpy(words, host.data() + b.mark_bytes, sizeof(words));
-    rep[1] = words[1];
-    return SB_OK;
+    return ice_report(c, b.it, sb_ice_marks(b.nx, b.ny), sb_ice_path(b.nx, b.k, b.it.incremental) == SbIcePath::WHOLE, true, rep);
 }
 
 int sb_band_coast_close(sb_ctx *c) {
@@ -658,11 +620,9 @@ int sb_band_coast_close(sb_ctx *c) {
     BandCoast &b = c->bc;
     if (!b.open) return fail(c, SB_ERR_ARG, "sb_band_coast_close without sb_band_coast_open");
     HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
-    for (DevBuf *d : {&b.bits, &b.marks, &b.coast})
-        if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    ice_free(b.it);
     b.lonlat.clear();
     b.open = false;
-    b.calls = 0;
     return SB_OK;
 }
 
@@ -671,23 +631,7 @@ int sb_um_ice_report(sb_ctx *c, long long rep[4]) {
     if (!rep) return fail(c, SB_ERR_ARG, "null report");
     UmCoast &u = c->um;
     if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_ice_report without sb_um_coast_open");
-    const long long tiles = (long long)sb_um_ice_groups(u.ny) * sb_um_ice_tiles(u.nx);
-    rep[0] = u.calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
-    HIPCHK(c, hipDeviceSynchronize());                           // (the ice calls ran on whichever stream the caller named)
-    if (sb_um_ice_path(u.incremental) == SbIcePath::WHOLE) {
-        // every call computes every workgroup and compares nothing
-        rep[1] = -1;
-        rep[2] = u.calls ? tiles : 0;
-        return SB_OK;
-    }
-    if (u.calls == 0) return SB_OK;
-    std::vector<unsigned char> host(u.mark_bytes + 2 * sizeof(unsigned));
-    HIPCHK(c, hipMemcpy(host.data(), u.marks.p, host.size(), hipMemcpyDeviceToHost));
-    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
-    unsigned words[2];
-    std::memcpy(words, host.data() + u.mark_bytes, sizeof(words));
-    rep[1] = words[1];
-    return SB_OK;
+    return ice_report(c, u.it, sb_um_ice_marks(u.nx, u.ny), sb_um_ice_path(u.it.incremental) == SbIcePath::WHOLE, true, rep);
 }
 
 int sb_um_coast_close(sb_ctx *c) {
@@ -695,10 +639,10 @@ int sb_um_coast_close(sb_ctx *c) {
     UmCoast &u = c->um;
     if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_coast_close without sb_um_coast_open");
     HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
-    for (DevBuf *d : {&u.coords, &u.bits, &u.marks, &u.coast, &u.lf})
+    for (DevBuf *d : {&u.coords, &u.lf})
         if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    ice_free(u.it);
     u.open = false;
-    u.calls = 0;
     return SB_OK;
 }
 

@@ -88,9 +88,9 @@ class HostPool {
 // the sb_con plane -- of the PREVIOUS step, so that the host copies of step i+1 overlap the device work of step i.
 void stream_release(sb_ctx *c) {
     DiagStream &d = c->ds;
-    for (DevBuf *b : {&d.z, &d.sd, &d.cdist, &d.ws, &d.wd, &d.thc, &d.p1, &d.theta, &d.v, &d.u, &d.out, &d.lsm, &d.ice, &d.icebits,
-                      &d.icemarks, &d.icecoast})
+    for (DevBuf *b : {&d.z, &d.sd, &d.cdist, &d.ws, &d.wd, &d.thc, &d.p1, &d.theta, &d.v, &d.u, &d.out, &d.lsm, &d.ice})
         if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    ice_free(d.it);
     for (int k = 0; k < 2; ++k) {
         if (d.pin_ice[k]) (void)hipHostFree(d.pin_ice[k]);
         if (d.ev_ice[k]) (void)hipEventDestroy(d.ev_ice[k]);
@@ -277,11 +277,10 @@ int stream_coast(sb_ctx *c, const T *lsm, const T *lon, const T *lat, T maxdist,
         return fail(c, SB_ERR_ARG, "sb_diag_stream_coast: window half-width " + std::to_string(k) + " exceeds SB_DIST_MAX_WINDOW = " +
                                        std::to_string(SB_DIST_MAX_WINDOW) + " cells");
     const size_t b2 = (size_t)nx * ny * sizeof(T), bitbytes = (size_t)ny * ((nx + 63) / 64) * sizeof(uint64_t);
-    const size_t markbytes = ((size_t)ny * sb_ice_tiles(nx) + 3) & ~(size_t)3;
-    if ((rc = ensure(c, d.lsm, b2)) || (rc = ensure(c, d.ice, b2)) || (rc = ensure(c, d.icebits, bitbytes)) ||
-        (rc = ensure(c, d.icemarks, markbytes + 4 * sizeof(unsigned))))
+    if ((rc = ensure(c, d.lsm, b2)) || (rc = ensure(c, d.ice, b2)) ||
+        (rc = ice_open(c, d.it, bitbytes, sb_ice_marks(nx, ny), sb_ice_path(nx, k, incremental) == SbIcePath::WHOLE ? b2 : 0,
+                       incremental, c->stream)))
         return rc;
-    if (sb_ice_path(nx, k, incremental) == SbIcePath::WHOLE && (rc = ensure(c, d.icecoast, b2))) return rc;
     if (d.pin_ice_cap < b2) {
         for (int s = 0; s < 2; ++s) {
             if (d.pin_ice[s]) (void)hipHostFree(d.pin_ice[s]);
@@ -297,15 +296,11 @@ int stream_coast(sb_ctx *c, const T *lsm, const T *lon, const T *lat, T maxdist,
     }
     if ((rc = dist_tables<T>(c, nx, ny, lon, lat, c->stream))) return rc;
     HIPCHK(c, hipMemcpyAsync(d.lsm.p, lsm, b2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d.icebits.p, 0, bitbytes, c->stream));           // the empty coast: the first ice call differs from it
-    HIPCHK(c, hipMemsetAsync((char *)d.icemarks.p + markbytes, 0, 4 * sizeof(unsigned), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                                // (lsm is the caller's pageable array)
     d.ice_lonlat.resize(((size_t)nx + ny) * sizeof(T));
     std::memcpy(d.ice_lonlat.data(), lon, (size_t)nx * sizeof(T));
     std::memcpy(d.ice_lonlat.data() + (size_t)nx * sizeof(T), lat, (size_t)ny * sizeof(T));
-    d.ice_k = k; d.ice_incremental = incremental ? 1 : 0; d.ice_maxdist = (double)maxdist;
-    d.ice_mark_bytes = markbytes;
-    d.ice_calls = 0;
+    d.ice_k = k; d.ice_maxdist = (double)maxdist;
     d.ice_ready = true;
     c->radius_hint = k + 1;                 // as get_dist_dev: the distance field bounds the search radius of the steps
     return SB_OK;
@@ -320,9 +315,9 @@ int stream_ice(sb_ctx *c, const T *ci) {
     if (!ci) return fail(c, SB_ERR_ARG, "null array pointer");
     const int nx = d.nlons, ny = d.nlats, k = d.ice_k;
     const size_t b2 = (size_t)nx * ny * sizeof(T);
-    const int slot = (int)(d.ice_calls & 1), first = d.ice_calls == 0 ? 1 : 0;
+    const int slot = (int)(d.it.calls & 1);
     double t0 = now_s();
-    if (d.ice_calls >= 2) HIPCHK(c, hipEventSynchronize(d.ev_ice[slot]));      // the slot's upload of two ice calls ago
+    if (d.it.calls >= 2) HIPCHK(c, hipEventSynchronize(d.ev_ice[slot]));      // the slot's upload of two ice calls ago
     double t1 = now_s();
     d.wait_s += t1 - t0;
     {
@@ -349,27 +344,21 @@ int stream_ice(sb_ctx *c, const T *ci) {
     const T *dphi = (const T *)c->vecs.p, *dlam = dphi + ny;
     const int cuts = sb_dist_cuts(c->dist_traits, k);
     const T maxdist = (T)d.ice_maxdist;
-    if (sb_ice_path(nx, k, d.ice_incremental) == SbIcePath::WHOLE) {
-        HIPCHK(c, sb_launch_edges<T>((const T *)d.lsm.p, (const T *)d.ice.p, (T *)d.icecoast.p, nx, ny, 0, BND_WRAPPER, st));
-        HIPCHK(c, sb_launch_dist<T>((const T *)d.icecoast.p, (const T *)d.lsm.p, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx,
-                                    (T *)d.cdist.p, nx, ny, k, maxdist, (uint64_t *)d.icebits.p, cuts, st));
+    if (sb_ice_path(nx, k, d.it.incremental) == SbIcePath::WHOLE) {
+        HIPCHK(c, sb_launch_edges<T>((const T *)d.lsm.p, (const T *)d.ice.p, (T *)d.it.coast.p, nx, ny, 0, BND_WRAPPER, st));
+        HIPCHK(c, sb_launch_dist<T>((const T *)d.it.coast.p, (const T *)d.lsm.p, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx,
+                                    (T *)d.cdist.p, nx, ny, k, maxdist, (uint64_t *)d.it.bits.p, cuts, st));
     } else {
-        unsigned char *marks = (unsigned char *)d.icemarks.p;
-        unsigned *rep = (unsigned *)(marks + d.ice_mark_bytes);
-        // the first call computes everything: every tile marked by the host; rep[0] cleared either way
-        if (first) {
-            HIPCHK(c, hipMemsetAsync(marks, 1, d.ice_mark_bytes, st));
-            HIPCHK(c, hipMemsetAsync(rep, 0, sizeof(unsigned), st));
-        } else
-            HIPCHK(c, hipMemsetAsync(marks, 0, d.ice_mark_bytes + sizeof(unsigned), st));
-        HIPCHK(c, sb_launch_edge_bits_delta<T>((const T *)d.lsm.p, (const T *)d.ice.p, (uint64_t *)d.icebits.p, marks, rep, nx, ny, k,
-                                               first, st));
+        IceCall ic;
+        if ((rc = ice_begin(c, d.it, st, ic))) return rc;
+        HIPCHK(c, sb_launch_edge_bits_delta<T>((const T *)d.lsm.p, (const T *)d.ice.p, (uint64_t *)d.it.bits.p, ic.marks, ic.rep, nx,
+                                               ny, k, ic.first, st));
         HIPCHK(c, sb_launch_dist_dirty<T>((const T *)d.lsm.p, dphi, dlam, dlam + nx, dlam + 2 * (size_t)nx, (T *)d.cdist.p, nx, ny, k,
-                                          maxdist, (const uint64_t *)d.icebits.p, cuts, marks, st));
+                                          maxdist, (const uint64_t *)d.it.bits.p, cuts, ic.marks, st));
     }
     HIPCHK(c, hipEventRecord(d.ev_ice_t[1], st));
     c->radius_hint = k + 1;
-    d.ice_calls++;
+    d.it.calls++;
     d.enqueue_s += now_s() - t2;
     return SB_OK;
 }
@@ -402,29 +391,14 @@ int sb_diag_stream_ice_report(sb_ctx *c, long long rep[4]) {
     if (!rep) return fail(c, SB_ERR_ARG, "null report");
     DiagStream &d = c->ds;
     if (!d.ice_ready) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice_report without sb_diag_stream_coast");
-    const long long tiles = (long long)d.nlats * sb_ice_tiles(d.nlons);
-    rep[0] = d.ice_calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (sb_ice_path(d.nlons, d.ice_k, d.ice_incremental) == SbIcePath::WHOLE) {
-        // every call computes every tile and compares nothing
-        rep[1] = -1;
-        rep[2] = d.ice_calls ? tiles : 0;
-        return SB_OK;
-    }
-    if (d.ice_calls == 0) return SB_OK;
-    std::vector<unsigned char> host(d.ice_mark_bytes + 2 * sizeof(unsigned));
-    HIPCHK(c, hipMemcpy(host.data(), d.icemarks.p, host.size(), hipMemcpyDeviceToHost));
-    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
-    unsigned words[2];
-    std::memcpy(words, host.data() + d.ice_mark_bytes, sizeof(words));
-    rep[1] = words[1];
-    return SB_OK;
+    return ice_report(c, d.it, sb_ice_marks(d.nlons, d.nlats), sb_ice_path(d.nlons, d.ice_k, d.it.incremental) == SbIcePath::WHOLE,
+                      false, rep);
 }
 
 int sb_diag_stream_ice_time(sb_ctx *c, double *ms) {
     if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
     DiagStream &d = c->ds;
-    if (!ms || !d.ice_ready || d.ice_calls == 0) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice_time without an ice call");
+    if (!ms || !d.ice_ready || d.it.calls == 0) return fail(c, SB_ERR_ARG, "sb_diag_stream_ice_time without an ice call");
     HIPCHK(c, hipEventSynchronize(d.ev_ice_t[1]));
     float t = 0.f;
     HIPCHK(c, hipEventElapsedTime(&t, d.ev_ice_t[0], d.ev_ice_t[1]));

@@ -116,6 +116,8 @@ template <typename T>
 struct EdgesBandSrc {
     static constexpr bool tail_by_index = false;
     int nx, nys, h, ld, f0, lo, hi, rule;
+    __device__ __forceinline__ int cols() const { return nx; }           // the cells it forms edges of (k_edge_bits_delta)
+    __device__ __forceinline__ int rows() const { return nys; }
     __device__ __forceinline__ size_t src(int x, int y) const {
         int X = x % nx;
         X = X < 0 ? X + nx : X;
@@ -133,6 +135,8 @@ template <typename T>
 struct EdgesUm {
     static constexpr bool tail_by_index = true;
     int NX, NY, hi, hj;
+    __device__ __forceinline__ int cols() const { return NX - 2 * hi; }  // the interior (k_edge_bits_delta)
+    __device__ __forceinline__ int rows() const { return NY - 2 * hj; }
     __device__ __forceinline__ size_t src(int x, int y) const {
         int X = x + hi, Y = y + hj;
         X = X < NX ? X : NX - 1;
@@ -324,6 +328,13 @@ __device__ __forceinline__ T sb_dist_finish_wave(T a_early, T a_late, T maxdist)
 //              workgroup-uniform arguments; the other two policies answer false and their instances are what they were.
 //   DistBandDirty  a band whose coast moves (sb_band_ice_*): DistBand's targets and pitch, DistDirty's early exit -- the marks
 //              are one byte per (OWN row, tile), so a target row y is row y - r0 of the plane.
+// no mark on the target rows y0 .. y0+rows-1 below `lim` in the tile's column of a plane whose row 0 is target row `off`
+__device__ __forceinline__ bool sb_marks_clear(const unsigned char *mark, int ntiles, int tile, int y0, int rows, int off, int lim) {
+    unsigned m = 0;
+    for (int r = 0; r < rows; ++r)
+        if (y0 + r < lim) m |= mark[(size_t)(y0 + r - off) * ntiles + tile];
+    return m == 0;
+}
 struct DistWhole {
     __device__ __forceinline__ int t0() const { return 0; }
     __device__ __forceinline__ int t1(int ny) const { return ny; }
@@ -344,10 +355,7 @@ struct DistDirty {
     __device__ __forceinline__ int t1(int ny) const { return ny; }
     __device__ __forceinline__ size_t at(int x, int y, int nx) const { return (size_t)y * nx + x; }
     __device__ __forceinline__ bool skip(int y0, int rows, int ny, int tile) const {
-        unsigned m = 0;
-        for (int r = 0; r < rows; ++r)
-            if (y0 + r < ny) m |= mark[(size_t)(y0 + r) * ntiles + tile];
-        return m == 0;
+        return sb_marks_clear(mark, ntiles, tile, y0, rows, 0, ny);
     }
 };
 struct DistBandDirty {
@@ -358,10 +366,7 @@ struct DistBandDirty {
     __device__ __forceinline__ int t1(int) const { return r1; }
     __device__ __forceinline__ size_t at(int x, int y, int) const { return (size_t)y * ld + x; }
     __device__ __forceinline__ bool skip(int y0, int rows, int, int tile) const {
-        unsigned m = 0;
-        for (int r = 0; r < rows; ++r)
-            if (y0 + r < r1) m |= mark[(size_t)(y0 + r - r0) * ntiles + tile];
-        return m == 0;
+        return sb_marks_clear(mark, ntiles, tile, y0, rows, r0, r1);
     }
 };
 

@@ -623,7 +623,7 @@ hipError_t sb_launch_dist_dirty(const T *mask, const T *phi, const T *lamf, cons
 }
 
 // One latitude band whose coast moves (sb_band_ice_*): sb_launch_dist_band's arguments without a coast plane -- `bits` is
-// the band's own bit plane over its nys source rows, kept up to date by k_edge_bits_delta_band, which also left the marks
+// the band's own bit plane over its nys source rows, kept up to date by k_edge_bits_delta's band instance, which also left the marks
 // (one byte per (own row, tile)).  The kernel sb_launch_dist_band would take; not k_dist (sb_ice_plan.hpp).
 template <typename T>
 hipError_t sb_launch_dist_band_dirty(const T *mask, const T *phi, const T *lamf, const T *shl, const T *chl, T *cdist, int nx,

@@ -3,8 +3,10 @@
 #pragma once
 #include "../../include/seabreeze_hip.h"
 #include "sb_launch.hpp"
+#include "sb_ice_plan.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <utility>
@@ -22,6 +24,16 @@ struct DevBuf {
     DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
     DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
     ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// What every coast that moves with the sea ice keeps on the device (a stream's, a band's, the UM layout's): its own coast
+// bit plane (the context's `coastbits` and `umbits` are scratch of other get_dist calls), [marks | rep] and, on the whole
+// path, a coast plane.  ice_open .. ice_free below work on it; what is specific to a layout stays with the layout.
+struct IceTrack {
+    DevBuf bits, marks, coast;
+    size_t mark_bytes = 0;              // bytes of the mark plane, rounded up to a word; rep (4 words) follows
+    int incremental = 1;
+    long long calls = 0;                // ice calls since ice_open; the caller counts a call once it is enqueued
 };
 
 class HostPool;                     // sb_capi_stream.hip
@@ -43,46 +55,40 @@ struct DiagStream {
     long steps = 0;
     double host_copy_s = 0.0, enqueue_s = 0.0, wait_s = 0.0;   // where the host spent its time (sb_diag_stream_stats)
     // a coast that moves with the sea ice (sb_diag_stream_coast / _ice): the land mask and the step's ice plane, the
-    // stream's own coast bit plane (the context's `coastbits` is scratch of other get_dist calls), [marks | rep] and, on
-    // the whole-grid path, a coast plane; the pinned staging of the ice plane; what sb_diag_stream_coast derived
+    // stream's planes of it (it); the pinned staging of the ice plane; what sb_diag_stream_coast derived
     bool ice_ready = false;                    // sb_diag_stream_coast since the last sb_diag_stream_begin
-    DevBuf lsm, ice, icebits, icemarks, icecoast;
+    DevBuf lsm, ice;
+    IceTrack it;
     void *pin_ice[2] = {nullptr, nullptr};
     size_t pin_ice_cap = 0;
     hipEvent_t ev_ice[2] = {nullptr, nullptr};
     hipEvent_t ev_ice_t[2] = {nullptr, nullptr};   // round the device work of the last ice call (sb_diag_stream_ice_time)
     std::vector<unsigned char> ice_lonlat;     // lon(nlons) | lat(nlats): every ice call keys the coordinate tables with them
-    int ice_k = 0, ice_incremental = 1;
+    int ice_k = 0;
     double ice_maxdist = 0.0;
-    size_t ice_mark_bytes = 0;                 // bytes of the mark plane, rounded up to a word; rep follows
-    long long ice_calls = 0;
 };
 
-// A band whose coast moves with the sea ice (sb_band_coast_open / sb_band_ice_*_dev): the geometry it was opened for, the
-// band's own coast bit plane over its source rows (the context's `coastbits` is scratch of other get_dist calls),
-// [marks | rep] and, on the whole path, a coast plane over the source rows; lon and the source rows' latitudes, with
-// which every ice call keys the coordinate tables.
+// A band whose coast moves with the sea ice (sb_band_coast_open / sb_band_ice_*_dev): the geometry it was opened for, its
+// planes (it: the bit plane and, on the whole path, the coast plane cover the band's source rows; one mark byte per (own
+// row, tile)); lon and the source rows' latitudes, with which every ice call keys the coordinate tables.
 struct BandCoast {
     bool open = false;
-    int esz = 0, nx = 0, ny = 0, halo = 0, south = 0, north = 0, k = 0, rule = 0, incremental = 1;
+    int esz = 0, nx = 0, ny = 0, halo = 0, south = 0, north = 0, k = 0, rule = 0;
     double maxdist = 0.0;
-    DevBuf bits, marks, coast;
-    size_t mark_bytes = 0;                     // bytes of the mark plane, rounded up to a word; rep follows
+    IceTrack it;
     std::vector<unsigned char> lonlat;         // lon(nx) | lat(nys)
-    long long calls = 0;
 };
 
 // A UM-layout coast that moves with the sea ice (sb_um_coast_open / sb_um_ice_*): the geometry it was opened for, the
-// coordinates on the device (tlat | tlon, interior fields), the context's own coast bit plane over the interior (`umbits`
-// is scratch of other get_dist_um calls), [marks | rep] with one mark byte per workgroup of the UM distance kernels, and, on
-// the whole path, a coast frame and an interior copy of landfrac.  Independent of the stream's and the band's moving coasts.
+// coordinates on the device (tlat | tlon, interior fields), its planes (it: the bit plane covers the interior, one mark
+// byte per workgroup of the UM distance kernels, the whole path's coast is a frame) and, on the whole path, an interior
+// copy of landfrac.  Independent of the stream's and the band's moving coasts.
 struct UmCoast {
     bool open = false;
-    int esz = 0, nx = 0, ny = 0, hi = 0, hj = 0, wi = 0, wj = 0, incremental = 1;
+    int esz = 0, nx = 0, ny = 0, hi = 0, hj = 0, wi = 0, wj = 0;
     double maxdist = 0.0;
-    DevBuf coords, bits, marks, coast, lf;
-    size_t mark_bytes = 0;                     // bytes of the mark plane, rounded up to a word; rep follows
-    long long calls = 0;
+    DevBuf coords, lf;
+    IceTrack it;
 };
 
 struct sb_ctx {
@@ -216,6 +222,69 @@ inline int ensure(sb_ctx *c, DevBuf &b, size_t bytes) {
     if (e != hipSuccess) return fail(c, SB_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
     b.cap = bytes;
     return SB_OK;
+}
+
+// ---- the planes of a coast that moves with the sea ice (IceTrack) ----
+// sizes in; the empty coast in the bit plane -- the first ice call differs from it -- and a cleared rep, enqueued on st
+inline int ice_open(sb_ctx *c, IceTrack &t, size_t bitbytes, SbIceMarks m, size_t coastbytes, int incremental, hipStream_t st) {
+    const size_t markbytes = ((size_t)m.rows * m.tiles + 3) & ~(size_t)3;
+    int rc;
+    if ((rc = ensure(c, t.bits, bitbytes)) || (rc = ensure(c, t.marks, markbytes + 4 * sizeof(unsigned)))) return rc;
+    if (coastbytes && (rc = ensure(c, t.coast, coastbytes))) return rc;
+    HIPCHK(c, hipMemsetAsync(t.bits.p, 0, bitbytes, st));
+    HIPCHK(c, hipMemsetAsync((char *)t.marks.p + markbytes, 0, 4 * sizeof(unsigned), st));
+    t.mark_bytes = markbytes;
+    t.incremental = incremental ? 1 : 0;
+    t.calls = 0;
+    return SB_OK;
+}
+
+// what a call on the delta path hands its kernels
+struct IceCall {
+    unsigned char *marks;
+    unsigned *rep;
+    int first;
+};
+
+// the first call computes everything: every byte marked by the host; rep[0] cleared either way
+inline int ice_begin(sb_ctx *c, const IceTrack &t, hipStream_t st, IceCall &call) {
+    call.marks = (unsigned char *)t.marks.p;
+    call.rep = (unsigned *)(call.marks + t.mark_bytes);
+    call.first = t.calls == 0 ? 1 : 0;
+    if (call.first) {
+        HIPCHK(c, hipMemsetAsync(call.marks, 1, t.mark_bytes, st));
+        HIPCHK(c, hipMemsetAsync(call.rep, 0, sizeof(unsigned), st));
+    } else
+        HIPCHK(c, hipMemsetAsync(call.marks, 0, t.mark_bytes + sizeof(unsigned), st));
+    return SB_OK;
+}
+
+// rep[4] of sb_*_ice_report: calls, calls whose coast differed (-1 on the whole path), bytes marked by the last call, bytes
+// of the plane.  device_wide: the ice calls ran on whichever stream the caller named; else on the context's own.
+inline int ice_report(sb_ctx *c, const IceTrack &t, SbIceMarks m, bool whole, bool device_wide, long long rep[4]) {
+    const long long tiles = (long long)m.rows * m.tiles;
+    rep[0] = t.calls; rep[1] = 0; rep[2] = 0; rep[3] = tiles;
+    HIPCHK(c, device_wide ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
+    if (whole) {
+        // every call computes every tile and compares nothing
+        rep[1] = -1;
+        rep[2] = t.calls ? tiles : 0;
+        return SB_OK;
+    }
+    if (t.calls == 0) return SB_OK;
+    std::vector<unsigned char> host(t.mark_bytes + 2 * sizeof(unsigned));
+    HIPCHK(c, hipMemcpy(host.data(), t.marks.p, host.size(), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < tiles; ++i) rep[2] += host[(size_t)i] ? 1 : 0;
+    unsigned words[2];
+    std::memcpy(words, host.data() + t.mark_bytes, sizeof(words));
+    rep[1] = words[1];
+    return SB_OK;
+}
+
+inline void ice_free(IceTrack &t) {
+    for (DevBuf *d : {&t.bits, &t.marks, &t.coast})
+        if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    t.calls = 0;
 }
 
 template <typename T>

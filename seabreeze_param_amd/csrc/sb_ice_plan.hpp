@@ -1,9 +1,10 @@
 // sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*), of a latitude band (sb_band_ice_*) or of the UM
 // layout (sb_um_ice_*) decides: which path it takes, and what a changed word of the coast bit plane can reach.
-// sb_capi_stream.hip and sb_capi_coast.hip ask for the path, k_edge_bits_delta[_band|_um] (sb_ice_kernels.hip) mark with the
-// same sb_ice_reach / sb_band_ice_reach / sb_um_ice_reach the host-only tests walk (tests/ice_plan_dump.cpp,
-// tests/band_ice_plan_dump.cpp, tests/um_ice_plan_dump.cpp).  Plain C++17: no HIP, no heap -- a host
-// compiler builds it alone; under hipcc the functions are also device functions.
+// sb_capi_stream.hip and sb_capi_coast.hip ask for the path, the three instances of k_edge_bits_delta (sb_ice_kernels.hip)
+// mark with the same sb_ice_reach / sb_band_ice_reach / sb_um_ice_reach the host-only tests walk (tests/plan_dump.cpp).
+// Every layout states its mark plane as one SbIceMarks (rows x tiles bytes) and its reach as one SbIceReach in the rows and
+// tiles OF THAT PLANE, so the kernel's mark loop, the distance kernels' early exit and the report read any of them alike.
+// Plain C++17: no HIP, no heap -- a host compiler builds it alone; under hipcc the functions are also device functions.
 //
 // The mark plane holds one byte per (target row, 256-column tile): the tiles of the distance kernels (a workgroup of
 // k_dist_bits_small is one row of a tile, of k_dist_bits and k_dist_wide two).  A target (xx, yy) reads the coast bits of
@@ -27,11 +28,21 @@
 
 SB_ICE_HD int sb_ice_tiles(int nx) { return (nx + SB_ICE_TILE - 1) / SB_ICE_TILE; }
 
-// the target rows r0 .. r1 and the tile columns a0 .. a1 and b0 .. b1 (the second piece is empty, b1 < b0, unless the span
-// crosses the seam) that the word at columns x0 .. x0+63 (x0 a multiple of 64, < nx) of row y can reach
+// a mark plane: rows x tiles bytes, row by row
+struct SbIceMarks {
+    int rows, tiles;
+};
+
+SB_ICE_HD SbIceMarks sb_ice_marks(int nx, int ny) { return SbIceMarks{ny, sb_ice_tiles(nx)}; }
+
+// what the word at columns x0 .. x0+63 (x0 a multiple of 64, < nx) of one row of the bit plane can reach, in any layout:
+// rows r0 .. r1 of the mark plane and its tiles a0 .. a1 and b0 .. b1 (all inclusive; the second piece is empty, b1 < b0,
+// unless the span crosses the seam of a circular grid)
 struct SbIceReach {
     int r0, r1, a0, a1, b0, b1;
 };
+
+// the whole grid: the mark plane's rows are the target rows
 
 SB_ICE_HD SbIceReach sb_ice_reach(int nx, int ny, int k, int x0, int y) {
     SbIceReach r;
@@ -61,11 +72,11 @@ SB_ICE_HD SbIceReach sb_ice_reach(int nx, int ny, int k, int x0, int y) {
 // DistBand tiles from column 0 with one target row per wave, as on the globe, so a tile holds whole waves here too.
 // Ghost source rows are compared and stored like own rows: their bits are what the neighbour band holds for its own
 // rows, formed here from the k+1 ghost rows of lsm and ci (the Sobel of the k-th ghost row reads the (k+1)-th).
-// r0, r1 of the result are source rows; a0 .. b1 as in sb_ice_reach.
+// r0, r1 of the result are OWN rows, the rows of the mark plane: the band's row offset is applied here and nowhere else.
+// Counted from the first own row that is the whole grid's rule for a plane of r1 - r0 rows and the row s - r0 (negative
+// south of the band, beyond the plane north of it: the clamp serves both): rows max(s-r0-k, 0) .. min(s-r0+k, r1-r0-1).
 SB_ICE_HD SbIceReach sb_band_ice_reach(int nx, int r0, int r1, int k, int x0, int s) {
-    SbIceReach r = sb_ice_reach(nx, r1, k, x0, s);               // rows max(s-k, 0) .. min(s+k, r1-1)
-    r.r0 = r.r0 < r0 ? r0 : r.r0;
-    return r;
+    return sb_ice_reach(nx, r1 - r0, k, x0, s - r0);
 }
 
 // WHOLE: k_edges into a scratch plane and the whole-grid distance launch (sb_launch_dist), for a stream opened with
@@ -86,7 +97,8 @@ struct SbBandIcePlan {
     bool ok;
     SbBandRows rows;
     SbIcePath path;
-    int nw, ntiles;          // words per row of the bit plane (rows.nys rows), tiles per row of the mark plane (ny rows)
+    int nw;                  // words per row of the bit plane (rows.nys rows)
+    SbIceMarks marks;        // ny own rows x tiles
 };
 
 inline SbBandIcePlan sb_band_ice_plan(int nx, int ny, int halo, bool south, bool north, int k, int incremental) {
@@ -96,7 +108,7 @@ inline SbBandIcePlan sb_band_ice_plan(int nx, int ny, int halo, bool south, bool
     p.rows = sb_band_rows(ny, halo, south, north, k);
     p.path = sb_ice_path(nx, k, incremental);
     p.nw = (nx + 63) / 64;
-    p.ntiles = sb_ice_tiles(nx);
+    p.marks = sb_ice_marks(nx, ny);
     return p;
 }
 
@@ -118,26 +130,25 @@ inline SbBandIcePlan sb_band_ice_plan(int nx, int ny, int halo, bool south, bool
 #define SB_UM_ICE_ROWS 4                                         // target rows of a workgroup (UM_DIST_TY, UMW_TY)
 #define SB_UM_ICE_COLS 64                                        // its columns: one wave per row
 
-SB_ICE_HD int sb_um_ice_groups(int ny) { return (ny + SB_UM_ICE_ROWS - 1) / SB_UM_ICE_ROWS; }
-SB_ICE_HD int sb_um_ice_tiles(int nx) { return (nx + SB_UM_ICE_COLS - 1) / SB_UM_ICE_COLS; }
+// row groups x tiles
+SB_ICE_HD SbIceMarks sb_um_ice_marks(int nx, int ny) {
+    return SbIceMarks{(ny + SB_UM_ICE_ROWS - 1) / SB_UM_ICE_ROWS, (nx + SB_UM_ICE_COLS - 1) / SB_UM_ICE_COLS};
+}
 
-// the row groups g0 .. g1 and the tiles t0 .. t1 (both inclusive, never empty) whose workgroups hold a target the word at
-// columns x0 .. x0+63 (x0 a multiple of 64, < nx) of interior row y (< ny) can move
-struct SbUmIceReach {
-    int g0, g1, t0, t1;
-};
-
-SB_ICE_HD SbUmIceReach sb_um_ice_reach(int nx, int ny, int wi, int wj, int x0, int y) {
-    SbUmIceReach r;
+// the row groups r0 .. r1 and the tiles a0 .. a1 (never empty; no second piece: nothing wraps) whose workgroups hold a
+// target the word at columns x0 .. x0+63 (x0 a multiple of 64, < nx) of interior row y (< ny) can move
+SB_ICE_HD SbIceReach sb_um_ice_reach(int nx, int ny, int wi, int wj, int x0, int y) {
+    SbIceReach r;
     const int ra = y - wj < 0 ? 0 : y - wj, rb = y + wj > ny - 1 ? ny - 1 : y + wj;
     const int ca = x0 - wi < 0 ? 0 : x0 - wi, cb = x0 + 63 + wi > nx - 1 ? nx - 1 : x0 + 63 + wi;
-    r.g0 = ra / SB_UM_ICE_ROWS; r.g1 = rb / SB_UM_ICE_ROWS;
-    r.t0 = ca / SB_UM_ICE_COLS; r.t1 = cb / SB_UM_ICE_COLS;
+    r.r0 = ra / SB_UM_ICE_ROWS; r.r1 = rb / SB_UM_ICE_ROWS;
+    r.a0 = ca / SB_UM_ICE_COLS; r.a1 = cb / SB_UM_ICE_COLS;
+    r.b0 = 0; r.b1 = -1;
     return r;
 }
 
 // The UM layout has no byte-probe kernel -- both distance kernels read the bit plane -- so `incremental` alone decides.
-// WHOLE: k_edges_um into a scratch frame and sb_launch_dist_um_win; DELTA: k_edge_bits_delta_um and the distance kernel
+// WHOLE: k_edges_um into a scratch frame and sb_launch_dist_um_win; DELTA: k_edge_bits_delta's UM instance and the distance kernel
 // under DistUmDirty.
 inline SbIcePath sb_um_ice_path(int incremental) { return incremental ? SbIcePath::DELTA : SbIcePath::WHOLE; }
 
@@ -146,7 +157,8 @@ inline SbIcePath sb_um_ice_path(int incremental) { return incremental ? SbIcePat
 struct SbUmIcePlan {
     bool ok;
     SbIcePath path;
-    int nw, ngroups, ntiles;     // words per row of the bit plane (ny rows); row groups and tiles per group of the mark plane
+    int nw;                      // words per row of the bit plane (ny rows)
+    SbIceMarks marks;            // row groups x tiles per group
 };
 
 inline SbUmIcePlan sb_um_ice_plan(int nx, int ny, int hi, int hj, int wi, int wj, int incremental) {
@@ -155,7 +167,6 @@ inline SbUmIcePlan sb_um_ice_plan(int nx, int ny, int hi, int hj, int wi, int wj
     if (!p.ok) return p;
     p.path = sb_um_ice_path(incremental);
     p.nw = (nx + 63) / 64;
-    p.ngroups = sb_um_ice_groups(ny);
-    p.ntiles = sb_um_ice_tiles(nx);
+    p.marks = sb_um_ice_marks(nx, ny);
     return p;
 }

@@ -19,7 +19,7 @@
 #include "sb_coast_common.hpp"
 #include "sb_ice_plan.hpp"
 
-// (EdgesUm, k_edges_um's layout and land rule: sb_coast_common.hpp -- k_edge_bits_delta_um shares it)
+// (EdgesUm, k_edges_um's layout and land rule: sb_coast_common.hpp -- k_edge_bits_delta's UM instance shares it)
 template <typename T>
 __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, const T *__restrict__ ci, T *__restrict__ coast,
                                                   int nx, int ny, int hi, int hj) {
@@ -406,7 +406,7 @@ hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tla
     return hipGetLastError();
 }
 
-// sb_launch_dist_um_win's choice of kernel over a bit plane that is already complete (k_edge_bits_delta_um wrote it),
+// sb_launch_dist_um_win's choice of kernel over a bit plane that is already complete (k_edge_bits_delta wrote it),
 // computing the marked workgroups alone.  landfrac_l: the ghost-celled frame, read in its interior; marks: one byte per
 // workgroup, ceil(ny/4) x ceil(nx/64).  One workgroup per tile as ever: an unmarked one leaves at once.
 template <typename T>
@@ -414,8 +414,9 @@ hipError_t sb_launch_dist_um_dirty(const T *landfrac_l, const T *tlat, const T *
                                    int wi, int wj, T maxdist, const uint64_t *bits, const unsigned char *marks, hipStream_t st) {
     if (hi < 0 || hj < 0 || wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
     const int nw = (nx + 63) / 64, NX = nx + 2 * hi;
-    const DistUmDirty g{marks, sb_um_ice_tiles(nx), NX, (size_t)hj * NX + hi};
-    const dim3 grid(sb_um_ice_tiles(nx), sb_um_ice_groups(ny));
+    const SbIceMarks m = sb_um_ice_marks(nx, ny);
+    const DistUmDirty g{marks, m.tiles, NX, (size_t)hj * NX + hi};
+    const dim3 grid(m.tiles, m.rows);
     if (wi == hi && wj == hj && wi <= 31 && wj <= 31)
         hipLaunchKernelGGL(k_dist_um_dirty<T>, grid, dim3(64 * UM_DIST_TY), 0, st, bits, landfrac_l, tlat, tlon, cdist, nx, ny, hi,
                            hj, nw, maxdist, g);

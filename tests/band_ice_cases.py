@@ -19,7 +19,9 @@ CASES = [("BITS32",      320, 15, 16, (33, 33, 33), "BITS32"),
          ("BYTES",        24, 15, 16, (17, 21, 19), "BYTES"),         # no bit plane: the whole path
          ("WIDE",        320, 40, 41, (50, 50, 50), "WIDE"),
          ("WIDE-odd",    320, 40, 41, (49, 51, 50), "WIDE"),
-         ("BITS32-700",  700, 15, 16, (33, 33, 33), "BITS32")]        # three tiles, a ragged last word, the seam
+         ("BITS32-700",  700, 15, 16, (33, 33, 33), "BITS32"),        # three tiles, a ragged last word, the seam
+         # a last word of 6 cells whose reach spans up to 31 rows: the delta kernel's mark loop takes more than one stride
+         ("SMALL-70",     70, 15, 16, (33, 33, 33), "BITS_SMALL")]
 
 PLANES = ["1 initial ice", "2 the same plane", "3 values changed, no cell crosses a threshold", "4 one interior cell crosses",
           "5 cells at rows r0-(k+1) and r1+k", "6 a cell at row r0-(k+2)", "7 cells at column 0 and nx-1",

@@ -1,5 +1,6 @@
-// plan_dump.cpp -- prints what seabreeze_param_amd/csrc/sb_diag_plan.hpp decides, and drives the host's half of the window
-// cache (sb_table_cache.hpp), one command per line of standard input, for tests/plan_dump.py and the tests that import it.
+// plan_dump.cpp -- prints what seabreeze_param_amd/csrc/sb_diag_plan.hpp and sb_ice_plan.hpp decide, and drives the host's
+// half of the window cache (sb_table_cache.hpp), one command per line of standard input, for tests/plan_dump.py and the
+// tests that import it.
 // Host only: the headers need neither HIP nor a device.
 //
 //   plan label [name=value ...]      the launch plan (sb_plan_diag) and the guard's (sb_plan_guard) of one SbPlanIn:
@@ -13,6 +14,19 @@
 //   other | failed | toggled         another diag call or band step ran k_scan; a launch failed; the switch was set
 //   word found radius nl             prints the word of plane W for a cell and what the query reads back from it:
 //                                    "word radius nl"
+//   ice | band_ice | um_ice  P | M label ...   what sb_ice_plan.hpp decides for a coast that moves with the sea ice: of a
+//                                    stream, of a latitude band, of the UM layout.  P: the path and the planes' sizes; M: the
+//                                    mark plane after the words that hold the changed cells (x, row of the bit plane) marked
+//                                    their reach, each word once, as k_edge_bits_delta does
+//     ice P label nx k incremental                        -> label WHOLE | DELTA
+//     ice M label nx ny k n x1 y1 .. xn yn                -> label ntiles, then ny * ntiles marks (0 / 1), row by row
+//     band_ice P label nx ny halo south north k incremental -> label NONE | (WHOLE | DELTA) f0 nys r0 r1 nw ntiles
+//     band_ice M label nx ny halo south north k n x1 s1 .. xn sn   (s: a SOURCE row)
+//                                                         -> label ntiles, then ny * ntiles marks, own row by own row
+//     um_ice P label nx ny hi hj wi wj incremental        -> label NONE | (WHOLE | DELTA) nw ngroups ntiles
+//     um_ice M label nx ny wi wj n x1 y1 .. xn yn         -> label ngroups ntiles, then ngroups * ntiles marks, group by group
+//                                    Exit status 2: a reach outside the mark plane (the kernel would write out of bounds);
+//                                    3: a plan whose path is not the path function's.
 // An input that is not named takes the default that get() states below; a name nobody asks for is an error.  The domain
 // is nx x 96 interior cells, nx = 200 unless given: both strip kernels' block grids are 7 x 6 (32 owned columns x 16 rows)
 // and fit their position planes unless `fits` is 0; the tile kernel's tiles are 32 x 32 (halo 24) and 32 x 16 (halo 32).
@@ -21,7 +35,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
+#include <utility>
+#include <vector>
 #include "../seabreeze_param_amd/csrc/sb_diag_plan.hpp"
+#include "../seabreeze_param_amd/csrc/sb_ice_plan.hpp"
 #include "../seabreeze_param_amd/csrc/sb_table_cache.hpp"
 
 namespace {
@@ -114,6 +132,101 @@ void print_switches(const char *label, const SbSwitches &s, const SbCall &c, SbP
                 (int)sb_band_folds_frame(s, sb_plan_contrast(in), in.nx), (int)p.table, (int)sb_plan_guard(in, p).on);
 }
 
+// ---- sb_ice_plan.hpp ----
+static_assert(SB_UM_ICE_ROWS == 4 && SB_UM_ICE_COLS == 64, "the tests' model states the UM tile as 4 x 64");
+
+// the next n integers of a line
+bool ints(char *&p, int *v, int n) {
+    for (int i = 0; i < n; ++i) {
+        char *end;
+        v[i] = (int)std::strtol(p, &end, 10);
+        if (end == p) return false;
+        p = end;
+    }
+    return true;
+}
+
+// The M line of any layout: reads "n x1 y1 .. xn yn" (x < nx, y < rows of the bit plane), marks what reach(x0, y) says
+// for each word once and prints the plane `m`.  -> the exit status, 0 to go on
+template <typename R>
+int print_marks(const char *label, char *p, int nx, int rows, SbIceMarks m, bool with_rows, R reach) {
+    int n, xy[2];
+    if (!ints(p, &n, 1) || n < 0) return 1;
+    std::set<std::pair<int, int>> words;
+    for (int i = 0; i < n; ++i) {
+        if (!ints(p, xy, 2) || xy[0] < 0 || xy[0] >= nx || xy[1] < 0 || xy[1] >= rows) return 1;
+        words.insert({xy[0] & ~63, xy[1]});
+    }
+    std::vector<unsigned char> marks((size_t)m.rows * m.tiles, 0);
+    for (const auto &w : words) {
+        const SbIceReach r = reach(w.first, w.second);
+        // a mark outside the plane: the kernel would write out of bounds.  The first piece is never empty.
+        if (r.r0 < 0 || r.r1 >= m.rows || r.r0 > r.r1 || r.a0 < 0 || r.a1 >= m.tiles || r.a0 > r.a1) return 2;
+        if (r.b0 <= r.b1 && (r.b0 < 0 || r.b1 >= m.tiles)) return 2;
+        for (int y = r.r0; y <= r.r1; ++y) {
+            for (int t = r.a0; t <= r.a1; ++t) marks[(size_t)y * m.tiles + t] = 1;
+            for (int t = r.b0; t <= r.b1; ++t) marks[(size_t)y * m.tiles + t] = 1;
+        }
+    }
+    std::printf("%s", label);
+    if (with_rows) std::printf(" %d", m.rows);
+    std::printf(" %d", m.tiles);
+    for (unsigned char b : marks) std::printf(" %d", (int)b);
+    std::printf("\n");
+    return 0;
+}
+
+const char *path_name(SbIcePath p) { return p == SbIcePath::WHOLE ? "WHOLE" : "DELTA"; }
+
+// one `ice`, `band_ice` or `um_ice` line -> the exit status, 0 to go on
+int ice_line(const char *cmd, char *rest) {
+    char what[8], label[128];
+    int at = 0, v[7];
+    if (std::sscanf(rest, "%7s %127s%n", what, label, &at) != 2 || (what[0] != 'P' && what[0] != 'M')) return 1;
+    char *p = rest + at;
+    const bool P = what[0] == 'P';
+    if (cmd[0] == 'i') {
+        if (P) {
+            if (!ints(p, v, 3)) return 1;
+            std::printf("%s %s\n", label, path_name(sb_ice_path(v[0], v[1], v[2])));
+            return 0;
+        }
+        if (!ints(p, v, 3) || v[0] < 1 || v[1] < 1) return 1;
+        const int nx = v[0], ny = v[1], k = v[2];
+        return print_marks(label, p, nx, ny, sb_ice_marks(nx, ny), false, [=](int x0, int y) { return sb_ice_reach(nx, ny, k, x0, y); });
+    }
+    if (cmd[0] == 'b') {
+        if (!ints(p, v, 6) || v[0] < 1 || v[1] < 1) return 1;
+        const int nx = v[0], k = v[5];
+        int inc = 1;
+        if (P && !ints(p, &inc, 1)) return 1;
+        const SbBandIcePlan pl = sb_band_ice_plan(nx, v[1], v[2], v[3] != 0, v[4] != 0, k, inc);
+        if (P) {
+            if (!pl.ok) std::printf("%s NONE\n", label);
+            else
+                std::printf("%s %s %d %d %d %d %d %d\n", label, path_name(pl.path), pl.rows.f0, pl.rows.nys, pl.rows.r0, pl.rows.r1,
+                            pl.nw, pl.marks.tiles);
+            return 0;
+        }
+        if (!pl.ok) return 1;
+        const int r0 = pl.rows.r0, r1 = pl.rows.r1;
+        return print_marks(label, p, nx, pl.rows.nys, pl.marks, false,
+                           [=](int x0, int s) { return sb_band_ice_reach(nx, r0, r1, k, x0, s); });
+    }
+    if (!ints(p, v, 2)) return 1;
+    const int nx = v[0], ny = v[1];
+    if (P) {
+        if (!ints(p, v, 5)) return 1;
+        const SbUmIcePlan pl = sb_um_ice_plan(nx, ny, v[0], v[1], v[2], v[3], v[4]);
+        if (!pl.ok) std::printf("%s NONE\n", label);
+        else std::printf("%s %s %d %d %d\n", label, path_name(pl.path), pl.nw, pl.marks.rows, pl.marks.tiles);
+        return pl.ok && pl.path != sb_um_ice_path(v[4]) ? 3 : 0;
+    }
+    if (!ints(p, v, 2) || nx < 1 || ny < 1) return 1;
+    const int wi = v[0], wj = v[1];
+    return print_marks(label, p, nx, ny, sb_um_ice_marks(nx, ny), true, [=](int x0, int y) { return sb_um_ice_reach(nx, ny, wi, wj, x0, y); });
+}
+
 }  // namespace
 
 int main() {
@@ -147,6 +260,8 @@ int main() {
                                (const void *)(uintptr_t)v[6], (const void *)(uintptr_t)v[7], (const void *)(uintptr_t)v[8]};
             std::printf("%s\n", why[(int)sb_tab_cache_decide(cache, key, (int)v[9])]);
             sb_tab_cache_filled(cache, key, (int)v[9]);
+        } else if (!std::strcmp(cmd, "ice") || !std::strcmp(cmd, "band_ice") || !std::strcmp(cmd, "um_ice")) {
+            if (const int rc = ice_line(cmd, rest)) return rc;
         } else if (!std::strcmp(cmd, "other")) sb_tab_cache_other_call(cache);
         else if (!std::strcmp(cmd, "failed")) sb_tab_cache_launch_failed(cache);
         else if (!std::strcmp(cmd, "toggled")) sb_tab_cache_toggled(cache);

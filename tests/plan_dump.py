@@ -1,5 +1,6 @@
-"""tests/plan_dump.cpp for the tests of seabreeze_param_amd/csrc/sb_diag_plan.hpp and sb_table_cache.hpp: built host-only with
-the compiler that builds the library, once per session; the lines it reads and the sections of the lines it prints.
+"""tests/plan_dump.cpp for the tests of seabreeze_param_amd/csrc/sb_diag_plan.hpp, sb_table_cache.hpp and sb_ice_plan.hpp: built
+host-only with the compiler that builds the library, once per session; the lines it reads and the sections of the lines it
+prints.
 
 A plan's line is  label | contrast | steps | kept | guard | guard tail;  `parse` gives the five sections behind the label,
 the steps as a list.  The domain is 200 x 96 cells, k_scan runs 12 workgroups there.
@@ -57,6 +58,18 @@ def switches_line(label, **kw):
 def run(exe, lines):
     """-> the lines the program prints (one for every `plan`, `switches`, `call` and `word`)"""
     return subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+
+
+def ice_dump(tmp_path_factory, layout):
+    """-> run(lines) over the `layout` lines ("ice", "band_ice", "um_ice": sb_ice_plan.hpp) of the program: it takes P and M
+    lines without the layout's word and gives {label: [the fields behind the label]}"""
+    exe = build(tmp_path_factory)
+
+    def run_layout(lines):
+        res = {ln.split()[0]: ln.split()[1:] for ln in run(exe, [f"{layout} {ln}" for ln in lines])}
+        assert len(res) == len(lines)
+        return res
+    return run_layout
 
 
 def parse(ln):

@@ -1,26 +1,21 @@
 """What an ice call of a latitude band decides on the host (seabreeze_param_amd/csrc/sb_ice_plan.hpp): whether the band has
 a plan at all (a cut side needs the (k+1)-th ghost row), which path it takes, and which (own row, 256-column tile) pairs a
-changed word of the band's coast bit plane marks -- the same sb_band_ice_reach that k_edge_bits_delta_band marks with on the
-device.
+changed word of the band's coast bit plane marks -- the same sb_band_ice_reach that k_edge_bits_delta's band instance marks
+with on the device.
 
-tests/band_ice_plan_dump.cpp is built host-only with the compiler that builds the library.  The expectation is a numpy
+tests/plan_dump.cpp (its `band_ice` lines) is built host-only with the compiler that builds the library.  The expectation is a numpy
 brute force over the distance kernels' window rule seen from a band (tests/band_ice_ref.py): every pair it finds must be
 marked (under-marking would leave a stale distance), and no mark may lie outside rows +-k and the tile columns covering
 +-(k + 63) of a changed cell (the cap is a condition of the design -- a word is 64 cells --, not a measurement).  Every word
 of every source row is walked, once through its first cell and once through its last, for the shapes of
 tests/test_band_ice_gpu.py.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import band_ice_ref
+import plan_dump
 from band_frames import cuts_of
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 #        id              nx  kwin halo  band heights
 CASES = [("BITS32",      320, 15, 16, (33, 33, 33)),
@@ -30,25 +25,13 @@ CASES = [("BITS32",      320, 15, 16, (33, 33, 33)),
          ("BYTES",        24, 15, 16, (17, 21, 19)),
          ("WIDE",        320, 40, 41, (50, 50, 50)),
          ("WIDE-odd",    320, 40, 41, (49, 51, 50)),
-         ("BITS32-700",  700, 15, 16, (33, 33, 33))]
+         ("BITS32-700",  700, 15, 16, (33, 33, 33)),
+         ("SMALL-70",     70, 15, 16, (33, 33, 33))]
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/band_ice_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "band_ice_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "band_ice_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: [fields]}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {ln.split()[0]: ln.split()[1:] for ln in out.splitlines()}
-        assert len(res) == len(lines)
-        return res
-    return run
+    return plan_dump.ice_dump(tmp_path_factory, "band_ice")
 
 
 def _plan(dump, nx, ny, halo, south, north, k, inc=1):

@@ -1,41 +1,24 @@
 """What an ice call of a stream decides on the host (seabreeze_param_amd/csrc/sb_ice_plan.hpp): which path it takes, and
 which (target row, 256-column tile) pairs a changed word of the coast bit plane marks -- the same sb_ice_reach that
-k_edge_bits_delta marks with on the device.
+k_edge_bits_delta's whole-grid instance marks with on the device.
 
-tests/ice_plan_dump.cpp is built host-only with the compiler that builds the library.  The expectation is a numpy brute
+tests/plan_dump.cpp (its `ice` lines) is built host-only with the compiler that builds the library.  The expectation is a numpy brute
 force over the distance kernels' window rule (tests/ice_ref.py): every pair it finds must be marked (under-marking would
 leave a stale distance), and no mark may lie outside rows +-k and the tile columns covering +-(k + 63) of a changed cell
 (the cap is a condition of the design -- a word is 64 cells --, not a measurement).
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import ice_ref
+import plan_dump
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRIDS = [(330, 40, 6), (200, 40, 6), (330, 60, 20), (700, 100, 40), (70, 40, 31), (24, 20, 15)]
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/ice_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "ice_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "ice_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: [fields]}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {ln.split()[0]: ln.split()[1:] for ln in out.splitlines()}
-        assert len(res) == len(lines)
-        return res
-    return run
+    return plan_dump.ice_dump(tmp_path_factory, "ice")
 
 
 def _cases(nx, ny, k):

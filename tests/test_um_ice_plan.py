@@ -1,23 +1,18 @@
 """What an ice call of the UM layout decides on the host (seabreeze_param_amd/csrc/sb_ice_plan.hpp): which path it takes,
 the sizes of its planes, and which workgroups of the UM distance kernels (4 rows x 64 columns) a changed word of the coast
-bit plane marks -- the same sb_um_ice_reach that k_edge_bits_delta_um marks with on the device.
+bit plane marks -- the same sb_um_ice_reach that k_edge_bits_delta's UM instance marks with on the device.
 
-tests/um_ice_plan_dump.cpp is built host-only with the compiler that builds the library.  Every word (x0, y) of every case
+tests/plan_dump.cpp (its `um_ice` lines) is built host-only with the compiler that builds the library.  Every word (x0, y) of every case
 is walked.  Lower bound: a brute force over targets (tests/um_ice_ref.py) -- every target whose window holds a cell of the
 word lies in a marked workgroup; under-marking would leave a stale distance.  Upper bound: no marked workgroup lies wholly
 outside rows y-wj-3 .. y+wj+3 and columns x0-wi-63 .. x0+63+wi+63 (whole words, whole row groups, whole tiles: a condition
 of the design, not a measurement).  A copy of the rule narrowed on purpose is caught by the lower bound.
 """
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import plan_dump
 import um_ice_ref as uir
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 #         nx   ny   wi   wj
 CASES = [(200, 70, 0, 0), (200, 70, 7, 3), (200, 70, 15, 15), (200, 70, 40, 33), (130, 37, 255, 255), (64, 4, 15, 15),
@@ -27,20 +22,7 @@ IDS = ["%dx%d-%d-%d" % c for c in CASES]
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    cxx = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not (shutil.which(cxx) or os.path.exists(cxx)):
-        pytest.skip("no hipcc to build tests/um_ice_plan_dump.cpp with")
-    exe = str(tmp_path_factory.mktemp("plan") / "um_ice_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-Wall", "-x", "c++", os.path.join(ROOT, "tests", "um_ice_plan_dump.cpp"), "-o", exe],
-                   check=True)
-
-    def run(lines):
-        """-> {label: [fields]}"""
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        res = {ln.split()[0]: ln.split()[1:] for ln in out.splitlines()}
-        assert len(res) == len(lines)
-        return res
-    return run
+    return plan_dump.ice_dump(tmp_path_factory, "um_ice")
 
 
 def _word_cells(nx, x0, y):
