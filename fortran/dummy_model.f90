@@ -27,6 +27,12 @@
 !                                every seabreeze_diag_um.  Step s ices (0.6) the sea cells of the sub-domain that touch
 !                                land and whose row j has mod(j + s, 3) == 0.  output.bin: per step the distance field on
 !                                tdims_l (ghost cells the edge cells, filled here), then sb_con windspeed winddir thc
+!     umtile                     um2d's sub-domain cut into 2 x 2 tiles, as a host model on a 2-D decomposition holds it: every
+!                                tile's frames (halo_size + 4 ghost cells) are copied out of the whole fields, in the role of
+!                                swap_bounds; tile_get_edges_um (ext = the window) and tile_get_dist_um (window +-(halo_size
+!                                + 3) cells) per tile, reassembled and compared with the whole-domain get_edges_um ->
+!                                get_dist_um_win; prints the number of differing cells and the largest difference.  No steps
+!                                are run; output.bin holds the whole-domain distance field (interior) and the reassembled one
 !     host                       the reference's call shape: host arrays in, host arrays out (default)
 !     dev                        the fields live on the device (sb_dev_alloc); per step only theta, u, v go up
 !                                and the four outputs come back; seabreeze_diag_dev
@@ -76,7 +82,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | um2dice | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | um2dice | umtile | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -123,6 +129,8 @@ program dummy_model
     call run_um2d()
   case ('um2dice')
     call run_um2dice()
+  case ('umtile')
+    call run_umtile()
   case ('status')
     call check_status()
   case ('bandsetup')
@@ -477,6 +485,70 @@ contains
     sb_con = 0.
     sb_con(1+hl:nx-hl, 1+hl:ny-hl) = sb_i
   end subroutine run_um2dice
+
+  !---------------------------------------------------------------------------
+  ! The UM-layout coast setup on a 2-D decomposition: the sub-domain and coordinates of run_um2d, window +-hl cells.  The
+  ! whole-domain pair runs on a layout of hl + 1 ghost cells (so that get_dist_um_win takes the kernel the tile call shares:
+  ! the fields are then equal to the last bit).  The domain is cut 2 x 2; a tile's frames of ht = hl + 1 ghost cells are
+  ! copied from the whole fields -- a neighbour's cells where the domain goes on, the edge cells beyond the domain's edge, as
+  ! get_edges_um pads them -- which is what swap_bounds leaves on a real run.  Every rank then forms the coast of its interior
+  ! and of the hl ghost cells its window reads, and the distance of its interior.
+  !---------------------------------------------------------------------------
+  subroutine run_umtile()
+    use sea_breeze_diag_mod, only : get_edges_um, get_dist_um_win, tile_get_edges_um, tile_get_dist_um, &
+                                    SB_TILE_WEST, SB_TILE_EAST, SB_TILE_SOUTH, SB_TILE_NORTH
+    integer :: hl, ht, nxi, nyi, i, j, ti, tj, x0, x1, y0, y1, nxt, nyt, sides, gi, gj, ndiff
+    integer :: xcut(3), ycut(3)
+    real :: dmax
+    real, allocatable :: lf_i(:,:), ci_i(:,:), tlat(:,:), tlon(:,:), whole_l(:,:), tiled(:,:)
+    real, allocatable :: lf_t(:,:), ci_t(:,:), lat_t(:,:), lon_t(:,:), coast_t(:,:)
+    hl = halo_size + 3; ht = hl + 1
+    nxi = nx - 2*hl; nyi = ny - 2*hl
+    if (nxi < 2 .or. nyi < 2) error stop 'umtile mode: grid too small for the ghost frame'
+    allocate(lf_i(nxi,nyi), ci_i(nxi,nyi), tlat(nxi,nyi), tlon(nxi,nyi), whole_l(nxi+2*ht,nyi+2*ht), tiled(nxi,nyi))
+    lf_i = land_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    ci_i = ice_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    do j = 1, nyi
+      tlon(:, j) = lon(1+hl:nx-hl)
+    end do
+    do i = 1, nxi
+      tlat(i, :) = lat(1+hl:ny-hl)
+    end do
+    whole_l = 0.
+    call get_edges_um(whole_l, ci_i, lf_i)
+    call get_dist_um_win(lf_i, whole_l, tlat, tlon, hl, hl)
+    xcut = [0, nxi/2, nxi]; ycut = [0, nyi/2, nyi]
+    tiled = -1.
+    do tj = 1, 2
+      do ti = 1, 2
+        x0 = xcut(ti); x1 = xcut(ti+1); y0 = ycut(tj); y1 = ycut(tj+1)
+        nxt = x1 - x0; nyt = y1 - y0
+        sides = 0
+        if (ti == 1) sides = sides + SB_TILE_WEST
+        if (ti == 2) sides = sides + SB_TILE_EAST
+        if (tj == 1) sides = sides + SB_TILE_SOUTH
+        if (tj == 2) sides = sides + SB_TILE_NORTH
+        allocate(lf_t(nxt+2*ht,nyt+2*ht), ci_t(nxt+2*ht,nyt+2*ht), lat_t(nxt+2*ht,nyt+2*ht), lon_t(nxt+2*ht,nyt+2*ht))
+        allocate(coast_t(nxt+2*ht,nyt+2*ht))
+        do j = 1, nyt + 2*ht                       ! in the role of swap_bounds
+          do i = 1, nxt + 2*ht
+            gi = min(max(x0 + i - ht, 1), nxi); gj = min(max(y0 + j - ht, 1), nyi)
+            lf_t(i, j) = lf_i(gi, gj); ci_t(i, j) = ci_i(gi, gj)
+            lat_t(i, j) = tlat(gi, gj); lon_t(i, j) = tlon(gi, gj)
+          end do
+        end do
+        coast_t = 0.
+        call tile_get_edges_um(lf_t, ci_t, coast_t, ht, ht, hl, hl, sides)
+        call tile_get_dist_um(lf_t, coast_t, lat_t, lon_t, ht, ht, hl, hl, sides)
+        tiled(x0+1:x1, y0+1:y1) = coast_t(1+ht:nxt+ht, 1+ht:nyt+ht)
+        deallocate(lf_t, ci_t, lat_t, lon_t, coast_t)
+      end do
+    end do
+    ndiff = count(tiled /= whole_l(1+ht:nxi+ht, 1+ht:nyi+ht))
+    dmax = maxval(abs(tiled - whole_l(1+ht:nxi+ht, 1+ht:nyi+ht)))
+    print '(a,1x,i0,1x,a,1x,es12.5)', 'umtile: differing cells', ndiff, 'largest difference', dmax
+    write (uout) whole_l(1+ht:nxi+ht, 1+ht:nyi+ht), tiled
+  end subroutine run_umtile
 
   !---------------------------------------------------------------------------
   ! Argument checks of the status-returning entry points: they answer error = 1 before any device work

@@ -42,6 +42,7 @@ module sea_breeze_diag_mod
   public :: band_seabreeze_diag, seabreeze_diag_dev, band_seabreeze_diag_dev
   public :: seabreeze_diag_um, SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK
   public :: get_edges_um, get_dist_um, get_dist_um_win
+  public :: tile_get_edges_um, tile_get_dist_um, SB_TILE_WEST, SB_TILE_EAST, SB_TILE_SOUTH, SB_TILE_NORTH
   public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
   public :: band_coast_open, band_ice_dev, band_ice_report, band_coast_close
   public :: um_coast_open, um_ice, um_ice_dev, um_ice_report, um_coast_close
@@ -61,6 +62,8 @@ module sea_breeze_diag_mod
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f64"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f64"
 #define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f64"
+#define SB_TILE_GET_EDGES_UM "sb_tile_get_edges_um_f64"
+#define SB_TILE_GET_DIST_UM  "sb_tile_get_dist_um_f64"
 #define SB_BAND_GET_EDGES "sb_band_get_edges_f64"
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f64"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f64_dev"
@@ -85,6 +88,8 @@ module sea_breeze_diag_mod
 #define SB_GET_EDGES_UM   "sb_get_edges_um_f32"
 #define SB_GET_DIST_UM    "sb_get_dist_um_f32"
 #define SB_GET_DIST_UM_WIN "sb_get_dist_um_win_f32"
+#define SB_TILE_GET_EDGES_UM "sb_tile_get_edges_um_f32"
+#define SB_TILE_GET_DIST_UM  "sb_tile_get_dist_um_f32"
 #define SB_BAND_GET_EDGES "sb_band_get_edges_f32"
 #define SB_BAND_GET_DIST  "sb_band_get_dist_f32"
 #define SB_BAND_GET_EDGES_DEV "sb_band_get_edges_f32_dev"
@@ -99,6 +104,8 @@ module sea_breeze_diag_mod
 #endif
 
   integer(c_int), parameter :: SB_BND_GLOBAL = 1, SB_BND_HALO = 2
+  ! the sides of a tile that are the domain's edge (tile_get_edges_um, tile_get_dist_um; include/seabreeze_hip.h: SB_TILE_*)
+  integer, parameter :: SB_TILE_WEST = 1, SB_TILE_EAST = 2, SB_TILE_SOUTH = 4, SB_TILE_NORTH = 8
   integer(c_int), save :: um_shape(4) = 0     ! nx, ny, halo_i, halo_j of the open UM coast (um_coast_open)
 
   interface band_get_dist       ! (maxdist as a real or as the integer literal, like get_dist)
@@ -198,6 +205,23 @@ module sea_breeze_diag_mod
       import :: c_ptr, c_int, rk
       type(c_ptr), value :: ctx
       integer(c_int), value :: nx, ny, hi, hj, wi, wj
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
+      real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_tile_get_edges_um(ctx, nx, ny, hi, hj, ei, ej, sides, lf, ci, coast) &
+        bind(C, name=SB_TILE_GET_EDGES_UM)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj, ei, ej, sides
+      real(rk), intent(in) :: lf(*), ci(*)
+      real(rk), intent(inout) :: coast(*)
+    end function
+    integer(c_int) function c_tile_get_dist_um(ctx, nx, ny, hi, hj, wi, wj, sides, coast, lf, tlat, tlon, maxdist, cdist) &
+        bind(C, name=SB_TILE_GET_DIST_UM)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj, wi, wj, sides
       real(rk), value :: maxdist
       real(rk), intent(in) :: coast(*), lf(*), tlat(*), tlon(*)
       real(rk), intent(inout) :: cdist(*)
@@ -795,6 +819,56 @@ contains
     if (rc /= 0) call fail('get_dist_um_win', rc)
     deallocate(c2)
   end subroutine get_dist_um_win
+
+  !---------------------------------------------------------------------------
+  ! The UM-layout coast setup on one tile of a 2-D domain decomposition (include/seabreeze_hip.h: sb_tile_get_edges_um,
+  ! sb_tile_get_dist_um): every field is the rank's frame on tdims_l, (nx+2*halo_i, ny+2*halo_j), its ghost cells filled by
+  ! the caller's swap_bounds -- the coordinate frames included; all frames have one shape, so the halo widths are stated.
+  ! sides: a sum of SB_TILE_* (a set bit: that side is the domain's edge; a clear one: a cut).  tile_get_edges_um writes 0/1
+  ! into the interior of coast_l and ext_i ghost columns / ext_j ghost rows beyond it on every cut side (halo >= ext + 1
+  ! there), so a rank forms the coast of the ghost cells its window reads; tile_get_dist_um overwrites the interior of
+  ! coast_l with the signed distance, as get_dist_um does, its sources being the coast cells of the interior and of the
+  ! ghost cells within the window on every cut side (halo >= win there).  The interior equals the tile's cells of the
+  ! whole-domain get_edges_um + get_dist_um_win.
+  !---------------------------------------------------------------------------
+  subroutine tile_get_edges_um(landfrac_l, icefrac_l, coast_l, halo_i, halo_j, ext_i, ext_j, sides)
+    real, intent(in), contiguous :: landfrac_l(:,:), icefrac_l(:,:)
+    real, intent(inout), contiguous :: coast_l(:,:)
+    integer, intent(in) :: halo_i, halo_j, ext_i, ext_j, sides
+    integer(c_int) :: nx, ny, rc
+    nx = size(coast_l, 1) - 2*halo_i; ny = size(coast_l, 2) - 2*halo_j
+    if (any(shape(landfrac_l) /= shape(coast_l)) .or. any(shape(icefrac_l) /= shape(coast_l)) .or. nx < 1 .or. ny < 1) &
+      call fail('tile_get_edges_um: need landfrac_l, icefrac_l, coast_l (nx+2*halo_i, ny+2*halo_j)', 1_c_int)
+    call ensure_ctx()
+    rc = c_tile_get_edges_um(ctx, nx, ny, int(halo_i, c_int), int(halo_j, c_int), int(ext_i, c_int), int(ext_j, c_int), &
+                             int(sides, c_int), landfrac_l, icefrac_l, coast_l)
+    if (rc /= 0) call fail('tile_get_edges_um', rc)
+  end subroutine tile_get_edges_um
+
+  subroutine tile_get_dist_um(landfrac_l, coast_l, true_latitude_l, true_longitude_l, halo_i, halo_j, win_i, win_j, sides, &
+                              maxdist)
+    real, intent(in), contiguous :: landfrac_l(:,:), true_latitude_l(:,:), true_longitude_l(:,:)
+    real, intent(inout), contiguous :: coast_l(:,:)
+    integer, intent(in) :: halo_i, halo_j, win_i, win_j, sides
+    real, intent(in), optional :: maxdist
+    real, allocatable :: c2(:,:)
+    real :: md
+    integer(c_int) :: nx, ny, rc
+    nx = size(coast_l, 1) - 2*halo_i; ny = size(coast_l, 2) - 2*halo_j
+    if (any(shape(landfrac_l) /= shape(coast_l)) .or. any(shape(true_latitude_l) /= shape(coast_l)) .or. &
+        any(shape(true_longitude_l) /= shape(coast_l)) .or. nx < 1 .or. ny < 1) &
+      call fail('tile_get_dist_um: need landfrac_l, coast_l, true_latitude_l, true_longitude_l (nx+2*halo_i, ny+2*halo_j)', &
+                1_c_int)
+    md = 180.
+    if (present(maxdist)) md = maxdist
+    allocate(c2(size(coast_l, 1), size(coast_l, 2)))
+    c2 = coast_l                                 ! (the coast mask the distance field replaces)
+    call ensure_ctx()
+    rc = c_tile_get_dist_um(ctx, nx, ny, int(halo_i, c_int), int(halo_j, c_int), int(win_i, c_int), int(win_j, c_int), &
+                            int(sides, c_int), c2, landfrac_l, true_latitude_l, true_longitude_l, real(md, rk), coast_l)
+    if (rc /= 0) call fail('tile_get_dist_um', rc)
+    deallocate(c2)
+  end subroutine tile_get_dist_um
 
   !---------------------------------------------------------------------------
   ! A UM-layout coast that moves with the sea ice (include/seabreeze_hip.h: sb_um_coast_open): the UM rebuilds its mask

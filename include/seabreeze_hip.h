@@ -784,7 +784,8 @@ int sb_get_edges_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j,
 /* 0 <= halo_i, halo_j <= 31 (else SB_ERR_ARG).  Sources (coast > 0) and targets are  */
 /* interior cells only: the UM's scatter reaches into the halo but swap_bounds        */
 /* discards those writes (:584-598), so there is no wrap and no clamp, and on a       */
-/* multi-rank run every rank sees its own coast cells only.  Only the interior of     */
+/* multi-rank run every rank sees its own coast cells only (sb_tile_get_dist_um_*     */
+/* below gives a rank its cells of the whole-domain field).  Only the interior of     */
 /* cdist is written; its ghost cells are left to the caller's swap_bounds /           */
 /* sb_fill_ghosts_*.  cdist == coast (in place, as the UM overwrites coast) works.    */
 /* Arithmetic in the working precision with the UM's constants R = 6370.9989,         */
@@ -853,6 +854,88 @@ int sb_get_dist_um_win_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo
                        const float *coast, const float *landfrac,
                        const float *true_lat, const float *true_lon,
                        float maxdist, float *cdist, void *stream);
+
+/* -------------------------------------------------------------------------------- */
+/* get_edges, get_dist -- UM layout, one tile of a 2-D domain decomposition           */
+/* The UM runs on a 2-D decomposition: every rank holds a rectangular tile on tdims_l */
+/* with ghost cells that swap_bounds fills.  sb_get_edges_um_* / sb_get_dist_um_win_* */
+/* follow the UM's text -- interior sources only -- so on such a run their field      */
+/* depends on how the domain was cut.  The tile calls give a rank its cells of the    */
+/* WHOLE-DOMAIN field from its own frame alone; the library exchanges nothing.        */
+/* Every field -- landfrac_l, icefrac_l, coast_l, cdist_l and the two coordinate      */
+/* frames true_lat_l, true_lon_l (degrees) -- is (nx+2*halo_i, ny+2*halo_j) with the  */
+/* tile's interior at (halo_i, halo_j).  The caller fills the ghost cells of the      */
+/* inputs once with its own swap_bounds (the coordinates are static).  sides: a sum   */
+/* of SB_TILE_* bits.  A side whose bit is set ends at the domain's edge: nothing     */
+/* beyond it is a source and nothing beyond it is written, which is what the          */
+/* whole-domain calls do at their rim.  A side whose bit is clear is a cut: the ghost */
+/* cells beyond it are a neighbour's cells.  (Where the domain ends inside the reach  */
+/* of a cut side -- a neighbour narrower than ext or the window -- the ghost cells    */
+/* beyond the domain are the caller's: coast_l must hold 0 there.)                    */
+/*                                                                                    */
+/* sb_tile_get_edges_um_*: the ice-aware rule and the Sobel of sb_get_edges_um_*;     */
+/* 0/1 goes into the interior of coast_l and into the ghost cells within ext_i        */
+/* columns / ext_j rows of it on every cut side, so a rank forms the coast of the     */
+/* ghost cells its distance window reads (ext = win) instead of receiving it.  Every  */
+/* other cell of coast_l is left untouched.  A cut side needs halo >= ext + 1 (the    */
+/* Sobel reads the ring one cell beyond the last cell it writes), an edge side        */
+/* halo >= 1, the ring sb_get_edges_um_* reads too.  coast_l must not overlap         */
+/* landfrac_l or icefrac_l.                                                           */
+/*                                                                                    */
+/* sb_tile_get_dist_um_*: sb_get_dist_um_win_*(win_i, win_j)'s rule with one change:  */
+/* sources are the coast cells (coast_l > 0) of the interior AND of the ghost cells    */
+/* within win_i columns / win_j rows on every cut side, their coordinates read from   */
+/* the coordinate frames.  Targets are interior cells only; only the interior of      */
+/* cdist_l is written; the sign is landfrac_l > 0 of the interior.  cdist_l == coast_l */
+/* works (the coast bit plane is formed in a launch of its own).  A cut side needs    */
+/* halo >= win; the window is 0 .. SB_DIST_UM_MAX_WINDOW each way.  The arithmetic is */
+/* always that of the wide kernel of sb_get_dist_um_win_*: both sines taken on the    */
+/* difference as written.  Whether a source is swept at or before a target is decided */
+/* on row and column differences, so the sweep-order reset survives the cut.          */
+/*                                                                                    */
+/* Result: the interior of cdist_l equals, bit for bit, the tile's cells of           */
+/* sb_get_edges_um_* followed by sb_get_dist_um_win_*(win_i, win_j) on the domain of  */
+/* which the frame is a cut-out -- same device, same precision -- wherever that call  */
+/* takes its wide kernel: any window that differs from its layout halo or exceeds 31. */
+/* Against a whole-domain call with win == halo <= 31 (sb_get_dist_um_*'s kernel) the  */
+/* fields differ by the two kernels' documented difference: up to 1e-12 relative in   */
+/* double, 2e-6 in single precision.  All four bits set is the whole domain.          */
+/* SB_ERR_ARG, with nothing enqueued and nothing written: bad sizes, sides outside    */
+/* 0 .. 15, ext or win negative or beyond 255, a halo too small as stated above, NULL, */
+/* coast_l overlapping an input of the edges call.                                    */
+/* The _dev forms take device pointers for every field and enqueue on `stream` (NULL: */
+/* the context's own): one kernel (edges), two (distance).  They do not synchronise,  */
+/* download or derive anything on the host.  Not served: a tile that follows moving   */
+/* sea ice (sb_um_ice_* keeps its interior-only rule), and the exchange itself.       */
+/* -------------------------------------------------------------------------------- */
+#define SB_TILE_WEST 1   /* the tile's first column is the domain's first column */
+#define SB_TILE_EAST 2   /* the tile's last column is the domain's last column */
+#define SB_TILE_SOUTH 4  /* the tile's first row is the domain's first row */
+#define SB_TILE_NORTH 8  /* the tile's last row is the domain's last row */
+int sb_tile_get_edges_um_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int ext_i, int ext_j, int sides,
+                       const double *landfrac_l, const double *icefrac_l, double *coast_l);
+int sb_tile_get_edges_um_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int ext_i, int ext_j, int sides,
+                       const float *landfrac_l, const float *icefrac_l, float *coast_l);
+int sb_tile_get_edges_um_f64_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int ext_i, int ext_j, int sides,
+                       const double *landfrac_l, const double *icefrac_l, double *coast_l, void *stream);
+int sb_tile_get_edges_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int ext_i, int ext_j, int sides,
+                       const float *landfrac_l, const float *icefrac_l, float *coast_l, void *stream);
+int sb_tile_get_dist_um_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, int sides,
+                       const double *coast_l, const double *landfrac_l,
+                       const double *true_lat_l, const double *true_lon_l,
+                       double maxdist, double *cdist_l);
+int sb_tile_get_dist_um_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, int sides,
+                       const float *coast_l, const float *landfrac_l,
+                       const float *true_lat_l, const float *true_lon_l,
+                       float maxdist, float *cdist_l);
+int sb_tile_get_dist_um_f64_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, int sides,
+                       const double *coast_l, const double *landfrac_l,
+                       const double *true_lat_l, const double *true_lon_l,
+                       double maxdist, double *cdist_l, void *stream);
+int sb_tile_get_dist_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, int sides,
+                       const float *coast_l, const float *landfrac_l,
+                       const float *true_lat_l, const float *true_lon_l,
+                       float maxdist, float *cdist_l, void *stream);
 
 /* -------------------------------------------------------------------------------- */
 /* a UM-layout coast that moves with the sea ice -- get_edges_um + get_dist_um_win,   */

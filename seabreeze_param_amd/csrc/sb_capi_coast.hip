@@ -1,5 +1,6 @@
 // sb_capi_coast.hip -- the coast setup of the C ABI: get_edges and get_dist on the whole grid, on one latitude band and in
-// the UM layout, a band's and a UM-layout coast that move with the sea ice, and search_radius.
+// the UM layout and on one tile of its 2-D decomposition, a band's and a UM-layout coast that move with the sea ice, and
+// search_radius.
 #include "sb_ctx.hpp"
 #include "sb_ice_plan.hpp"
 
@@ -499,6 +500,104 @@ int get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, const T *coast, 
     return get_dist_um_win_host<T>(c, nx, ny, hi, hj, hi, hj, coast, lf, tlat, tlon, maxdist, cdist);
 }
 
+// ---- one tile of a 2-D domain decomposition (sb_tile_get_edges_um_*, sb_tile_get_dist_um_*) ----
+// Every field is the rank's frame, (nx + 2hi) x (ny + 2hj) with the interior at (hi, hj), ghost cells filled by the caller's
+// swap_bounds; a set bit of `sides` says that side is the domain's edge.  `reach` is ext (edges: what is written beyond the
+// interior on a cut side; the Sobel reads one cell more) or the window (distance: what is read), `ring` that one cell more.
+int check_tile_um(sb_ctx *c, const char *what, int nx, int ny, int hi, int hj, int ri, int rj, int sides, int ring) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    const std::string w(what);
+    if (nx < 1 || ny < 1 || hi < 0 || hj < 0) return fail(c, SB_ERR_ARG, "bad " + w + " arguments");
+    if (sides < 0 || sides > 15) return fail(c, SB_ERR_ARG, w + ": sides must be a sum of SB_TILE_* bits, 0 .. 15");
+    if (ri < 0 || rj < 0 || ri > SB_DIST_UM_MAX_WINDOW || rj > SB_DIST_UM_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, w + ": ext / win must be 0 .. SB_DIST_UM_MAX_WINDOW = " + std::to_string(SB_DIST_UM_MAX_WINDOW));
+    if ((double)(nx + 2.0 * hi) * (double)(ny + 2.0 * hj) > 2.0e9) return fail(c, SB_ERR_ARG, "grid too large");
+    const bool cut_i = !(sides & SB_TILE_WEST) || !(sides & SB_TILE_EAST), cut_j = !(sides & SB_TILE_SOUTH) || !(sides & SB_TILE_NORTH);
+    const int need_i = cut_i ? ri + ring : ring, need_j = cut_j ? rj + ring : ring;
+    if (hi < need_i || hj < need_j)
+        return fail(c, SB_ERR_ARG, w + ": the halo " + std::to_string(hi) + " x " + std::to_string(hj) + " is smaller than " +
+                                       std::to_string(need_i) + " x " + std::to_string(need_j) +
+                                       (ring ? " (ext + 1 on a cut side, 1 on an edge side: the Sobel reads the ring beyond what it writes)"
+                                             : " (the window on a cut side: its ghost cells are sources)"));
+    return SB_OK;
+}
+
+inline bool overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+template <typename T>
+int check_tile_edges_um(sb_ctx *c, int nx, int ny, int hi, int hj, int ei, int ej, int sides, const T *lf, const T *ci, const T *coast) {
+    int rc = check_tile_um(c, "tile_get_edges_um", nx, ny, hi, hj, ei, ej, sides, 1);
+    if (rc) return rc;
+    if (!lf || !ci || !coast) return fail(c, SB_ERR_ARG, "tile_get_edges_um: null array pointer");
+    const size_t nb = (size_t)(nx + 2 * hi) * (ny + 2 * hj) * sizeof(T);
+    if (overlap(coast, lf, nb) || overlap(coast, ci, nb))
+        return fail(c, SB_ERR_ARG, "tile_get_edges_um: coast_l overlaps an input (the Sobel of a cell reads its neighbours' flags)");
+    return SB_OK;
+}
+
+template <typename T>
+int tile_get_edges_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int ei, int ej, int sides, const T *lf, const T *ci, T *coast,
+                          void *stream) {
+    int rc = check_tile_edges_um<T>(c, nx, ny, hi, hj, ei, ej, sides, lf, ci, coast);
+    if (rc) return rc;
+    HIPCHK(c, sb_launch_edges_um_tile<T>(lf, ci, coast, nx, ny, hi, hj, ei, ej, sides, stream_of(c, stream)));
+    return SB_OK;
+}
+
+template <typename T>
+int tile_get_edges_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, int ei, int ej, int sides, const T *lf, const T *ci, T *coast) {
+    int rc = check_tile_edges_um<T>(c, nx, ny, hi, hj, ei, ej, sides, lf, ci, coast);
+    if (rc) return rc;
+    const size_t n = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    Stager s(c);
+    T *dl = s.in(lf, n), *dc = s.in(ci, n), *dco = s.in((const T *)coast, n);   // (coast in as well: the cells not written stay)
+    if (s.rc) return s.rc;
+    rc = tile_get_edges_um_dev<T>(c, nx, ny, hi, hj, ei, ej, sides, dl, dc, dco, nullptr);
+    if (rc) return rc;
+    s.back(coast, dco, n);
+    return s.finish();
+}
+
+template <typename T>
+int check_tile_dist_um(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, int sides, const T *coast, const T *lf,
+                       const T *tlat, const T *tlon, const T *cdist) {
+    int rc = check_tile_um(c, "tile_get_dist_um", nx, ny, hi, hj, wi, wj, sides, 0);
+    if (rc) return rc;
+    if (!coast || !lf || !tlat || !tlon || !cdist) return fail(c, SB_ERR_ARG, "tile_get_dist_um: null array pointer");
+    return SB_OK;
+}
+
+template <typename T>
+int tile_get_dist_um_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, int sides, const T *coast, const T *lf,
+                         const T *tlat, const T *tlon, T maxdist, T *cdist, void *stream) {
+    int rc = check_tile_dist_um<T>(c, nx, ny, hi, hj, wi, wj, sides, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    // the coordinates are device frames: nothing is derived from them on the host, nothing is kept between calls
+    if ((rc = ensure(c, c->umbits, sb_dist_um_tile_bits_bytes(nx, ny, wi, wj, sides)))) return rc;
+    HIPCHK(c, sb_launch_dist_um_tile<T>(coast, lf, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, sides, maxdist, (uint64_t *)c->umbits.p,
+                                        stream_of(c, stream)));
+    return SB_OK;
+}
+
+template <typename T>
+int tile_get_dist_um_host(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, int sides, const T *coast, const T *lf,
+                          const T *tlat, const T *tlon, T maxdist, T *cdist) {
+    int rc = check_tile_dist_um<T>(c, nx, ny, hi, hj, wi, wj, sides, coast, lf, tlat, tlon, cdist);
+    if (rc) return rc;
+    const size_t n = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    Stager s(c);
+    // (cdist in as well: its ghost cells stay; with cdist == coast both copies hold the same field)
+    T *dco = s.in(coast, n), *dl = s.in(lf, n), *dla = s.in(tlat, n), *dlo = s.in(tlon, n), *dcd = s.in((const T *)cdist, n);
+    if (s.rc) return s.rc;
+    rc = tile_get_dist_um_dev<T>(c, nx, ny, hi, hj, wi, wj, sides, dco, dl, dla, dlo, maxdist, dcd, nullptr);
+    if (rc) return rc;
+    s.back(cdist, dcd, n);
+    return s.finish();
+}
+
 // ---- a UM-layout coast that moves with the sea ice (sb_um_coast_open_*, sb_um_ice_*) ----
 // The UM rebuilds its mask from icefrac inside the timestep routine (ref: UM/vn10.7/sea_breeze_diag.F90:384-445), so
 // get_edges_um + get_dist_um_win per timestep cost the whole interior again.  Here the context keeps the interior's coast
@@ -729,6 +828,24 @@ int sb_um_coast_close(sb_ctx *c) {
                                        const T *lf, const T *tlat, const T *tlon, T maxdist, T *cdist,              \
                                        void *stream) {                                                              \
         return get_dist_um_win_dev<T>(c, nx, ny, hi, hj, wi, wj, coast, lf, tlat, tlon, maxdist, cdist, stream);    \
+    }                                                                                                              \
+    int sb_tile_get_edges_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int ei, int ej, int sides, const T *lf, \
+                                   const T *ci, T *coast) {                                                        \
+        return tile_get_edges_um_host<T>(c, nx, ny, hi, hj, ei, ej, sides, lf, ci, coast);                         \
+    }                                                                                                              \
+    int sb_tile_get_edges_um_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int ei, int ej, int sides,      \
+                                         const T *lf, const T *ci, T *coast, void *stream) {                       \
+        return tile_get_edges_um_dev<T>(c, nx, ny, hi, hj, ei, ej, sides, lf, ci, coast, stream);                  \
+    }                                                                                                              \
+    int sb_tile_get_dist_um_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, int sides,            \
+                                  const T *coast, const T *lf, const T *tlat, const T *tlon, T maxdist, T *cdist) { \
+        return tile_get_dist_um_host<T>(c, nx, ny, hi, hj, wi, wj, sides, coast, lf, tlat, tlon, maxdist, cdist);  \
+    }                                                                                                              \
+    int sb_tile_get_dist_um_##SFX##_dev(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, int sides,      \
+                                        const T *coast, const T *lf, const T *tlat, const T *tlon, T maxdist,      \
+                                        T *cdist, void *stream) {                                                  \
+        return tile_get_dist_um_dev<T>(c, nx, ny, hi, hj, wi, wj, sides, coast, lf, tlat, tlon, maxdist, cdist,    \
+                                       stream);                                                                    \
     }                                                                                                              \
     int sb_um_coast_open_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const T *tlat,            \
                                const T *tlon, T maxdist, int incremental) {                                         \

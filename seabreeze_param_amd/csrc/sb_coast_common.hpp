@@ -1,6 +1,6 @@
 // sb_coast_common.hpp -- what the coast setup's kernels share: sb_coast_kernels.hip (regular grids: k_edges, k_dist,
 // k_dist_bits_small, k_dist_bits, k_dist_wide) and sb_um_coast_kernels.hip (the UM layout on curvilinear grids:
-// k_edges_um, k_dist_um, k_dist_um_wide) and sb_ice_kernels.hip (a moving coast: k_edge_bits_delta[_band|_um]).
+// k_edges_um, k_dist_um, k_dist_um_wide, k_edges_um_tile, k_dist_um_tile) and sb_ice_kernels.hip (a moving coast: k_edge_bits_delta[_band|_um]).
 // ref: sobel.f90:19-193, UM/vn10.7/sea_breeze_diag.F90:386-601
 // The Sobel block, the coast bit plane and its bit strings, the haversine term, the two forms of the epilogue (minimum a
 // per sweep class -> distance -> sweep-time reset -> sign) and the per-target walk of a window that fits one word.
@@ -148,6 +148,25 @@ struct EdgesUm {
         if (c <= T(0.2)) return (l >= T(0.5)) ? 1 : 0;            // ref: UM :390-396
         return (l + c >= T(0.5)) ? 1 : 0;                          // ref: UM :397-403
     }
+};
+
+// k_edges_um_tile's layout (one tile of a 2-D decomposition, sb_tile_get_edges_um_*): EdgesUm's rule on a written rectangle
+// that is not the interior -- it takes in `ext` ghost columns / rows on every cut side -- so the pitch ld and the rows NY of
+// the frame are stated apart from the rectangle's size (the kernel's nx, ny), and (ox, oy) is the frame cell of written cell
+// (0, 0).  The host holds ox, oy >= 1: the ring cell (-1, -1) lies inside the frame; cells past the ring are clamped into it
+// as EdgesUm clamps them.
+template <typename T>
+struct EdgesUmTile {
+    static constexpr bool tail_by_index = true;
+    int ld, NY, ox, oy;
+    __device__ __forceinline__ size_t src(int x, int y) const {
+        int X = x + ox, Y = y + oy;
+        X = X < ld ? X : ld - 1;
+        Y = Y < NY ? Y : NY - 1;
+        return (size_t)Y * ld + X;
+    }
+    __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + oy) * ld + x + ox; }
+    __device__ __forceinline__ int land(T l, T c) const { return EdgesUm<T>{}.land(l, c); }
 };
 
 // ---- the coast bit plane ----

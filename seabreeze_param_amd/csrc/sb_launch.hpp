@@ -228,6 +228,20 @@ template <typename T>
 hipError_t sb_launch_dist_um_win(const T *coast, const T *landfrac, const T *tlat, const T *tlon, T *cdist, int nx, int ny,
                                  int hi, int hj, int wi, int wj, T maxdist, uint64_t *bits, hipStream_t st);
 
+// One tile of a 2-D decomposition (sb_tile_get_edges_um_*, sb_tile_get_dist_um_*; sb_um_coast_kernels.hip).  Every field is
+// the tile's (nx + 2hi) x (ny + 2hj) frame (first cell); sides: SB_TILE_* bits, a set bit = that side is the domain's edge.
+// Edges: 0/1 into the interior and ei ghost columns / ej ghost rows on every cut side; hipErrorInvalidValue unless the halo
+// holds one cell more than is written on every side.  Distance: sources are the coast cells of the interior and of wi ghost
+// columns / wj ghost rows on every cut side (hipErrorInvalidValue unless the halo holds them), targets the interior; cdist_l
+// may be coast_l; bits: sb_dist_um_tile_bits_bytes of workspace.  k_dist_um_wide's arithmetic whatever the window.
+template <typename T>
+hipError_t sb_launch_edges_um_tile(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, int ei, int ej, int sides,
+                                   hipStream_t st);
+size_t sb_dist_um_tile_bits_bytes(int nx, int ny, int wi, int wj, int sides);
+template <typename T>
+hipError_t sb_launch_dist_um_tile(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
+                                  int ny, int hi, int hj, int wi, int wj, int sides, T maxdist, uint64_t *bits, hipStream_t st);
+
 // A UM-layout coast that moves with the sea ice (sb_um_ice_*; sb_ice_kernels.hip, sb_ice_plan.hpp).  lf, ci: the
 // (nx + 2hi) x (ny + 2hj) frames (first cell), hi, hj >= 1 (else hipErrorInvalidValue).  The interior's coast under the UM's
 // rule as bits, compared with and written into the context's UM bit plane (ny * ceil(nx/64) words); every workgroup of the

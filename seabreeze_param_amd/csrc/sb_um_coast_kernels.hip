@@ -8,6 +8,7 @@
 //                  rows, from per-cell coordinates     ref: UM/vn10.7/sea_breeze_diag.F90:448-601 (get_dist)
 //   k_dist_um_wide the same rule for a window of up to +-255 cells stated apart from the ghost width (sb_get_dist_um_win_*)
 //   k_dist_um_dirty, k_dist_um_wide_dirty  the two under DistUmDirty: only the workgroups an ice call marked (sb_um_ice_*)
+//   k_edges_um_tile, k_dist_um_tile  one tile of a 2-D decomposition: ghost cells in reach are sources (sb_tile_get_*_um_*)
 //
 // The UM's get_dist is a scatter from interior coast cells into a window that reaches into the halo; swap_bounds then
 // throws the halo writes away (:584-598).  So sources and targets are interior cells only -- no wrap, no clamp -- and
@@ -30,6 +31,9 @@ __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, cons
 // ---- which workgroups a UM distance launch computes, and where landfrac lies ----
 // A policy G, the body's last argument (the kernels are thin __global__ wrappers round um_dist_body / um_dist_wide_body, so
 // the whole-interior instances keep their names and are the kernels they were before the policy came):
+//   (src_row, src_rows, bit_col, co: the row of the coast bit plane a source row is and how many it has, the plane's column of
+//   a column, where a cell's coordinates lie -- the interior and nothing else under the first two policies, the expressions
+//   the body held before DistUmTile came)
 //   DistUmWhole  every workgroup computes; landfrac is an interior (nx, ny) field.  An empty type.
 //   DistUmDirty  the coast moves with the sea ice (sb_um_ice_*): a workgroup whose byte of the mark plane (one per
 //                SB_UM_ICE_ROWS-row group x 64-column tile, sb_ice_plan.hpp) is clear returns before any bit word, barrier or
@@ -39,6 +43,10 @@ __global__ __launch_bounds__(256) void k_edges_um(const T *__restrict__ lf, cons
 struct DistUmWhole {
     __device__ __forceinline__ bool skip(int, int) const { return false; }
     __device__ __forceinline__ size_t lf(int x, int y, int nx) const { return (size_t)y * nx + x; }
+    __device__ __forceinline__ int src_row(int ys) const { return ys; }
+    __device__ __forceinline__ int src_rows(int ny) const { return ny; }
+    __device__ __forceinline__ int bit_col(int p) const { return p; }
+    __device__ __forceinline__ size_t co(int x, int y, int nx) const { return (size_t)y * nx + x; }
 };
 struct DistUmDirty {
     const unsigned char *mark;
@@ -46,6 +54,28 @@ struct DistUmDirty {
     size_t off;
     __device__ __forceinline__ bool skip(int group, int tile) const { return mark[(size_t)group * ntiles + tile] == 0; }
     __device__ __forceinline__ size_t lf(int x, int y, int) const { return off + (size_t)y * ld + x; }
+    __device__ __forceinline__ int src_row(int ys) const { return ys; }
+    __device__ __forceinline__ int src_rows(int ny) const { return ny; }
+    __device__ __forceinline__ int bit_col(int p) const { return p; }
+    __device__ __forceinline__ size_t co(int x, int y, int nx) const { return (size_t)y * nx + x; }
+};
+// DistUmTile (k_dist_um_wide's body only): see k_dist_um_tile below.  landfrac and the coordinates are handed over at the
+// interior's first cell, so a cell is y * ld + x; the reach west, south and north (each <= SB_DIST_UM_MAX_WINDOW = 255; east:
+// the width of the bit plane says it) travels in one word, so two scalars are all the policy carries -- with them apart the
+// fp64 instance went beyond its scalar registers' spill lanes and took a private segment (20 bytes, never addressed).
+struct DistUmTile {
+    int e, ld;                                                   // e = eW | eS << 8 | eN << 16
+    __device__ __forceinline__ int eW() const { return e & 255; }
+    __device__ __forceinline__ int eS() const { return (e >> 8) & 255; }
+    __device__ __forceinline__ int eN() const { return e >> 16; }
+    __device__ __forceinline__ bool skip(int, int) const { return false; }
+    __device__ __forceinline__ size_t lf(int x, int y, int) const { return (size_t)y * ld + x; }
+    __device__ __forceinline__ int src_row(int ys) const { return ys + eS(); }
+    __device__ __forceinline__ int src_rows(int ny) const { return ny + eS() + eN(); }
+    __device__ __forceinline__ int bit_col(int p) const { return p + eW(); }
+    // (x, y may be negative: a ghost cell west or south of the interior; the offset is taken modulo 2^64 and the cell lies
+    // inside the frame)
+    __device__ __forceinline__ size_t co(int x, int y, int) const { return (size_t)y * ld + x; }
 };
 
 // The gather.  A workgroup holds UM_DIST_TY target rows of 64 columns (one wave per row).  Its reach is the
@@ -211,6 +241,7 @@ __global__ __launch_bounds__(64 * UM_DIST_TY) void k_dist_um_dirty(const uint64_
 #define UMW_WORDS ((UMW_SPAN + 63) / 64)
 #define UMW_CAP 1024                                             // entries of the compact source list
 #define UMW_SIN_POLY_MAX 0.5
+static_assert(SB_DIST_UM_MAX_WINDOW <= 255, "DistUmTile packs a reach into eight bits");
 static_assert(UMW_CAP >= UMW_SPAN, "k_dist_um_wide: a chunk holds at least one row");
 static_assert(UMW_CAP <= 65535 && UMW_SLOTS <= 64 * UMW_TY, "k_dist_um_wide: 16-bit list offsets, a thread per slot");
 
@@ -268,10 +299,10 @@ __device__ __forceinline__ void um_dist_wide_body(const uint64_t *__restrict__ b
         const int ns = j == 0 ? UMW_SLOTS : 2 * UMW_A;
         int anyv = 0;
         for (int i = tid; i < ns * UMW_WORDS; i += 64 * UMW_TY) {
-            const int s = i / UMW_WORDS, w = i - s * UMW_WORDS, ys = slot_row(s, j);
+            const int s = i / UMW_WORDS, w = i - s * UMW_WORDS, ys = g.src_row(slot_row(s, j));   // (row of the bit plane)
             uint64_t v = 0;
-            if (w < nws && slot_k(s, j) <= wj && ys >= 0 && ys < ny) {
-                v = um_row_bits64(bits + (size_t)ys * nw, x0 - wi + 64 * w, nw);
+            if (w < nws && slot_k(s, j) <= wj && ys >= 0 && ys < g.src_rows(ny)) {
+                v = um_row_bits64(bits + (size_t)ys * nw, g.bit_col(x0 - wi + 64 * w), nw);
                 if (w == nws - 1) v &= lastmask;
             }
             s_bw[s][w] = v;
@@ -286,7 +317,7 @@ __device__ __forceinline__ void um_dist_wide_body(const uint64_t *__restrict__ b
         if (!have) {                                             // the first coordinates this workgroup reads
             have = true;
             if (valid) {
-                const size_t o = (size_t)yy * nx + xx;
+                const size_t o = g.co(xx, yy, nx);
                 phit = tlat[o] * d2r;                            // phi1 (ref: UM :524)
                 const T lam1 = tlon[o] * d2r;                    // lam1 (:523)
                 l2 = ((r2d * lam1) > T(180.)) ? d2r * ((r2d * lam1) - T(360.)) : lam1;   // ref: UM :560-564
@@ -315,11 +346,11 @@ __device__ __forceinline__ void um_dist_wide_body(const uint64_t *__restrict__ b
                 uint64_t v = s_bw[s][w];
                 if (!v) continue;
                 int e = s_off[s][w];
-                const size_t orow = (size_t)slot_row(s, j) * nx;
+                const size_t orow = g.co(0, slot_row(s, j), nx);
                 while (v) {
                     const int b = __builtin_ctzll(v);
                     v &= v - 1ull;
-                    const size_t o = orow + (x0 - wi + 64 * w + b);      // (a set bit is an interior cell)
+                    const size_t o = orow + (x0 - wi + 64 * w + b);      // (a set bit is a source cell: interior, or under DistUmTile a ghost cell in reach)
                     const T lat = tlat[o], lon = tlon[o];
                     const T phis = lat * d2r;
                     s_phi[e] = phis;
@@ -382,6 +413,78 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_wide_dirty(const uint64
     um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
 }
 
+// ------------------------------------------------------------------------------------
+// One tile of a 2-D domain decomposition (sb_tile_get_edges_um_*, sb_tile_get_dist_um_*): every field is the rank's frame
+// of (nx + 2hi) x (ny + 2hj) cells with the interior at (hi, hj), ghost cells filled by the caller's swap_bounds.  A side
+// is a CUT (a neighbour's cells lie beyond it) or an EDGE of the domain (nothing beyond it is a source or is written).
+//   k_edges_um_tile  sb_edges_block under EdgesUmTile (sb_coast_common.hpp): the written rectangle is the interior and
+//                    `ext` ghost columns / rows on every cut side, so a rank forms the coast of its ghost cells itself;
+//   k_dist_um_tile   um_dist_wide_body under DistUmTile.  Sources are the coast cells of [-eW, nx+eE) x [-eS, ny+eN) in
+//                    interior coordinates, e* = the window on a cut side and 0 on an edge side: the plane's rows are the source rows
+//                    (src_row, src_rows: the test 0 <= ys < ny is taken on those), and the coast bit plane spans exactly that
+//                    rectangle (pitch nw words, origin (-eW, -eS): bit_col), so um_row_bits64's zeros beyond the plane are the column clip.  Targets are the
+//                    interior; coordinates and landfrac are read through the frame's pitch and offset (co, lf).  Whether a
+//                    source is swept at or before a target is decided on row and column DIFFERENCES (ii, 64 wd + b <=
+//                    qown), which a translation of the origin leaves alone: the sweep-order reset survives the cut.  No exit
+//                    is added (skip is false), LDS is the body's.
+// ------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_edges_um_tile(const T *__restrict__ lf, const T *__restrict__ ci, T *__restrict__ coast,
+                                                       int wx, int wy, EdgesUmTile<T> p) {
+    __shared__ unsigned char s_land[EDGE_LDS];
+    sb_edges_block(lf, ci, coast, s_land, wx, wy, p);
+}
+template <typename T>
+__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_tile(const uint64_t *__restrict__ bits, const T *__restrict__ landfrac,
+                                                              const T *__restrict__ tlat, const T *__restrict__ tlon,
+                                                              T *__restrict__ cdist, int nx, int ny, int hi, int hj, int wi,
+                                                              int wj, int nw, T maxdist, DistUmTile g) {
+    // (landfrac, tlat, tlon: the interior's first cell of their frames; cdist: the frame's first cell, as in k_dist_um_wide)
+    um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
+}
+
+// what a tile call reaches beyond its interior on each side: `e` cells on a cut side, none on an edge side
+struct SbTileReach { int eW, eE, eS, eN; };
+static inline SbTileReach sb_tile_reach(int sides, int ei, int ej) {
+    return SbTileReach{(sides & SB_TILE_WEST) ? 0 : ei, (sides & SB_TILE_EAST) ? 0 : ei, (sides & SB_TILE_SOUTH) ? 0 : ej,
+                       (sides & SB_TILE_NORTH) ? 0 : ej};
+}
+
+template <typename T>
+hipError_t sb_launch_edges_um_tile(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, int ei, int ej, int sides,
+                                   hipStream_t st) {
+    const SbTileReach r = sb_tile_reach(sides, ei, ej);
+    // the ring the Sobel reads lies inside the frame: one cell beyond the written rectangle on every side
+    if (ei < 0 || ej < 0 || hi < r.eW + 1 || hi < r.eE + 1 || hj < r.eS + 1 || hj < r.eN + 1) return hipErrorInvalidValue;
+    const int wx = nx + r.eW + r.eE, wy = ny + r.eS + r.eN;
+    const EdgesUmTile<T> p{nx + 2 * hi, ny + 2 * hj, hi - r.eW, hj - r.eS};
+    hipLaunchKernelGGL(k_edges_um_tile<T>, dim3((wx + 255) / 256, (wy + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lf, ci, coast,
+                       wx, wy, p);
+    return hipGetLastError();
+}
+
+size_t sb_dist_um_tile_bits_bytes(int nx, int ny, int wi, int wj, int sides) {
+    const SbTileReach r = sb_tile_reach(sides, wi, wj);
+    return (size_t)(ny + r.eS + r.eN) * ((nx + r.eW + r.eE + 63) / 64) * sizeof(uint64_t);
+}
+
+template <typename T>
+hipError_t sb_launch_dist_um_tile(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
+                                  int ny, int hi, int hj, int wi, int wj, int sides, T maxdist, uint64_t *bits, hipStream_t st) {
+    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
+    const SbTileReach r = sb_tile_reach(sides, wi, wj);
+    // every source cell lies inside the frame
+    if (hi < r.eW || hi < r.eE || hj < r.eS || hj < r.eN) return hipErrorInvalidValue;
+    const int wx = nx + r.eW + r.eE, wy = ny + r.eS + r.eN, nw = (wx + 63) / 64, NX = nx + 2 * hi;
+    // (two launches: the bit plane is complete before any cdist cell is written, so cdist_l may be coast_l)
+    sb_launch_coastbits<T>(coast_l, bits, wx, wy, nw, NX, (size_t)(hj - r.eS) * NX + (hi - r.eW), st);
+    const DistUmTile g{r.eW | (r.eS << 8) | (r.eN << 16), NX};
+    const size_t o = (size_t)hj * NX + hi;                       // the interior's first cell (cdist_l: the body adds it itself)
+    hipLaunchKernelGGL(k_dist_um_tile<T>, dim3((nx + 63) / 64, (ny + UMW_TY - 1) / UMW_TY), dim3(64 * UMW_TY), 0, st, bits,
+                       landfrac_l + o, tlat_l + o, tlon_l + o, cdist_l, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t sb_launch_edges_um(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, hipStream_t st) {
     hipLaunchKernelGGL(k_edges_um<T>, dim3((nx + 255) / 256, (ny + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st,
@@ -437,3 +540,12 @@ template hipError_t sb_launch_dist_um_win<float>(const float *, const float *, c
                                                  int, int, int, int, int, float, uint64_t *, hipStream_t);
 template hipError_t sb_launch_dist_um_win<double>(const double *, const double *, const double *, const double *, double *,
                                                   int, int, int, int, int, int, double, uint64_t *, hipStream_t);
+
+template hipError_t sb_launch_edges_um_tile<float>(const float *, const float *, float *, int, int, int, int, int, int, int,
+                                                   hipStream_t);
+template hipError_t sb_launch_edges_um_tile<double>(const double *, const double *, double *, int, int, int, int, int, int, int,
+                                                    hipStream_t);
+template hipError_t sb_launch_dist_um_tile<float>(const float *, const float *, const float *, const float *, float *, int, int,
+                                                  int, int, int, int, int, float, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um_tile<double>(const double *, const double *, const double *, const double *, double *, int,
+                                                   int, int, int, int, int, int, double, uint64_t *, hipStream_t);

@@ -21,6 +21,8 @@ SB_BND_WRAPPER, SB_BND_GLOBAL, SB_BND_HALO = 0, 1, 2
 SB_UM_THETA_TO_T0, SB_UM_LEVEL_WALK = 1, 2
 SB_DIST_MAX_WINDOW = 255            # include/seabreeze_hip.h: the widest get_dist window (kwin, or the derived half-width)
 SB_DIST_UM_MAX_WINDOW = 255         # include/seabreeze_hip.h: the widest window of get_dist_um_win, each way
+# include/seabreeze_hip.h: the sides of a tile (tile_get_edges_um, tile_get_dist_um) that are the domain's edge
+SB_TILE_WEST, SB_TILE_EAST, SB_TILE_SOUTH, SB_TILE_NORTH = 1, 2, 4, 8
 
 _SFX = {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
 _CT = {np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double}
@@ -469,6 +471,50 @@ class Context:
         self._chk(rc, "sb_get_dist_um_win")
         return cdist
 
+    def tile_get_edges_um(self, landfrac_l, icefrac_l, halo_i, halo_j, ext_i, ext_j, sides, out=None):
+        """get_edges_um for one tile of a 2-D domain decomposition (include/seabreeze_hip.h: sb_tile_get_edges_um):
+        landfrac_l, icefrac_l are the tile's frames (ny + 2*halo_j, nx + 2*halo_i), ghost cells filled; sides is a sum of
+        SB_TILE_* (a set bit: that side is the domain's edge).  Returns coast on that frame with 0/1 in the interior and in
+        the ghost cells within ext_i columns / ext_j rows of it on every cut side (halo >= ext + 1 there); every other cell
+        is that of `out` (zeros without it)."""
+        landfrac_l = np.ascontiguousarray(landfrac_l)
+        dt = np.dtype(landfrac_l.dtype)
+        icefrac_l = _host(icefrac_l, dt)
+        ny, nx = landfrac_l.shape[0] - 2 * halo_j, landfrac_l.shape[1] - 2 * halo_i
+        if icefrac_l.shape != landfrac_l.shape:
+            raise ValueError("landfrac_l and icefrac_l must have the same shape")
+        coast = np.zeros_like(landfrac_l) if out is None else out
+        if coast.shape != landfrac_l.shape or coast.dtype != dt or not coast.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of the input's shape and dtype")
+        rc = getattr(self.lib, f"sb_tile_get_edges_um_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i),
+                                                                  C.c_int(halo_j), C.c_int(ext_i), C.c_int(ext_j),
+                                                                  C.c_int(sides), _p(landfrac_l), _p(icefrac_l), _p(coast))
+        self._chk(rc, "sb_tile_get_edges_um")
+        return coast
+
+    def tile_get_dist_um(self, coast_l, landfrac_l, true_lat_l, true_lon_l, halo_i, halo_j, win_i, win_j, sides,
+                         maxdist=180.0, out=None):
+        """get_dist_um_win for one tile of a 2-D domain decomposition (include/seabreeze_hip.h: sb_tile_get_dist_um): every
+        field is the tile's frame (ny + 2*halo_j, nx + 2*halo_i), the coordinates included; sources are the coast cells of
+        the interior and of the ghost cells within the window on every cut side (halo >= win there).  Returns the signed
+        distance on the frame: the interior is written -- the tile's cells of the whole-domain field -- the ghost cells are
+        those of `out` (zeros without it).  out may be coast_l itself."""
+        coast_l = np.ascontiguousarray(coast_l)
+        dt = np.dtype(coast_l.dtype)
+        landfrac_l = _host(landfrac_l, dt); true_lat_l = _host(true_lat_l, dt); true_lon_l = _host(true_lon_l, dt)
+        ny, nx = coast_l.shape[0] - 2 * halo_j, coast_l.shape[1] - 2 * halo_i
+        if halo_i < 0 or halo_j < 0 or any(a.shape != coast_l.shape for a in (landfrac_l, true_lat_l, true_lon_l)):
+            raise ValueError("landfrac_l, true_lat_l, true_lon_l must be frames of coast_l's shape")
+        cdist = np.zeros_like(coast_l) if out is None else out
+        if cdist.shape != coast_l.shape or cdist.dtype != dt or not cdist.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous, of coast_l's shape and dtype")
+        rc = getattr(self.lib, f"sb_tile_get_dist_um_{_SFX[dt]}")(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i),
+                                                                 C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j),
+                                                                 C.c_int(sides), _p(coast_l), _p(landfrac_l), _p(true_lat_l),
+                                                                 _p(true_lon_l), _CT[dt](maxdist), _p(cdist))
+        self._chk(rc, "sb_tile_get_dist_um")
+        return cdist
+
     def band_get_edges(self, lsm_f, ci_f, halo, south, north, rule=1, out=None):
         """get_edges(rule, SB_BND_GLOBAL) for one latitude band in the band step's frame: lsm_f, ci_f are
         (ny + 2*halo, nx + 2*halo) with the ghost row next to the interior filled on every cut side (south / north False);
@@ -721,6 +767,23 @@ class Context:
         self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j),
                      _p(coast_l), _p(landfrac), _p(true_lat), _p(true_lon), _CT[dt](maxdist), _p(cdist),
                      C.c_void_p(stream) if stream else None), "sb_get_dist_um_win_dev")
+
+    def tile_get_edges_um_dev(self, dtype, nx, ny, halo_i, halo_j, ext_i, ext_j, sides, landfrac_l, icefrac_l, coast_l,
+                              stream=None):
+        """tile_get_edges_um on device frames (raw addresses); enqueues without synchronising."""
+        fn = getattr(self.lib, f"sb_tile_get_edges_um_{_SFX[np.dtype(dtype)]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), C.c_int(ext_i), C.c_int(ext_j),
+                     C.c_int(sides), _p(landfrac_l), _p(icefrac_l), _p(coast_l), C.c_void_p(stream) if stream else None),
+                  "sb_tile_get_edges_um_dev")
+
+    def tile_get_dist_um_dev(self, dtype, nx, ny, halo_i, halo_j, win_i, win_j, sides, coast_l, landfrac_l, true_lat_l,
+                             true_lon_l, cdist_l, maxdist=180.0, stream=None):
+        """tile_get_dist_um on device frames (raw addresses, coordinates included); enqueues without synchronising."""
+        dt = np.dtype(dtype)
+        fn = getattr(self.lib, f"sb_tile_get_dist_um_{_SFX[dt]}_dev")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j),
+                     C.c_int(sides), _p(coast_l), _p(landfrac_l), _p(true_lat_l), _p(true_lon_l), _CT[dt](maxdist),
+                     _p(cdist_l), C.c_void_p(stream) if stream else None), "sb_tile_get_dist_um_dev")
 
     def sigma_moments_dev(self, dtype, nx, ny, halo, sigma, moments5, stream=None):
         """Band-local sigma moments -> 5 doubles at device address moments5."""
