@@ -33,6 +33,12 @@
 !                                + 3) cells) per tile, reassembled and compared with the whole-domain get_edges_um ->
 !                                get_dist_um_win; prints the number of differing cells and the largest difference.  No steps
 !                                are run; output.bin holds the whole-domain distance field (interior) and the reassembled one
+!     umtileice                  umtile's cut with um2dice's sea ice: <nsteps> ice planes (no steps are run).  Per plane the
+!                                whole-domain get_edges_um -> get_dist_um_win; per tile um_tile_coast_open once, then
+!                                swap_bounds' copy of icefrac and um_tile_ice per plane, um_tile_ice_report,
+!                                um_tile_coast_close; reassembled and compared plane by plane: prints the number of differing
+!                                cells and the largest difference, and the reports summed over the tiles.  output.bin: per
+!                                plane the whole-domain distance field (interior) and the reassembled one
 !     host                       the reference's call shape: host arrays in, host arrays out (default)
 !     dev                        the fields live on the device (sb_dev_alloc); per step only theta, u, v go up
 !                                and the four outputs come back; seabreeze_diag_dev
@@ -82,7 +88,7 @@ program dummy_model
   integer(4) :: hdr(4)
 
   if (command_argument_count() < 3) then
-    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | um2dice | umtile | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
+    print *, 'usage: dummy_model <input.bin> <output.bin> <nsteps> [host | dev | um | um2d | um2dice | umtile | umtileice | status | bandsetup | radius | band <rank> <nranks> <idfile>]'
     error stop 2
   end if
   call get_command_argument(1, fin)
@@ -131,6 +137,8 @@ program dummy_model
     call run_um2dice()
   case ('umtile')
     call run_umtile()
+  case ('umtileice')
+    call run_umtileice()
   case ('status')
     call check_status()
   case ('bandsetup')
@@ -549,6 +557,97 @@ contains
     print '(a,1x,i0,1x,a,1x,es12.5)', 'umtile: differing cells', ndiff, 'largest difference', dmax
     write (uout) whole_l(1+ht:nxi+ht, 1+ht:nyi+ht), tiled
   end subroutine run_umtile
+
+  !---------------------------------------------------------------------------
+  ! A tile that follows moving sea ice: run_umtile's sub-domain, coordinates, window (+-hl), cut and frames (ht = hl + 1
+  ! ghost cells, copied from the whole fields in the role of swap_bounds: the edge cells beyond the domain's edge, which is
+  ! what the whole-domain get_edges_um holds in its ring) under run_um2dice's ice planes.  What a UM rank does per
+  ! timestep: one swap_bounds of icefrac -- the copy below -- then um_tile_ice.  The module holds one context, so the tiles
+  ! take turns: each opens its coast, runs the planes in order and closes it.
+  !---------------------------------------------------------------------------
+  subroutine run_umtileice()
+    use sea_breeze_diag_mod, only : get_edges_um, get_dist_um_win, um_tile_coast_open, um_tile_ice, um_tile_ice_report, &
+                                    um_tile_coast_close
+    integer :: hl, ht, nxi, nyi, i, j, ti, tj, x0, x1, y0, y1, nxt, nyt, gi, gj, ndiff, s
+    integer :: xcut(3), ycut(3), beyond(4)
+    integer(c_long_long) :: rep(4), total(4)
+    real :: dmax
+    real, allocatable :: lf_i(:,:), ci_s(:,:,:), tlat(:,:), tlon(:,:), whole_l(:,:), whole(:,:,:), tiled(:,:,:)
+    real, allocatable :: lf_t(:,:), ci_t(:,:), lat_t(:,:), lon_t(:,:), cd_t(:,:)
+    logical, allocatable :: shore(:,:)
+    hl = halo_size + 3; ht = hl + 1
+    nxi = nx - 2*hl; nyi = ny - 2*hl
+    if (nxi < 2 .or. nyi < 2) error stop 'umtileice mode: grid too small for the ghost frame'
+    if (nsteps < 1) error stop 'umtileice mode: needs at least one ice plane'
+    allocate(lf_i(nxi,nyi), ci_s(nxi,nyi,nsteps), tlat(nxi,nyi), tlon(nxi,nyi), whole_l(nxi+2*ht,nyi+2*ht), shore(nxi,nyi))
+    allocate(whole(nxi,nyi,nsteps), tiled(nxi,nyi,nsteps))
+    lf_i = land_frac(1+hl:nx-hl, 1+hl:ny-hl)
+    do j = 1, nyi
+      tlon(:, j) = lon(1+hl:nx-hl)
+    end do
+    do i = 1, nxi
+      tlat(i, :) = lat(1+hl:ny-hl)
+    end do
+    do j = 1, nyi                                ! sea cells that touch land
+      do i = 1, nxi
+        shore(i, j) = lf_i(i, j) == 0. .and. any(lf_i(max(i-1,1):min(i+1,nxi), max(j-1,1):min(j+1,nyi)) > 0.)
+      end do
+    end do
+    do s = 1, nsteps
+      ci_s(:, :, s) = ice_frac(1+hl:nx-hl, 1+hl:ny-hl)
+      do j = 1, nyi
+        if (mod(j + s, 3) == 0) then
+          where (shore(:, j)) ci_s(:, j, s) = 0.6
+        end if
+      end do
+      whole_l = 0.
+      call get_edges_um(whole_l, ci_s(:, :, s), lf_i)
+      call get_dist_um_win(lf_i, whole_l, tlat, tlon, hl, hl)
+      whole(:, :, s) = whole_l(1+ht:nxi+ht, 1+ht:nyi+ht)
+    end do
+    xcut = [0, nxi/2, nxi]; ycut = [0, nyi/2, nyi]
+    tiled = -1.
+    total = 0
+    do tj = 1, 2
+      do ti = 1, 2
+        x0 = xcut(ti); x1 = xcut(ti+1); y0 = ycut(tj); y1 = ycut(tj+1)
+        nxt = x1 - x0; nyt = y1 - y0
+        beyond = [x0, nxi - x1, y0, nyi - y1]
+        allocate(lf_t(nxt+2*ht,nyt+2*ht), ci_t(nxt+2*ht,nyt+2*ht), lat_t(nxt+2*ht,nyt+2*ht), lon_t(nxt+2*ht,nyt+2*ht))
+        allocate(cd_t(nxt+2*ht,nyt+2*ht))
+        do j = 1, nyt + 2*ht
+          do i = 1, nxt + 2*ht
+            gi = min(max(x0 + i - ht, 1), nxi); gj = min(max(y0 + j - ht, 1), nyi)
+            lf_t(i, j) = lf_i(gi, gj)
+            lat_t(i, j) = tlat(gi, gj); lon_t(i, j) = tlon(gi, gj)
+          end do
+        end do
+        cd_t = 0.
+        call um_tile_coast_open(lat_t, lon_t, ht, ht, hl, hl, beyond)
+        do s = 1, nsteps
+          do j = 1, nyt + 2*ht                     ! in the role of swap_bounds
+            do i = 1, nxt + 2*ht
+              gi = min(max(x0 + i - ht, 1), nxi); gj = min(max(y0 + j - ht, 1), nyi)
+              ci_t(i, j) = ci_s(gi, gj, s)
+            end do
+          end do
+          call um_tile_ice(lf_t, ci_t, cd_t)
+          tiled(x0+1:x1, y0+1:y1, s) = cd_t(1+ht:nxt+ht, 1+ht:nyt+ht)
+        end do
+        call um_tile_ice_report(rep)
+        total = total + rep
+        call um_tile_coast_close()
+        deallocate(lf_t, ci_t, lat_t, lon_t, cd_t)
+      end do
+    end do
+    ndiff = count(tiled /= whole)
+    dmax = maxval(abs(tiled - whole))
+    print '(a,1x,i0,1x,a,1x,es12.5)', 'umtileice: differing cells', ndiff, 'largest difference', dmax
+    print '(a,4(1x,i0))', 'umtileice: ice report', total
+    do s = 1, nsteps
+      write (uout) whole(:, :, s), tiled(:, :, s)
+    end do
+  end subroutine run_umtileice
 
   !---------------------------------------------------------------------------
   ! Argument checks of the status-returning entry points: they answer error = 1 before any device work

@@ -46,6 +46,7 @@ module sea_breeze_diag_mod
   public :: band_get_edges, band_get_dist, band_get_edges_dev, band_get_dist_dev
   public :: band_coast_open, band_ice_dev, band_ice_report, band_coast_close
   public :: um_coast_open, um_ice, um_ice_dev, um_ice_report, um_coast_close
+  public :: um_tile_coast_open, um_tile_ice, um_tile_ice_dev, um_tile_ice_report, um_tile_coast_close
   public :: search_radius, band_search_radius
   integer, parameter :: SB_UM_THETA_TO_T0 = 1, SB_UM_LEVEL_WALK = 2
 
@@ -73,6 +74,9 @@ module sea_breeze_diag_mod
 #define SB_UM_COAST_OPEN      "sb_um_coast_open_f64"
 #define SB_UM_ICE             "sb_um_ice_f64"
 #define SB_UM_ICE_DEV         "sb_um_ice_f64_dev"
+#define SB_UM_TILE_COAST_OPEN "sb_um_tile_coast_open_f64"
+#define SB_UM_TILE_ICE        "sb_um_tile_ice_f64"
+#define SB_UM_TILE_ICE_DEV    "sb_um_tile_ice_f64_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f64"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f64"
 #else
@@ -99,6 +103,9 @@ module sea_breeze_diag_mod
 #define SB_UM_COAST_OPEN      "sb_um_coast_open_f32"
 #define SB_UM_ICE             "sb_um_ice_f32"
 #define SB_UM_ICE_DEV         "sb_um_ice_f32_dev"
+#define SB_UM_TILE_COAST_OPEN "sb_um_tile_coast_open_f32"
+#define SB_UM_TILE_ICE        "sb_um_tile_ice_f32"
+#define SB_UM_TILE_ICE_DEV    "sb_um_tile_ice_f32_dev"
 #define SB_SEARCH_RADIUS      "sb_search_radius_f32"
 #define SB_BAND_SEARCH_RADIUS "sb_band_search_radius_f32"
 #endif
@@ -107,6 +114,7 @@ module sea_breeze_diag_mod
   ! the sides of a tile that are the domain's edge (tile_get_edges_um, tile_get_dist_um; include/seabreeze_hip.h: SB_TILE_*)
   integer, parameter :: SB_TILE_WEST = 1, SB_TILE_EAST = 2, SB_TILE_SOUTH = 4, SB_TILE_NORTH = 8
   integer(c_int), save :: um_shape(4) = 0     ! nx, ny, halo_i, halo_j of the open UM coast (um_coast_open)
+  integer(c_int), save :: um_tile_shape(4) = 0   ! the same of the open UM tile coast (um_tile_coast_open)
 
   interface band_get_dist       ! (maxdist as a real or as the integer literal, like get_dist)
     module procedure band_get_dist_r
@@ -302,6 +310,34 @@ module sea_breeze_diag_mod
       integer(c_long_long), intent(inout) :: rep(4)
     end function
     integer(c_int) function c_um_coast_close(ctx) bind(C, name="sb_um_coast_close")
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx
+    end function
+    integer(c_int) function c_um_tile_coast_open(ctx, nx, ny, hi, hj, wi, wj, beyond, tlat_l, tlon_l, maxdist, incremental) &
+        bind(C, name=SB_UM_TILE_COAST_OPEN)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nx, ny, hi, hj, wi, wj, incremental
+      integer(c_int), intent(in) :: beyond(4)
+      real(rk), value :: maxdist
+      real(rk), intent(in) :: tlat_l(*), tlon_l(*)
+    end function
+    integer(c_int) function c_um_tile_ice(ctx, lf, ci, cdist) bind(C, name=SB_UM_TILE_ICE)
+      import :: c_ptr, c_int, rk
+      type(c_ptr), value :: ctx
+      real(rk), intent(in) :: lf(*), ci(*)
+      real(rk), intent(inout) :: cdist(*)
+    end function
+    integer(c_int) function c_um_tile_ice_dev(ctx, lf, ci, cdist, stream) bind(C, name=SB_UM_TILE_ICE_DEV)
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ctx, lf, ci, cdist, stream
+    end function
+    integer(c_int) function c_um_tile_ice_report(ctx, rep) bind(C, name="sb_um_tile_ice_report")
+      import :: c_ptr, c_int, c_long_long
+      type(c_ptr), value :: ctx
+      integer(c_long_long), intent(inout) :: rep(4)
+    end function
+    integer(c_int) function c_um_tile_coast_close(ctx) bind(C, name="sb_um_tile_coast_close")
       import :: c_ptr, c_int
       type(c_ptr), value :: ctx
     end function
@@ -941,6 +977,77 @@ contains
     if (rc /= 0) call fail('um_coast_close', rc)
     um_shape = 0
   end subroutine um_coast_close
+
+  !---------------------------------------------------------------------------
+  ! One tile of the UM's 2-D decomposition whose coast moves with the sea ice (include/seabreeze_hip.h:
+  ! sb_um_tile_coast_open): what a UM rank calls, because um_ice keeps the interior-only rule and its field depends on the
+  ! cut.  Open once per landfrac -- true_latitude_l, true_longitude_l on tdims_l (nx+2*halo_i, ny+2*halo_j), degrees, ghost
+  ! cells filled, are copied; beyond(4): the domain's cells beyond the tile's west, east, south and north side (0: the
+  ! domain's edge); the window is +-win_i x +-win_j, each 0 .. 255; every side needs a halo of min(window, beyond) + 1 --
+  ! then, per timestep, one swap_bounds of icefrac_l and um_tile_ice: landfrac_l, icefrac_l and cdist_l on tdims_l.  Only
+  ! the interior of cdist_l is written -- the tile's cells of the whole-domain field -- and what a call left there must
+  ! still be there at the next one.  um_tile_ice_dev takes device frames and only enqueues on the context's stream.
+  !---------------------------------------------------------------------------
+  subroutine um_tile_coast_open(true_latitude_l, true_longitude_l, halo_i, halo_j, win_i, win_j, beyond, maxdist, incremental)
+    real, intent(in), contiguous :: true_latitude_l(:,:), true_longitude_l(:,:)
+    integer, intent(in) :: halo_i, halo_j, win_i, win_j, beyond(4)
+    real, intent(in), optional :: maxdist
+    logical, intent(in), optional :: incremental
+    real :: md
+    integer(c_int) :: rc, inc, nx, ny
+    if (any(shape(true_longitude_l) /= shape(true_latitude_l))) &
+      call fail('um_tile_coast_open: need true_latitude_l, true_longitude_l (nx+2*halo_i, ny+2*halo_j)', 1_c_int)
+    nx = int(size(true_latitude_l, 1) - 2*halo_i, c_int); ny = int(size(true_latitude_l, 2) - 2*halo_j, c_int)
+    md = 180.
+    if (present(maxdist)) md = maxdist
+    inc = 1_c_int
+    if (present(incremental)) inc = merge(1_c_int, 0_c_int, incremental)
+    call ensure_ctx()
+    rc = c_um_tile_coast_open(ctx, nx, ny, int(halo_i, c_int), int(halo_j, c_int), int(win_i, c_int), int(win_j, c_int), &
+                              int(beyond, c_int), true_latitude_l, true_longitude_l, real(md, rk), inc)
+    if (rc /= 0) call fail('um_tile_coast_open', rc)
+    um_tile_shape = [nx, ny, int(halo_i, c_int), int(halo_j, c_int)]
+  end subroutine um_tile_coast_open
+
+  subroutine um_tile_ice(landfrac_l, icefrac_l, cdist_l)
+    real, intent(in), contiguous :: landfrac_l(:,:), icefrac_l(:,:)
+    real, intent(inout), contiguous :: cdist_l(:,:)
+    integer(c_int) :: rc
+    integer :: want(2)
+    want = [um_tile_shape(1) + 2*um_tile_shape(3), um_tile_shape(2) + 2*um_tile_shape(4)]
+    if (um_tile_shape(1) < 1) call fail('um_tile_ice without um_tile_coast_open', 1_c_int)
+    if (any(shape(landfrac_l) /= want) .or. any(shape(icefrac_l) /= want) .or. any(shape(cdist_l) /= want)) &
+      call fail('um_tile_ice: need landfrac_l, icefrac_l, cdist_l (nx+2*halo_i, ny+2*halo_j) of the open coast', 1_c_int)
+    call ensure_ctx()
+    rc = c_um_tile_ice(ctx, landfrac_l, icefrac_l, cdist_l)
+    if (rc /= 0) call fail('um_tile_ice', rc)
+  end subroutine um_tile_ice
+
+  subroutine um_tile_ice_dev(landfrac_l, icefrac_l, cdist_l)
+    type(c_ptr), intent(in) :: landfrac_l, icefrac_l, cdist_l
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_um_tile_ice_dev(ctx, landfrac_l, icefrac_l, cdist_l, c_null_ptr)
+    if (rc /= 0) call fail('um_tile_ice_dev', rc)
+  end subroutine um_tile_ice_dev
+
+  ! (synchronises) um_ice_report's four fields for the tile coast
+  subroutine um_tile_ice_report(rep)
+    integer(c_long_long), intent(out) :: rep(4)
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rep = 0
+    rc = c_um_tile_ice_report(ctx, rep)
+    if (rc /= 0) call fail('um_tile_ice_report', rc)
+  end subroutine um_tile_ice_report
+
+  subroutine um_tile_coast_close()
+    integer(c_int) :: rc
+    call ensure_ctx()
+    rc = c_um_tile_coast_close(ctx)
+    if (rc /= 0) call fail('um_tile_coast_close', rc)
+    um_tile_shape = 0
+  end subroutine um_tile_coast_close
 
   !---------------------------------------------------------------------------
   ! ref: generic/sea_breeze_diag.f90:457-481

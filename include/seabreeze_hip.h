@@ -905,8 +905,8 @@ int sb_get_dist_um_win_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int halo
 /* coast_l overlapping an input of the edges call.                                    */
 /* The _dev forms take device pointers for every field and enqueue on `stream` (NULL: */
 /* the context's own): one kernel (edges), two (distance).  They do not synchronise,  */
-/* download or derive anything on the host.  Not served: a tile that follows moving   */
-/* sea ice (sb_um_ice_* keeps its interior-only rule), and the exchange itself.       */
+/* download or derive anything on the host.  A tile that follows moving sea ice:      */
+/* sb_um_tile_coast_open_* / sb_um_tile_ice_* below.  Not served: the exchange itself.*/
 /* -------------------------------------------------------------------------------- */
 #define SB_TILE_WEST 1   /* the tile's first column is the domain's first column */
 #define SB_TILE_EAST 2   /* the tile's last column is the domain's last column */
@@ -959,8 +959,10 @@ int sb_tile_get_dist_um_f32_dev(sb_ctx *ctx, int nx, int ny, int halo_i, int hal
 /* the whole interior with sb_get_edges_um's and sb_get_dist_um_win's kernels (for    */
 /* A/B runs, and for runs in which every tile changes).  SB_ERR_ARG: bad sizes, a     */
 /* halo below 1, a window outside 0 .. 255, NULL, already open.  The UM state is      */
-/* independent of the stream's (sb_diag_stream_coast) and the band's                  */
-/* (sb_band_coast_open_*) moving coasts: one context may hold all three.              */
+/* independent of the stream's (sb_diag_stream_coast), the band's                     */
+/* (sb_band_coast_open_*) and a UM tile's (sb_um_tile_coast_open_*) moving coasts:    */
+/* one context may hold all four.  On a decomposed run the interior-only rule makes   */
+/* this field depend on the cut: a rank of such a run opens the tile coast instead.   */
 /*                                                                                    */
 /* The rule is the UM's ice-aware land rule (:390-403) and sb_get_dist_um_win_*'s     */
 /* distance rule in every respect: interior sources and targets only, no wrap, no     */
@@ -1007,6 +1009,81 @@ int sb_um_ice_f64(sb_ctx *ctx, const double *landfrac_l, const double *icefrac_l
 int sb_um_ice_f32(sb_ctx *ctx, const float *landfrac_l, const float *icefrac_l, float *cdist_l);
 int sb_um_ice_report(sb_ctx *ctx, long long rep[4]);
 int sb_um_coast_close(sb_ctx *ctx);
+
+/* -------------------------------------------------------------------------------- */
+/* one tile of the UM's 2-D decomposition whose coast moves with the sea ice --       */
+/* sb_tile_get_edges_um + sb_tile_get_dist_um, kept up to date on the device,         */
+/* incrementally                                                                      */
+/* The UM runs decomposed and rebuilds its mask from icefrac at every timestep.       */
+/* sb_um_ice_* follows the ice but keeps the interior-only rule, so its field depends */
+/* on the cut; the tile setup calls above give the whole-domain field but cost the    */
+/* whole tile per call.  Here the context keeps the coast of the tile's SOURCE        */
+/* rectangle as a bit plane of its own; an ice call compares the new coast with the   */
+/* stored one in 64-cell words and computes again only the workgroups of the tile     */
+/* distance kernel (4 rows x 64 columns of the interior) a changed word can reach     */
+/* through the window -- a changed word of a neighbour's ghost cells included.        */
+/*                                                                                    */
+/* sb_um_tile_coast_open_*: every field of the ice calls is the rank's frame,         */
+/* (nx+2*halo_i, ny+2*halo_j) with the interior at (halo_i, halo_j), as in the tile   */
+/* calls.  beyond[4]: the number of DOMAIN cells beyond the tile's west, east, south  */
+/* and north side; 0 says that side is the domain's edge, any value >= the window     */
+/* that the window never sees the domain's end.  Sources are the coast cells of       */
+/* [-eW, nx+eE) x [-eS, ny+eN) in interior coordinates with e* = min(win, beyond*):   */
+/* the tile calls' reach with the domain's end stated, so a neighbour narrower than   */
+/* the window needs nothing of the caller.  Every side needs halo >= e* + 1 (the      */
+/* Sobel of the outermost source cell reads one cell further; on an edge side that is */
+/* the one-cell ring sb_get_edges_um_* reads).  Ghost cells beyond the domain hold    */
+/* what the whole-domain frame's ring holds there: the caller's, as at the            */
+/* whole-domain call's rim.  true_lat_l, true_lon_l (degrees) are HOST frames and are */
+/* copied to the device.  Allocates the context's tile planes and may synchronise.    */
+/* incremental = 0: every ice call computes the whole tile with the tile setup calls' */
+/* kernels (for A/B runs, and for runs in which every workgroup changes).  The state  */
+/* stands beside sb_um_coast_open_*'s: one context may hold both, and the stream's    */
+/* and the band's moving coasts as well.                                              */
+/*                                                                                    */
+/* sb_um_tile_ice_*_dev: landfrac_l, icefrac_l, cdist_l are DEVICE frames in the      */
+/* precision the coast was opened with.  Enqueues on `stream` (NULL: the context's    */
+/* own) one clear of [marks | changed-word counter], the delta kernel and the         */
+/* distance kernel; no synchronisation, no download, no host compare.  Only the       */
+/* interior of cdist_l is written: all of it by the first call, the marked workgroups */
+/* by later ones.  The caller's side of the contract:                                 */
+/*   * the content of landfrac_l (ghost cells within e* + 1 included) and the         */
+/*     coordinates stand while the coast is open;                                     */
+/*   * swap_bounds refreshes the ghost cells of icefrac_l within e* + 1 of the        */
+/*     interior before every ice call;                                                */
+/*   * the interior of cdist_l is left alone between calls;                           */
+/*   * the ghost cells of cdist_l are the caller's swap_bounds, as ever.              */
+/* sb_um_tile_ice_f64 / _f32 take HOST frames: they stage all three (cdist_l too),    */
+/* synchronise and return the interior of cdist_l; its ghost cells are untouched.     */
+/* Result: after every call the interior of cdist_l equals, bit for bit, the tile's   */
+/* cells of sb_get_edges_um_* followed by sb_get_dist_um_win_*(win_i, win_j) on the   */
+/* domain of which the frame is a cut-out -- same device, same precision -- wherever  */
+/* that call takes its wide kernel (any window that differs from its layout halo or   */
+/* exceeds 31); against its other kernel the documented 1e-12 / 2e-6 applies, as for  */
+/* the tile calls.  The arithmetic is always the wide kernel's.  The coast bit plane  */
+/* is the context's own: any other coast call on the context between two ice calls    */
+/* leaves the next ice call exact.                                                    */
+/* SB_ERR_ARG, with nothing enqueued, nothing written and the state untouched: bad    */
+/* sizes, a window outside 0 .. 255, a negative beyond, a halo below e* + 1 on any    */
+/* side, NULL, already open (open); not open, the other precision, NULL (ice calls,   */
+/* report, close).                                                                    */
+/*                                                                                    */
+/* sb_um_tile_ice_report (synchronises the device): sb_um_ice_report's four fields -- */
+/* [0] ice calls since the open [1] those after the first whose coast differed (-1 on */
+/* the whole path) [2] workgroup tiles the last call marked (the first call: all)     */
+/* [3] tiles of the interior, ceil(ny/4) * ceil(nx/64).  sb_um_tile_coast_close       */
+/* (synchronises the device) frees the planes.                                        */
+/* -------------------------------------------------------------------------------- */
+int sb_um_tile_coast_open_f64(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, const int beyond[4],
+                              const double *true_lat_l, const double *true_lon_l, double maxdist, int incremental);
+int sb_um_tile_coast_open_f32(sb_ctx *ctx, int nx, int ny, int halo_i, int halo_j, int win_i, int win_j, const int beyond[4],
+                              const float *true_lat_l, const float *true_lon_l, float maxdist, int incremental);
+int sb_um_tile_ice_f64_dev(sb_ctx *ctx, const double *landfrac_l, const double *icefrac_l, double *cdist_l, void *stream);
+int sb_um_tile_ice_f32_dev(sb_ctx *ctx, const float *landfrac_l, const float *icefrac_l, float *cdist_l, void *stream);
+int sb_um_tile_ice_f64(sb_ctx *ctx, const double *landfrac_l, const double *icefrac_l, double *cdist_l);
+int sb_um_tile_ice_f32(sb_ctx *ctx, const float *landfrac_l, const float *icefrac_l, float *cdist_l);
+int sb_um_tile_ice_report(sb_ctx *ctx, long long rep[4]);
+int sb_um_tile_coast_close(sb_ctx *ctx);
 
 /* -------------------------------------------------------------------------------- */
 /* swap_bounds -- ghost-cell fill of one latitude band of a multi-GPU run            */

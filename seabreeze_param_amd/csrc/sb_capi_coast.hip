@@ -1,6 +1,6 @@
 // sb_capi_coast.hip -- the coast setup of the C ABI: get_edges and get_dist on the whole grid, on one latitude band and in
-// the UM layout and on one tile of its 2-D decomposition, a band's and a UM-layout coast that move with the sea ice, and
-// search_radius.
+// the UM layout and on one tile of its 2-D decomposition, a band's, a UM-layout and a UM tile's coast that move with the sea
+// ice, and search_radius.
 #include "sb_ctx.hpp"
 #include "sb_ice_plan.hpp"
 
@@ -695,6 +695,109 @@ int um_ice_host(sb_ctx *c, const T *lf, const T *ci, T *cdist) {
     return s.finish();
 }
 
+// ---- one tile of the UM's 2-D decomposition whose coast moves with the sea ice (sb_um_tile_coast_open_*, sb_um_tile_ice_*) ----
+// sb_um_ice_* keeps the UM's interior-only rule, so on a decomposed run its field depends on the cut; the tile setup calls
+// give the whole-domain field but cost the whole tile per call.  Here the context keeps the coast of the tile's SOURCE
+// rectangle (the interior and e* = min(window, beyond*) ghost columns / rows on each side: sb_ice_plan.hpp) as a bit plane
+// of its own and the coordinate frames on the device; an ice call is one clear of [marks | changed-word counter],
+// k_edge_bits_delta's tile instance and k_dist_um_tile over the marked workgroups.  Nothing waits, nothing is exchanged.
+template <typename T>
+int um_tile_coast_open(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const int *beyond, const T *tlat_l,
+                       const T *tlon_l, T maxdist, int incremental) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    UmTileCoast &u = c->umt;
+    if (u.open) return fail(c, SB_ERR_ARG, "sb_um_tile_coast_open: already open (sb_um_tile_coast_close first)");
+    if (nx < 1 || ny < 1 || hi < 0 || hj < 0 || !beyond || !tlat_l || !tlon_l) return fail(c, SB_ERR_ARG, "bad um_tile_coast_open arguments");
+    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW)
+        return fail(c, SB_ERR_ARG, "um_tile_coast_open: the window +-" + std::to_string(wi) + " x +-" + std::to_string(wj) +
+                                       " needs 0 <= win_i, win_j <= SB_DIST_UM_MAX_WINDOW = " +
+                                       std::to_string(SB_DIST_UM_MAX_WINDOW) + " cells");
+    if (beyond[0] < 0 || beyond[1] < 0 || beyond[2] < 0 || beyond[3] < 0)
+        return fail(c, SB_ERR_ARG, "um_tile_coast_open: beyond[] counts the domain's cells beyond a side: 0 (the domain's edge) or more");
+    if ((double)(nx + 2.0 * hi) * (double)(ny + 2.0 * hj) > 2.0e9) return fail(c, SB_ERR_ARG, "grid too large");
+    const SbUmTileIcePlan pl = sb_um_tile_ice_plan(nx, ny, hi, hj, wi, wj, beyond, incremental);
+    if (!pl.ok) {
+        const SbTileReach r = sb_um_tile_ice_sources(wi, wj, beyond);
+        return fail(c, SB_ERR_ARG, "um_tile_coast_open: the halo " + std::to_string(hi) + " x " + std::to_string(hj) +
+                                       " is smaller than " + std::to_string((r.eW > r.eE ? r.eW : r.eE) + 1) + " x " +
+                                       std::to_string((r.eS > r.eN ? r.eS : r.eN) + 1) +
+                                       " (min(window, beyond) + 1 on every side: the Sobel reads the ring beyond the last source cell)");
+    }
+    const SbTileReach r = pl.reach;
+    const size_t nl = (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    int rc;
+    if ((rc = ensure(c, u.coords, 2 * nl * sizeof(T))) ||
+        (rc = ice_open(c, u.it, (size_t)(ny + r.eS + r.eN) * pl.nw * sizeof(uint64_t), pl.marks,
+                       pl.path == SbIcePath::WHOLE ? nl * sizeof(T) : 0, incremental, c->stream)))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(u.coords.p, tlat_l, nl * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync((T *)u.coords.p + nl, tlon_l, nl * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                                // (the caller's coordinates may go now)
+    u.esz = (int)sizeof(T);
+    u.nx = nx; u.ny = ny; u.hi = hi; u.hj = hj; u.wi = wi; u.wj = wj;
+    for (int i = 0; i < 4; ++i) u.beyond[i] = beyond[i];
+    u.maxdist = (double)maxdist;
+    u.open = true;
+    return SB_OK;
+}
+
+template <typename T>
+int check_um_tile_ice(sb_ctx *c, const T *lf, const T *ci, const T *cdist) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    const UmTileCoast &u = c->umt;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_tile_ice without sb_um_tile_coast_open");
+    if (u.esz != (int)sizeof(T)) return fail(c, SB_ERR_ARG, "sb_um_tile_ice: the UM tile coast was opened in the other precision");
+    if (!lf || !ci || !cdist) return fail(c, SB_ERR_ARG, "null array pointer");
+    return SB_OK;
+}
+
+template <typename T>
+int um_tile_ice_dev(sb_ctx *c, const T *lf, const T *ci, T *cdist, void *stream) {
+    int rc = check_um_tile_ice<T>(c, lf, ci, cdist);
+    if (rc) return rc;
+    UmTileCoast &u = c->umt;
+    const int nx = u.nx, ny = u.ny, hi = u.hi, hj = u.hj;
+    const SbUmTileIcePlan pl = sb_um_tile_ice_plan(nx, ny, hi, hj, u.wi, u.wj, u.beyond, u.it.incremental);
+    const T *tlat = (const T *)u.coords.p, *tlon = tlat + (size_t)(nx + 2 * hi) * (ny + 2 * hj);
+    const T maxdist = (T)u.maxdist;
+    hipStream_t st = stream_of(c, stream);
+    if (pl.path == SbIcePath::WHOLE) {
+        // the tile setup calls' chain on the context's own planes, with the reach from `beyond`
+        HIPCHK(c, sb_launch_edges_um_tile_reach<T>(lf, ci, (T *)u.it.coast.p, nx, ny, hi, hj, pl.reach, st));
+        HIPCHK(c, sb_launch_dist_um_tile_reach<T>((const T *)u.it.coast.p, lf, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj, pl.reach,
+                                                  maxdist, (uint64_t *)u.it.bits.p, st));
+    } else {
+        IceCall ic;
+        if ((rc = ice_begin(c, u.it, st, ic))) return rc;
+        HIPCHK(c, sb_launch_edge_bits_delta_um_tile<T>(lf, ci, (uint64_t *)u.it.bits.p, ic.marks, ic.rep, nx, ny, hi, hj, u.wi, u.wj,
+                                                       pl.reach, ic.first, st));
+        HIPCHK(c, sb_launch_dist_um_tile_dirty<T>(lf, tlat, tlon, cdist, nx, ny, hi, hj, u.wi, u.wj, pl.reach, maxdist,
+                                                  (const uint64_t *)u.it.bits.p, ic.marks, st));
+    }
+    u.it.calls++;
+    return SB_OK;
+}
+
+template <typename T>
+int um_tile_ice_host(sb_ctx *c, const T *lf, const T *ci, T *cdist) {
+    int rc = check_um_tile_ice<T>(c, lf, ci, cdist);
+    if (rc) return rc;
+    const UmTileCoast &u = c->umt;
+    const int NX = u.nx + 2 * u.hi;
+    const size_t nl = (size_t)NX * (u.ny + 2 * u.hj);
+    Stager s(c);
+    // (cdist in as well: later calls write the marked workgroups only, the rest of the interior is the caller's from the call before)
+    T *dl = s.in(lf, nl), *dc = s.in(ci, nl), *dcd = s.in((const T *)cdist, nl);
+    if (s.rc) return s.rc;
+    rc = um_tile_ice_dev<T>(c, dl, dc, dcd, nullptr);
+    if (rc) return rc;
+    // the interior only: the caller's ghost cells are untouched
+    hipError_t e = hipMemcpy2DAsync(cdist + (size_t)u.hj * NX + u.hi, (size_t)NX * sizeof(T), dcd + (size_t)u.hj * NX + u.hi,
+                                    (size_t)NX * sizeof(T), (size_t)u.nx * sizeof(T), (size_t)u.ny, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) return hipfail(c, e, "hipMemcpy2DAsync D2H");
+    return s.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -740,6 +843,25 @@ int sb_um_coast_close(sb_ctx *c) {
     HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
     for (DevBuf *d : {&u.coords, &u.lf})
         if (d->p) { (void)hipFree(d->p); d->p = nullptr; d->cap = 0; }
+    ice_free(u.it);
+    u.open = false;
+    return SB_OK;
+}
+
+int sb_um_tile_ice_report(sb_ctx *c, long long rep[4]) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    if (!rep) return fail(c, SB_ERR_ARG, "null report");
+    UmTileCoast &u = c->umt;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_tile_ice_report without sb_um_tile_coast_open");
+    return ice_report(c, u.it, sb_um_ice_marks(u.nx, u.ny), sb_um_ice_path(u.it.incremental) == SbIcePath::WHOLE, true, rep);
+}
+
+int sb_um_tile_coast_close(sb_ctx *c) {
+    if (!c) return fail(nullptr, SB_ERR_ARG, "null context");
+    UmTileCoast &u = c->umt;
+    if (!u.open) return fail(c, SB_ERR_ARG, "sb_um_tile_coast_close without sb_um_tile_coast_open");
+    HIPCHK(c, hipDeviceSynchronize());                           // (an ice call may still be reading the planes)
+    if (u.coords.p) { (void)hipFree(u.coords.p); u.coords.p = nullptr; u.coords.cap = 0; }
     ice_free(u.it);
     u.open = false;
     return SB_OK;
@@ -855,6 +977,16 @@ int sb_um_coast_close(sb_ctx *c) {
         return um_ice_dev<T>(c, lf, ci, cdist, stream);                                                             \
     }                                                                                                              \
     int sb_um_ice_##SFX(sb_ctx *c, const T *lf, const T *ci, T *cdist) { return um_ice_host<T>(c, lf, ci, cdist); } \
+    int sb_um_tile_coast_open_##SFX(sb_ctx *c, int nx, int ny, int hi, int hj, int wi, int wj, const int *beyond,  \
+                                    const T *tlat_l, const T *tlon_l, T maxdist, int incremental) {                \
+        return um_tile_coast_open<T>(c, nx, ny, hi, hj, wi, wj, beyond, tlat_l, tlon_l, maxdist, incremental);     \
+    }                                                                                                              \
+    int sb_um_tile_ice_##SFX##_dev(sb_ctx *c, const T *lf, const T *ci, T *cdist, void *stream) {                  \
+        return um_tile_ice_dev<T>(c, lf, ci, cdist, stream);                                                       \
+    }                                                                                                              \
+    int sb_um_tile_ice_##SFX(sb_ctx *c, const T *lf, const T *ci, T *cdist) {                                      \
+        return um_tile_ice_host<T>(c, lf, ci, cdist);                                                              \
+    }                                                                                                              \
     int sb_dist_window_##SFX(int nx, int ny, const T *lon, const T *lat, T maxdist, int *k) {                       \
         return dist_window<T>(nx, ny, lon, lat, maxdist, k);                                                        \
     }

@@ -1,6 +1,6 @@
 // sb_coast_common.hpp -- what the coast setup's kernels share: sb_coast_kernels.hip (regular grids: k_edges, k_dist,
 // k_dist_bits_small, k_dist_bits, k_dist_wide) and sb_um_coast_kernels.hip (the UM layout on curvilinear grids:
-// k_edges_um, k_dist_um, k_dist_um_wide, k_edges_um_tile, k_dist_um_tile) and sb_ice_kernels.hip (a moving coast: k_edge_bits_delta[_band|_um]).
+// k_edges_um, k_dist_um, k_dist_um_wide, k_edges_um_tile, k_dist_um_tile) and sb_ice_kernels.hip (a moving coast: k_edge_bits_delta[_band|_um|_um_tile]).
 // ref: sobel.f90:19-193, UM/vn10.7/sea_breeze_diag.F90:386-601
 // The Sobel block, the coast bit plane and its bit strings, the haversine term, the two forms of the epilogue (minimum a
 // per sweep class -> distance -> sweep-time reset -> sign) and the per-target walk of a window that fits one word.
@@ -167,6 +167,15 @@ struct EdgesUmTile {
     }
     __device__ __forceinline__ size_t dst(int x, int y) const { return (size_t)(y + oy) * ld + x + ox; }
     __device__ __forceinline__ int land(T l, T c) const { return EdgesUm<T>{}.land(l, c); }
+};
+// ... and the same rule for k_edge_bits_delta's tile instance (sb_um_tile_ice_*), which asks its policy for the cells it
+// forms edges of: the source rectangle of wx x wy cells, whose first cell is frame cell (ox, oy).  A type of its own, so
+// that k_edges_um_tile's instance carries what it carried.
+template <typename T>
+struct EdgesUmTileSrc : EdgesUmTile<T> {
+    int wx, wy;
+    __device__ __forceinline__ int cols() const { return wx; }
+    __device__ __forceinline__ int rows() const { return wy; }
 };
 
 // ---- the coast bit plane ----

@@ -26,7 +26,7 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
-// What every coast that moves with the sea ice keeps on the device (a stream's, a band's, the UM layout's): its own coast
+// What every coast that moves with the sea ice keeps on the device (a stream's, a band's, the UM layout's, a UM tile's): its own coast
 // bit plane (the context's `coastbits` and `umbits` are scratch of other get_dist calls), [marks | rep] and, on the whole
 // path, a coast plane.  ice_open .. ice_free below work on it; what is specific to a layout stays with the layout.
 struct IceTrack {
@@ -88,6 +88,19 @@ struct UmCoast {
     int esz = 0, nx = 0, ny = 0, hi = 0, hj = 0, wi = 0, wj = 0;
     double maxdist = 0.0;
     DevBuf coords, lf;
+    IceTrack it;
+};
+
+// One tile of the UM layout's 2-D decomposition whose coast moves with the sea ice (sb_um_tile_coast_open /
+// sb_um_tile_ice_*): the geometry it was opened for (beyond: the domain cells beyond the west, east, south and north
+// side), the coordinate FRAMES on the device (tlat | tlon), its planes (it: the bit plane covers the source rectangle of
+// sb_um_tile_ice_plan, one mark byte per workgroup of k_dist_um_tile over the interior, the whole path's coast is a
+// frame).  Independent of the other three moving coasts.
+struct UmTileCoast {
+    bool open = false;
+    int esz = 0, nx = 0, ny = 0, hi = 0, hj = 0, wi = 0, wj = 0, beyond[4] = {0, 0, 0, 0};
+    double maxdist = 0.0;
+    DevBuf coords;
     IceTrack it;
 };
 
@@ -178,6 +191,7 @@ struct sb_ctx {
     DiagStream ds;
     BandCoast bc;
     UmCoast um;
+    UmTileCoast umt;
 };
 
 // What a band step means to the diag code underneath travels as an argument: band_diag_dev builds one value per phase,

@@ -1,5 +1,5 @@
-// sb_ice_kernels.hip -- the coast of a domain whose sea ice moves (sb_diag_stream_ice_*, sb_band_ice_*, sb_um_ice_*): one
-// kernel that turns the land mask and a step's ice plane into the domain's coast bit plane and says what the difference
+// sb_ice_kernels.hip -- the coast of a domain whose sea ice moves (sb_diag_stream_ice_*, sb_band_ice_*, sb_um_ice_*,
+// sb_um_tile_ice_*): one kernel that turns the land mask and a step's ice plane into the domain's coast bit plane and says what the difference
 // can reach.
 //
 //   k_edge_bits_delta  a Sobel block of k_edges (sb_edges_each, sb_coast_common.hpp) whose flags are balloted into the
@@ -7,7 +7,7 @@
 //                      k_edges + k_coastbits pay.  A word belongs to one wave of one workgroup, so that wave reads the
 //                      stored word, and where the new one differs writes it, counts it and marks every (row, tile) of the
 //                      mark plane the word can reach -- the distance kernels under a Dist*Dirty policy then compute those
-//                      again and leave the rest of the resident cdist alone.  One body, three instances, which differ in
+//                      again and leave the rest of the resident cdist alone.  One body, four instances, which differ in
 //                      the Sobel policy and in the reach (sb_ice_plan.hpp: an SbIceReach in the rows and tiles of the
 //                      layout's own mark plane, from the function the host-only tests walk):
 //     the whole grid   EdgesIce: the f2py flavour's cell mapping and land rule (rule 0, lsm + ci > 0.4: ref sobel.f90:51,
@@ -22,6 +22,11 @@
 //                      64-column tile); DistUmDirty behind it.  EdgesUm keeps tail_by_index: that only says how lanes past
 //                      the ring are staged; lanes whose column is past nx still leave sb_edges_each before emit.
 //                      k_edges_um writes the same coast as a plane for the whole path.
+//     a UM tile        EdgesUmTileSrc over the tile's SOURCE rectangle in the rank's frame (EdgesUmTile's rule: the interior
+//                      and e* ghost columns / rows on each side, sb_ice_plan.hpp; 256-column blocks from rectangle column
+//                      0, so a word of the rectangle's bit plane belongs to one wave); sb_um_tile_ice_reach, the UM
+//                      layout's mark plane over the interior; DistUmTileDirty behind it.  k_edges_um_tile writes the
+//                      same coast as a plane for the whole path.
 // Marks are stores of 1 into a byte plane the host cleared ahead of the launch: stores that race write the same value.
 // rep[0] counts the changed words of this call (cleared with the marks); the wave that counts the first one adds one
 // to rep[1], the calls whose coast differed, unless the call is the domain's first (`first`: everything is marked by the
@@ -61,6 +66,13 @@ struct ReachUm {
     int nx, ny, wi, wj;
     __device__ __forceinline__ int tiles() const { return sb_um_ice_marks(nx, ny).tiles; }
     __device__ __forceinline__ SbIceReach operator()(int x0, int y) const { return sb_um_ice_reach(nx, ny, wi, wj, x0, y); }
+};
+struct ReachUmTile {
+    int nx, ny, wi, wj, eW, eS;                                  // nx, ny: the interior; (x0, s): a word of the source rectangle
+    __device__ __forceinline__ int tiles() const { return sb_um_ice_marks(nx, ny).tiles; }
+    __device__ __forceinline__ SbIceReach operator()(int x0, int s) const {
+        return sb_um_tile_ice_reach(nx, ny, wi, wj, eW, eS, x0, s);
+    }
 };
 
 // p.cols() x p.rows(): the cells of the bit plane (a band's source rows) -- from the policy, so that the Sobel and the
@@ -150,6 +162,25 @@ hipError_t sb_launch_edge_bits_delta_um(const T *lf, const T *ci, uint64_t *bits
     return launch_delta(lf, ci, bits, marks, rep, EdgesUm<T>{nx + 2 * hi, ny + 2 * hj, hi, hj}, ReachUm{nx, ny, wi, wj}, nx, ny,
                         first, st);
 }
+
+// ---- one tile of the UM layout's 2-D decomposition (sb_um_tile_ice_*) ----
+// lf, ci: the frame's first cell; r: the source rectangle (sb_um_tile_ice_sources); bits: its plane.
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_um_tile(const T *lf, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                             int ny, int hi, int hj, int wi, int wj, SbTileReach r, int first, hipStream_t st) {
+    // the ring lies inside the frame, and a changed word's reach inside the mark plane (e* <= the window: sb_ice_plan.hpp)
+    if (r.eW < 0 || r.eE < 0 || r.eS < 0 || r.eN < 0 || r.eW > wi || r.eE > wi || r.eS > wj || r.eN > wj || hi < r.eW + 1 ||
+        hi < r.eE + 1 || hj < r.eS + 1 || hj < r.eN + 1)
+        return hipErrorInvalidValue;
+    const int wx = nx + r.eW + r.eE, wy = ny + r.eS + r.eN;
+    const EdgesUmTileSrc<T> p{{nx + 2 * hi, ny + 2 * hj, hi - r.eW, hj - r.eS}, wx, wy};
+    return launch_delta(lf, ci, bits, marks, rep, p, ReachUmTile{nx, ny, wi, wj, r.eW, r.eS}, wx, wy, first, st);
+}
+
+template hipError_t sb_launch_edge_bits_delta_um_tile<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *,
+                                                             int, int, int, int, int, int, SbTileReach, int, hipStream_t);
+template hipError_t sb_launch_edge_bits_delta_um_tile<double>(const double *, const double *, uint64_t *, unsigned char *,
+                                                              unsigned *, int, int, int, int, int, int, SbTileReach, int, hipStream_t);
 
 template hipError_t sb_launch_edge_bits_delta_um<float>(const float *, const float *, uint64_t *, unsigned char *, unsigned *, int,
                                                         int, int, int, int, int, int, hipStream_t);

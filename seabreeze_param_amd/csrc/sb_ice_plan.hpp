@@ -1,7 +1,9 @@
 // sb_ice_plan.hpp -- what an ice call of a stream (sb_diag_stream_ice_*), of a latitude band (sb_band_ice_*) or of the UM
-// layout (sb_um_ice_*) decides: which path it takes, and what a changed word of the coast bit plane can reach.
-// sb_capi_stream.hip and sb_capi_coast.hip ask for the path, the three instances of k_edge_bits_delta (sb_ice_kernels.hip)
-// mark with the same sb_ice_reach / sb_band_ice_reach / sb_um_ice_reach the host-only tests walk (tests/plan_dump.cpp).
+// layout (sb_um_ice_*) or of one tile of its 2-D decomposition (sb_um_tile_ice_*) decides: which path it takes, and what a
+// changed word of the coast bit plane can reach.
+// sb_capi_stream.hip and sb_capi_coast.hip ask for the path, the four instances of k_edge_bits_delta (sb_ice_kernels.hip)
+// mark with the same sb_ice_reach / sb_band_ice_reach / sb_um_ice_reach / sb_um_tile_ice_reach the host-only tests walk
+// (tests/plan_dump.cpp, tests/um_tile_ice_plan_dump.cpp).
 // Every layout states its mark plane as one SbIceMarks (rows x tiles bytes) and its reach as one SbIceReach in the rows and
 // tiles OF THAT PLANE, so the kernel's mark loop, the distance kernels' early exit and the report read any of them alike.
 // Plain C++17: no HIP, no heap -- a host compiler builds it alone; under hipcc the functions are also device functions.
@@ -136,7 +138,8 @@ SB_ICE_HD SbIceMarks sb_um_ice_marks(int nx, int ny) {
 }
 
 // the row groups r0 .. r1 and the tiles a0 .. a1 (never empty; no second piece: nothing wraps) whose workgroups hold a
-// target the word at columns x0 .. x0+63 (x0 a multiple of 64, < nx) of interior row y (< ny) can move
+// target the word at columns x0 .. x0+63 (x0 a multiple of 64, < nx) of interior row y (< ny) can move.  (A UM tile's words
+// lie elsewhere -- x0 and y may be negative or beyond the interior: sb_um_tile_ice_reach below says why the clamps serve.)
 SB_ICE_HD SbIceReach sb_um_ice_reach(int nx, int ny, int wi, int wj, int x0, int y) {
     SbIceReach r;
     const int ra = y - wj < 0 ? 0 : y - wj, rb = y + wj > ny - 1 ? ny - 1 : y + wj;
@@ -167,6 +170,62 @@ inline SbUmIcePlan sb_um_ice_plan(int nx, int ny, int hi, int hj, int wi, int wj
     if (!p.ok) return p;
     p.path = sb_um_ice_path(incremental);
     p.nw = (nx + 63) / 64;
+    p.marks = sb_um_ice_marks(nx, ny);
+    return p;
+}
+
+// ---- one tile of the UM layout's 2-D decomposition (sb_um_tile_coast_open_*, sb_um_tile_ice_*; sb_capi_coast.hip) ----
+// Every field is the rank's frame of (nx + 2hi) x (ny + 2hj) cells with the interior at (hi, hj).  beyond[4]: the domain
+// cells beyond the tile's west, east, south and north side (0: that side is the domain's edge).  Sources are the coast
+// cells of the rectangle [-eW, nx+eE) x [-eS, ny+eN) in interior coordinates, e* = min(window, beyond*): sb_tile_reach
+// (sb_um_coast_kernels.hip) with the domain's end stated, so a neighbour narrower than the window needs nothing of the
+// caller (the setup calls leave that to a zeroed coast_l; an ice call has no coast_l).
+struct SbTileReach { int eW, eE, eS, eN; };
+
+inline SbTileReach sb_um_tile_ice_sources(int wi, int wj, const int beyond[4]) {
+    return SbTileReach{beyond[0] < wi ? beyond[0] : wi, beyond[1] < wi ? beyond[1] : wi, beyond[2] < wj ? beyond[2] : wj,
+                       beyond[3] < wj ? beyond[3] : wj};
+}
+
+// The bit plane spans exactly the source rectangle -- pitch ceil((nx+eW+eE)/64) words, origin (-eW, -eS), so a word is
+// aligned to the rectangle and may straddle the interior's west edge -- and the mark plane is sb_um_ice_marks(nx, ny): one
+// byte per workgroup of k_dist_um_tile, tiled from interior cell (0, 0).  k_dist_um_tile is um_dist_wide_body, whose
+// targets are as uncoupled as sb_um_ice_reach's argument needs (no ballot over targets, value-neutral exits).  A target
+// (xx, yy) of the interior reads the coast bits of rows yy-wj .. yy+wj and columns xx-wi .. xx+wi that lie inside the
+// rectangle (src_rows clips the rows, um_row_bits64's zeros beyond the plane the columns) and nothing else of the coast.
+// The word at rectangle columns x0 .. x0+63 of rectangle row s holds interior columns x0-eW .. x0-eW+63 of interior row
+// s-eS, so it can move the targets of rows max(s-eS-wj, 0) .. min(s-eS+wj, ny-1) and columns max(x0-eW-wi, 0) ..
+// min(x0-eW+63+wi, nx-1) and nothing else: sb_um_ice_reach of (x0-eW, s-eS), whose two clamps serve arguments that are
+// negative (a ghost word west or south of the interior) or beyond the interior (east, north) as they stand.  Neither
+// range is empty: e* <= the window gives x0-eW+63+wi >= 63 and s-eS+wj >= 0; x0 < nx+eW+eE gives x0-eW-wi < nx+eE-wi <= nx,
+// and s < ny+eS+eN gives s-eS-wj < ny likewise.  The same relation holds between sb_band_ice_reach and sb_ice_reach.
+SB_ICE_HD SbIceReach sb_um_tile_ice_reach(int nx, int ny, int wi, int wj, int eW, int eS, int x0, int s) {
+    return sb_um_ice_reach(nx, ny, wi, wj, x0 - eW, s - eS);
+}
+
+// What sb_um_tile_coast_open_* decides: ok == false for sizes, windows or a negative beyond it refuses and for a halo
+// below e* + 1 on any side (the Sobel of the outermost source cell reads one cell further; on an edge side, e* = 0, that
+// is the ring sb_get_edges_um_* reads); else the path (`incremental` alone, as sb_um_ice_path), the source rectangle and
+// the sizes of the planes.
+struct SbUmTileIcePlan {
+    bool ok;
+    SbIcePath path;
+    SbTileReach reach;
+    int nw;                      // words per row of the bit plane (ny + eS + eN rows)
+    SbIceMarks marks;            // row groups x tiles per group of the interior
+};
+
+inline SbUmTileIcePlan sb_um_tile_ice_plan(int nx, int ny, int hi, int hj, int wi, int wj, const int beyond[4], int incremental) {
+    SbUmTileIcePlan p{};
+    p.ok = nx >= 1 && ny >= 1 && wi >= 0 && wi <= 255 && wj >= 0 && wj <= 255 && beyond[0] >= 0 && beyond[1] >= 0 &&
+           beyond[2] >= 0 && beyond[3] >= 0;
+    if (!p.ok) return p;
+    const SbTileReach r = sb_um_tile_ice_sources(wi, wj, beyond);
+    p.ok = hi >= r.eW + 1 && hi >= r.eE + 1 && hj >= r.eS + 1 && hj >= r.eN + 1;
+    if (!p.ok) return p;
+    p.path = sb_um_ice_path(incremental);
+    p.reach = r;
+    p.nw = (nx + r.eW + r.eE + 63) / 64;
     p.marks = sb_um_ice_marks(nx, ny);
     return p;
 }

@@ -3,6 +3,7 @@
 #include "sb_device.hpp"
 #include "sb_diag_plan.hpp"
 #include "sb_dist_plan.hpp"
+#include "sb_ice_plan.hpp"
 
 #define SB_STATS_MAX_BLOCKS 2048
 #define SB_DIST_TY 4                // rows per k_dist tile
@@ -255,6 +256,28 @@ hipError_t sb_launch_edge_bits_delta_um(const T *lf, const T *ci, uint64_t *bits
 template <typename T>
 hipError_t sb_launch_dist_um_dirty(const T *landfrac_l, const T *tlat, const T *tlon, T *cdist, int nx, int ny, int hi, int hj,
                                    int wi, int wj, T maxdist, const uint64_t *bits, const unsigned char *marks, hipStream_t st);
+
+// One tile of the UM layout's 2-D decomposition whose coast moves with the sea ice (sb_um_tile_ice_*; sb_ice_kernels.hip,
+// sb_um_coast_kernels.hip, sb_ice_plan.hpp).  Every field is the tile's (nx + 2hi) x (ny + 2hj) frame (first cell); r: the
+// source rectangle (sb_um_tile_ice_sources: e* = min(window, cells of the domain beyond that side));
+// hipErrorInvalidValue unless e* <= the window and the halo holds e* + 1 cells on every side.  bits: (ny+eS+eN) *
+// ceil((nx+eW+eE)/64) words, the rectangle's plane; marks, rep: as sb_launch_edge_bits_delta_um, over the interior.
+template <typename T>
+hipError_t sb_launch_edge_bits_delta_um_tile(const T *lf, const T *ci, uint64_t *bits, unsigned char *marks, unsigned *rep, int nx,
+                                             int ny, int hi, int hj, int wi, int wj, SbTileReach r, int first, hipStream_t st);
+// ... and k_dist_um_tile over that bit plane, computing the marked workgroups of cdist_l's interior alone
+template <typename T>
+hipError_t sb_launch_dist_um_tile_dirty(const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx, int ny, int hi,
+                                        int hj, int wi, int wj, SbTileReach r, T maxdist, const uint64_t *bits,
+                                        const unsigned char *marks, hipStream_t st);
+// the whole path: sb_launch_edges_um_tile / sb_launch_dist_um_tile with the reach stated per side instead of by `sides`
+template <typename T>
+hipError_t sb_launch_edges_um_tile_reach(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, SbTileReach r,
+                                         hipStream_t st);
+template <typename T>
+hipError_t sb_launch_dist_um_tile_reach(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
+                                        int ny, int hi, int hj, int wi, int wj, SbTileReach r, T maxdist, uint64_t *bits,
+                                        hipStream_t st);
 
 // search_radius (sb_radius_kernels.hip): the radius of every band cell's window from mask alone.  The kernels work in
 // WINDOW coordinates: a row as the windows see it has W cells -- the nx cells of the circle (SB_BND_GLOBAL, a band;

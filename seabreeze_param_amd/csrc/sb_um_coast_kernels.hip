@@ -9,6 +9,7 @@
 //   k_dist_um_wide the same rule for a window of up to +-255 cells stated apart from the ghost width (sb_get_dist_um_win_*)
 //   k_dist_um_dirty, k_dist_um_wide_dirty  the two under DistUmDirty: only the workgroups an ice call marked (sb_um_ice_*)
 //   k_edges_um_tile, k_dist_um_tile  one tile of a 2-D decomposition: ghost cells in reach are sources (sb_tile_get_*_um_*)
+//   k_dist_um_tile_dirty  k_dist_um_tile under DistUmTileDirty: only the workgroups an ice call marked (sb_um_tile_ice_*)
 //
 // The UM's get_dist is a scatter from interior coast cells into a window that reaches into the halo; swap_bounds then
 // throws the halo writes away (:584-598).  So sources and targets are interior cells only -- no wrap, no clamp -- and
@@ -76,6 +77,13 @@ struct DistUmTile {
     // (x, y may be negative: a ghost cell west or south of the interior; the offset is taken modulo 2^64 and the cell lies
     // inside the frame)
     __device__ __forceinline__ size_t co(int x, int y, int) const { return (size_t)y * ld + x; }
+};
+// DistUmTileDirty (sb_um_tile_ice_*): DistUmTile's rows, columns and offsets with DistUmDirty's exit on the mark byte --
+// workgroup-uniform and ahead of every barrier, as there.  The launch is one workgroup per byte of the mark plane, so the
+// plane's pitch is the grid's width and the policy carries the pointer beside DistUmTile's two scalars and nothing else.
+struct DistUmTileDirty : DistUmTile {
+    const unsigned char *mark;
+    __device__ __forceinline__ bool skip(int group, int tile) const { return mark[(size_t)group * gridDim.x + tile] == 0; }
 };
 
 // The gather.  A workgroup holds UM_DIST_TY target rows of 64 columns (one wave per row).  Its reach is the
@@ -443,24 +451,40 @@ __global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_tile(const uint64_t *__
     um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
 }
 
-// what a tile call reaches beyond its interior on each side: `e` cells on a cut side, none on an edge side
-struct SbTileReach { int eW, eE, eS, eN; };
+template <typename T>
+__global__ __launch_bounds__(64 * UMW_TY) void k_dist_um_tile_dirty(const uint64_t *__restrict__ bits,
+                                                                    const T *__restrict__ landfrac, const T *__restrict__ tlat,
+                                                                    const T *__restrict__ tlon, T *__restrict__ cdist, int nx,
+                                                                    int ny, int hi, int hj, int wi, int wj, int nw, T maxdist,
+                                                                    DistUmTileDirty g) {
+    // (the pointers as in k_dist_um_tile; the bit plane is complete: k_edge_bits_delta's tile instance wrote it)
+    um_dist_wide_body<T>(bits, landfrac, tlat, tlon, cdist, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
+}
+
+// what a tile call reaches beyond its interior on each side (SbTileReach: sb_ice_plan.hpp): `e` cells on a cut side, none
+// on an edge side
 static inline SbTileReach sb_tile_reach(int sides, int ei, int ej) {
     return SbTileReach{(sides & SB_TILE_WEST) ? 0 : ei, (sides & SB_TILE_EAST) ? 0 : ei, (sides & SB_TILE_SOUTH) ? 0 : ej,
                        (sides & SB_TILE_NORTH) ? 0 : ej};
 }
 
 template <typename T>
-hipError_t sb_launch_edges_um_tile(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, int ei, int ej, int sides,
-                                   hipStream_t st) {
-    const SbTileReach r = sb_tile_reach(sides, ei, ej);
+hipError_t sb_launch_edges_um_tile_reach(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, SbTileReach r,
+                                         hipStream_t st) {
     // the ring the Sobel reads lies inside the frame: one cell beyond the written rectangle on every side
-    if (ei < 0 || ej < 0 || hi < r.eW + 1 || hi < r.eE + 1 || hj < r.eS + 1 || hj < r.eN + 1) return hipErrorInvalidValue;
+    if (r.eW < 0 || r.eE < 0 || r.eS < 0 || r.eN < 0 || hi < r.eW + 1 || hi < r.eE + 1 || hj < r.eS + 1 || hj < r.eN + 1)
+        return hipErrorInvalidValue;
     const int wx = nx + r.eW + r.eE, wy = ny + r.eS + r.eN;
     const EdgesUmTile<T> p{nx + 2 * hi, ny + 2 * hj, hi - r.eW, hj - r.eS};
     hipLaunchKernelGGL(k_edges_um_tile<T>, dim3((wx + 255) / 256, (wy + EDGE_ROWS - 1) / EDGE_ROWS), dim3(256), 0, st, lf, ci, coast,
                        wx, wy, p);
     return hipGetLastError();
+}
+template <typename T>
+hipError_t sb_launch_edges_um_tile(const T *lf, const T *ci, T *coast, int nx, int ny, int hi, int hj, int ei, int ej, int sides,
+                                   hipStream_t st) {
+    if (ei < 0 || ej < 0) return hipErrorInvalidValue;
+    return sb_launch_edges_um_tile_reach<T>(lf, ci, coast, nx, ny, hi, hj, sb_tile_reach(sides, ei, ej), st);
 }
 
 size_t sb_dist_um_tile_bits_bytes(int nx, int ny, int wi, int wj, int sides) {
@@ -468,13 +492,19 @@ size_t sb_dist_um_tile_bits_bytes(int nx, int ny, int wi, int wj, int sides) {
     return (size_t)(ny + r.eS + r.eN) * ((nx + r.eW + r.eE + 63) / 64) * sizeof(uint64_t);
 }
 
-template <typename T>
-hipError_t sb_launch_dist_um_tile(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
-                                  int ny, int hi, int hj, int wi, int wj, int sides, T maxdist, uint64_t *bits, hipStream_t st) {
-    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return hipErrorInvalidValue;
-    const SbTileReach r = sb_tile_reach(sides, wi, wj);
+static bool um_tile_reach_ok(int hi, int hj, int wi, int wj, const SbTileReach &r) {
+    if (wi < 0 || wi > SB_DIST_UM_MAX_WINDOW || wj < 0 || wj > SB_DIST_UM_MAX_WINDOW) return false;
+    // DistUmTile packs a reach into eight bits; a reach beyond the window holds no source
+    if (r.eW < 0 || r.eE < 0 || r.eS < 0 || r.eN < 0 || r.eW > wi || r.eE > wi || r.eS > wj || r.eN > wj) return false;
     // every source cell lies inside the frame
-    if (hi < r.eW || hi < r.eE || hj < r.eS || hj < r.eN) return hipErrorInvalidValue;
+    return hi >= r.eW && hi >= r.eE && hj >= r.eS && hj >= r.eN;
+}
+
+template <typename T>
+hipError_t sb_launch_dist_um_tile_reach(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
+                                        int ny, int hi, int hj, int wi, int wj, SbTileReach r, T maxdist, uint64_t *bits,
+                                        hipStream_t st) {
+    if (!um_tile_reach_ok(hi, hj, wi, wj, r)) return hipErrorInvalidValue;
     const int wx = nx + r.eW + r.eE, wy = ny + r.eS + r.eN, nw = (wx + 63) / 64, NX = nx + 2 * hi;
     // (two launches: the bit plane is complete before any cdist cell is written, so cdist_l may be coast_l)
     sb_launch_coastbits<T>(coast_l, bits, wx, wy, nw, NX, (size_t)(hj - r.eS) * NX + (hi - r.eW), st);
@@ -482,6 +512,31 @@ hipError_t sb_launch_dist_um_tile(const T *coast_l, const T *landfrac_l, const T
     const size_t o = (size_t)hj * NX + hi;                       // the interior's first cell (cdist_l: the body adds it itself)
     hipLaunchKernelGGL(k_dist_um_tile<T>, dim3((nx + 63) / 64, (ny + UMW_TY - 1) / UMW_TY), dim3(64 * UMW_TY), 0, st, bits,
                        landfrac_l + o, tlat_l + o, tlon_l + o, cdist_l, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t sb_launch_dist_um_tile(const T *coast_l, const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx,
+                                  int ny, int hi, int hj, int wi, int wj, int sides, T maxdist, uint64_t *bits, hipStream_t st) {
+    if (wi < 0 || wj < 0) return hipErrorInvalidValue;
+    return sb_launch_dist_um_tile_reach<T>(coast_l, landfrac_l, tlat_l, tlon_l, cdist_l, nx, ny, hi, hj, wi, wj,
+                                           sb_tile_reach(sides, wi, wj), maxdist, bits, st);
+}
+
+// k_dist_um_tile over a bit plane that is already complete (k_edge_bits_delta's tile instance wrote it: the source
+// rectangle r, pitch ceil((nx+eW+eE)/64) words), computing the marked workgroups of the interior alone.  Every pointer is
+// the frame's first cell; marks: one byte per workgroup, ceil(ny/4) x ceil(nx/64) -- the grid, which is the plane's pitch
+// DistUmTileDirty reads.
+template <typename T>
+hipError_t sb_launch_dist_um_tile_dirty(const T *landfrac_l, const T *tlat_l, const T *tlon_l, T *cdist_l, int nx, int ny, int hi,
+                                        int hj, int wi, int wj, SbTileReach r, T maxdist, const uint64_t *bits,
+                                        const unsigned char *marks, hipStream_t st) {
+    if (!um_tile_reach_ok(hi, hj, wi, wj, r)) return hipErrorInvalidValue;
+    const int nw = (nx + r.eW + r.eE + 63) / 64, NX = nx + 2 * hi;
+    const SbIceMarks m = sb_um_ice_marks(nx, ny);
+    const DistUmTileDirty g{{r.eW | (r.eS << 8) | (r.eN << 16), NX}, marks};
+    const size_t o = (size_t)hj * NX + hi;
+    hipLaunchKernelGGL(k_dist_um_tile_dirty<T>, dim3(m.tiles, m.rows), dim3(64 * UMW_TY), 0, st, bits, landfrac_l + o, tlat_l + o,
+                       tlon_l + o, cdist_l, nx, ny, hi, hj, wi, wj, nw, maxdist, g);
     return hipGetLastError();
 }
 
@@ -549,3 +604,17 @@ template hipError_t sb_launch_dist_um_tile<float>(const float *, const float *, 
                                                   int, int, int, int, int, float, uint64_t *, hipStream_t);
 template hipError_t sb_launch_dist_um_tile<double>(const double *, const double *, const double *, const double *, double *, int,
                                                    int, int, int, int, int, int, double, uint64_t *, hipStream_t);
+template hipError_t sb_launch_edges_um_tile_reach<float>(const float *, const float *, float *, int, int, int, int, SbTileReach,
+                                                         hipStream_t);
+template hipError_t sb_launch_edges_um_tile_reach<double>(const double *, const double *, double *, int, int, int, int, SbTileReach,
+                                                          hipStream_t);
+template hipError_t sb_launch_dist_um_tile_reach<float>(const float *, const float *, const float *, const float *, float *, int,
+                                                        int, int, int, int, int, SbTileReach, float, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um_tile_reach<double>(const double *, const double *, const double *, const double *, double *,
+                                                         int, int, int, int, int, int, SbTileReach, double, uint64_t *, hipStream_t);
+template hipError_t sb_launch_dist_um_tile_dirty<float>(const float *, const float *, const float *, float *, int, int, int, int,
+                                                        int, int, SbTileReach, float, const uint64_t *, const unsigned char *,
+                                                        hipStream_t);
+template hipError_t sb_launch_dist_um_tile_dirty<double>(const double *, const double *, const double *, double *, int, int, int,
+                                                         int, int, int, SbTileReach, double, const uint64_t *,
+                                                         const unsigned char *, hipStream_t);

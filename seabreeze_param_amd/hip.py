@@ -111,6 +111,7 @@ class Context:
         self.h = h
         self._stream = None          # (dtype, nx, ny) of the stream begun last (stream_begin)
         self._um = None              # (dtype, nx, ny, halo_i, halo_j) of the open UM coast (um_coast_open)
+        self._um_tile = None         # the same of the open UM tile coast (um_tile_coast_open)
 
     def close(self):
         if getattr(self, "h", None):
@@ -743,6 +744,63 @@ class Context:
     def um_coast_close(self):
         self._chk(self.lib.sb_um_coast_close(self.h), "sb_um_coast_close")
         self._um = None
+
+    def um_tile_coast_open(self, dtype, nx, ny, halo_i, halo_j, win_i, win_j, beyond, true_lat_l, true_lon_l, maxdist=180.0,
+                           incremental=True):
+        """Open the moving coast of one tile of a 2-D domain decomposition (include/seabreeze_hip.h:
+        sb_um_tile_coast_open): every field is the rank's (ny + 2*halo_j, nx + 2*halo_i) frame; true_lat_l, true_lon_l,
+        degrees, are host frames and are copied to the device.  beyond: the domain cells beyond the tile's west, east, south
+        and north side (0: the domain's edge).  The window is +-win_i x +-win_j, each 0 .. SB_DIST_UM_MAX_WINDOW; every side
+        needs halo >= min(win, beyond) + 1."""
+        dt = np.dtype(dtype)
+        true_lat_l = _host(true_lat_l, dt); true_lon_l = _host(true_lon_l, dt)
+        shape = (ny + 2 * halo_j, nx + 2 * halo_i)
+        if true_lat_l.shape != shape or true_lon_l.shape != shape:
+            raise ValueError(f"true_lat_l, true_lon_l must be {shape}")
+        if len(beyond) != 4:
+            raise ValueError("beyond must hold four counts: west, east, south, north")
+        b = (C.c_int * 4)(*[int(v) for v in beyond])
+        fn = getattr(self.lib, f"sb_um_tile_coast_open_{_SFX[dt]}")
+        self._chk(fn(self.h, C.c_int(nx), C.c_int(ny), C.c_int(halo_i), C.c_int(halo_j), C.c_int(win_i), C.c_int(win_j), b,
+                     _p(true_lat_l), _p(true_lon_l), _CT[dt](maxdist), C.c_int(1 if incremental else 0)),
+                  "sb_um_tile_coast_open")
+        self._um_tile = (dt, nx, ny, halo_i, halo_j)
+
+    def um_tile_ice_dev(self, dtype, landfrac_l, icefrac_l, cdist_l, stream=None):
+        """Enqueue the coast and distance update of the interior of cdist_l for this ice frame (device frames, raw
+        addresses, the precision the tile coast was opened with); no synchronisation."""
+        fn = getattr(self.lib, f"sb_um_tile_ice_{_SFX[np.dtype(dtype)]}_dev")
+        self._chk(fn(self.h, _p(landfrac_l), _p(icefrac_l), _p(cdist_l), C.c_void_p(stream) if stream else None),
+                  "sb_um_tile_ice_dev")
+
+    def um_tile_ice(self, landfrac_l, icefrac_l, cdist_l):
+        """The tile's ice call on host frames (ny + 2*halo_j, nx + 2*halo_i) of the precision the tile coast was opened
+        with: stages them, synchronises and writes the interior of cdist_l in place (its ghost cells are untouched; what
+        the call before left in its interior must still be there).  Returns cdist_l."""
+        if getattr(self, "_um_tile", None) is None:
+            raise SeabreezeHipError("um_tile_ice without um_tile_coast_open")
+        dt, nx, ny, hi, hj = self._um_tile
+        shape = (ny + 2 * hj, nx + 2 * hi)
+        landfrac_l = _host(landfrac_l, dt); icefrac_l = _host(icefrac_l, dt)
+        if landfrac_l.shape != shape or icefrac_l.shape != shape:
+            raise ValueError(f"landfrac_l and icefrac_l must be {shape}")
+        if not isinstance(cdist_l, np.ndarray) or cdist_l.shape != shape or cdist_l.dtype != dt or not cdist_l.flags.c_contiguous:
+            raise ValueError(f"cdist_l must be a C-contiguous {shape} array of the coast's dtype")
+        self._chk(getattr(self.lib, f"sb_um_tile_ice_{_SFX[dt]}")(self.h, _p(landfrac_l), _p(icefrac_l), _p(cdist_l)),
+                  "sb_um_tile_ice")
+        return cdist_l
+
+    def um_tile_ice_report(self):
+        """um_ice_report's four fields for the tile coast: ice calls since the open / those after the first whose coast
+        differed (-1 on the whole path) / workgroup tiles (4 rows x 64 columns of the interior) the last call marked / tiles
+        of the interior.  Synchronises."""
+        arr = (C.c_longlong * 4)()
+        self._chk(self.lib.sb_um_tile_ice_report(self.h, arr), "sb_um_tile_ice_report")
+        return dict(calls=arr[0], changed_calls=arr[1], tiles_marked=arr[2], tiles=arr[3])
+
+    def um_tile_coast_close(self):
+        self._chk(self.lib.sb_um_tile_coast_close(self.h), "sb_um_tile_coast_close")
+        self._um_tile = None
 
     def get_edges_um_dev(self, dtype, nx, ny, halo_i, halo_j, landfrac_l, icefrac_l, coast, stream=None):
         """UM-layout get_edges on device arrays (raw addresses); enqueues without synchronising."""
